@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the KGE scoring hot path on MI355X (contract: see the task prompt / DESIGN.md 7).
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,7 @@ bf16 tables, batch n=512.  One STEP = the two score blocks of a 1vsAll batch
 matrix -> 2*n*E scored triples per step, computed as the reference's KgeModel.score_sp_po
 (kge_model.py:749-789) does: both blocks from ONE two-sided launch (kge_score_sp_po; bit-identical
 to the two separate calls, whose per-launch figures are reported next to it as
-roofline.one_sided_launch).  Inputs (tables, index vectors) are resident in HBM before the
+roofline.one_sided_launch, --full).  Inputs (tables, index vectors) are resident in HBM before the
 timed region.  Data is synthetic (no datasets/network here): N(0, 0.1)
 tables (examples/toy-complex-train.yaml:18-22), uniform random queries.
 
@@ -42,13 +42,19 @@ E_WD, R_WD, DIM_WD = 4594485, 822, 256  # Wikidata5M shape (K5)
 F32_MFMA_PEAK_TF = 157.3  # MI355X_MICROARCH.md: dense f32 matrix peak
 BF16_MFMA_PEAK_TF = 2500.0  # MI355X_MICROARCH.md: dense bf16 matrix peak (no sparsity)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured streaming copy)
+DUMP_BYTES = 64 * 10**6 - 4096  # --dump-outputs: every file together, .npy headers included
+# Warm-up floor (steps) in front of the timed region, whatever --warmup asks: on MI355X the first ~60 ms of back-to-back
+# group launches after start-up run ~4 % slower per step than the rest (five regions of 2,000 steps behind 200 warm-up
+# steps: 0.0284 ms per step in the first, 0.0269-0.0274 in the other four).  8,192 steps = ~0.22 s.
+WARMUP_MIN_STEPS = 8192
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=500)
+    ap.add_argument("--warmup", type=int, default=500,
+                    help="untimed steps before the timed region (N = 1: at least WARMUP_MIN_STEPS are run)")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true",
@@ -68,11 +74,22 @@ def parse():
     ap.add_argument("--streams", type=int, default=None,
                     help="N > 1: batches in flight in the sharded step (batch k's exchange and scoring on HIP stream "
                          "k %% streams; default: 2 with the step as a hipGraph where that has checked out, else 1)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed region of K steps is run this many times; the median region is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed region of K steps is run this many times; the median region is reported "
+                         "(default 5; 1 in a --gpus 1 run without --full, whose K steps are the only timed ones)")
     ap.add_argument("--shape", choices=["wikidata5m", "fb15k"], default="wikidata5m",
                     help="N > 1 only: which sharded workload is the headline value (the other is reported beside it)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also measure and check everything beside the headline figure (the single-pass mode, "
+                         "the settled launch rate and roofline, the bit check of the group launch, the other legs, the "
+                         "counter passes, cpu_baseline); without it the run times the headline region and stops")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write the score blocks of the last timed step as DIR/score_sp.npy "
+                         "and DIR/score_po.npy (float32 [batch, E]; a fixed sample of rows when both exceed 64 MB)")
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full or a.gpus > 1 else 1
+    return a
 
 
 def make_inputs(rank, device, n):
@@ -1042,6 +1059,8 @@ def main():
     device = torch.device("cuda", local)
     # KGE_BENCH_FORCE_DIST=1: exercise the sharded step (RCCL init + all-gather) with one rank
     if world > 1 or os.environ.get("KGE_BENCH_FORCE_DIST") == "1":
+        if a.dump_outputs:
+            raise SystemExit("bench: --dump-outputs is for the single-GPU step (--gpus 1)")
         return main_sharded(a, world, rank, device)
 
     from kge_amd import engine
@@ -1143,12 +1162,32 @@ def main():
     # `value`: the PARITY-COMPLIANT mode -- split queries (KGE_FLAG_SPLIT_QUERY: q = q_hi + q_lo, f32-level parity on the
     # bf16 tables: ranks equal to float32 arithmetic's up to its own summation noise, tests/test_gpu_bshape_ranks.py).
     # The single-pass mode (query vector rounded to ONE bf16: training tolerance, 4 % of the ranks move against that
-    # bar) is timed the same way and reported beside it.
-    def measure(flags, tag, lanes):
+    # bar) is timed the same way and reported beside it (--full).
+    def dump_last_step(md):
+        """--dump-outputs: the score blocks the last timed step (the last batch of the last group launch) handed to its
+        caller, sp block and po block, float32 [n, E] each; a fixed sample of rows where both exceed DUMP_BYTES."""
+        import numpy as np
+        g, lane = md.last
+        last = md.group(g)[lane]["out"][g - 1]  # [n, 2, E]
+        torch.cuda.synchronize()
+        rows = torch.arange(n)
+        if 2 * n * E_FB * 4 > DUMP_BYTES:
+            keep = DUMP_BYTES // (2 * E_FB * 4)
+            rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for side, name in enumerate(("score_sp", "score_po")):
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), last[rows.to(device), side].cpu().numpy())
+
+    def measure(key, flags, tag, lanes):
         md = Mode(flags, tag, lanes)
-        md.run_steps(a.warmup)
+        md.run_steps(max(a.warmup, WARMUP_MIN_STEPS))
         md.run_steps(L)
+        md.group(a.steps % L or L)  # the buffers of a remainder group are made here, not inside the timed region
         el, regions, host_el = timed_regions(md.run_steps, torch.cuda.synchronize, a.steps, a.repeats)
+        if a.dump_outputs and key == "parity":
+            dump_last_step(md)
+        if not a.full:
+            return md, {"el": el, "regions": regions, "host": host_el, "lanes": md.lanes}, None
         bad = None
         md.run_steps(L * md.lanes)  # one full group per lane, in flight together: every lane's scores are checked
         for lane in range(md.lanes):
@@ -1166,26 +1205,68 @@ def main():
                     "settled_launches": launches}, None
 
     modes, res = {}, {}
-    for key, flags, tag in (("parity", engine.FLAG_SPLIT_QUERY, "split-query"), ("training", None, "single-pass")):
+    legs = (("parity", engine.FLAG_SPLIT_QUERY, "split-query"), ("training", None, "single-pass"))
+    for key, flags, tag in legs if a.full else legs[:1]:
         r = why = None
         if a.lanes > 1:
             try:
-                md, r, why = measure(flags, tag, a.lanes)
+                md, r, why = measure(key, flags, tag, a.lanes)
             except Exception as exc:  # lanes are an optimisation of the issue order: never lose the line to them
                 why = f"{type(exc).__name__}: {exc}"
                 torch.cuda.synchronize()
             if r is None:
                 print(f"bench: {tag}: {a.lanes} lanes failed ({why}); one lane", file=sys.stderr)
         if r is None:
-            md, r, why = measure(flags, tag, 1)
+            md, r, why = measure(key, flags, tag, 1)
             if r is None:
                 raise SystemExit(f"bench: {why}")
         modes[key], res[key] = md, r
-    if os.environ.get("KGE_BENCH_MAIN_ONLY") == "1":  # a quick check of the timed region alone
-        total = 2.0 * n * E_FB * a.steps
+    total = 2.0 * n * E_FB * a.steps
+    if a.full and os.environ.get("KGE_BENCH_MAIN_ONLY") == "1":  # a quick check of the two timed modes alone
         print(json.dumps({k: {"value": total / v["el"], "us_per_step": v["el"] / a.steps * 1e6, "lanes": v["lanes"],
                               "launch_us": v["launch_ms"] * 1e3, "host_us_per_step": v["host"] / a.steps * 1e6}
                           for k, v in res.items()}))
+        return
+
+    rp = res["parity"]
+    head = {
+        "metric": "scored triples/sec (1vsAll, ComplEx d=512)",
+        "value": total / rp["el"],
+        "unit": "scored triples/s",
+        # `value` / `ms_per_step` come from the contract's timed region: K = `steps` batches = ceil(K / group) launches
+        # behind an idle gap -- a BURST (the first launches of a burst run 25-45 % faster than sustained issue).
+        # `value_settled` (--full) is the same step at the settled rate: the average of >= 40 back-to-back group launches.
+        "value_kind": (f"settled: {a.steps} steps = {(a.steps + L - 1) // L} back-to-back group launches per timed region"
+                       if (a.steps + L - 1) // L >= 40 else
+                       f"burst: {a.steps} steps = {(a.steps + L - 1) // L} group launch(es) per timed region"),
+        "value_mode": "parity-compliant: split queries (q = q_hi + q_lo on the matrix cores; ranks equal to float32 "
+                      "arithmetic on the bf16 tables up to its summation noise).  The single-pass mode is "
+                      "`training_tolerance` (--full)",
+        "n_gpus": 1,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "repeats": a.repeats,
+        "ms_per_step": rp["el"] / a.steps * 1e3,
+        "regions_ms_per_step": [r / a.steps * 1e3 for r in rp["regions"]],
+        "host_issue_ms_per_step": rp["host"] / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic",
+        "config": {
+            "workload": "FB15k-237 shape ComplEx d=512 1vsAll scoring, bf16 tables, f32 scores: the score_sp and "
+                        "score_po blocks of a batch per step (KgeModel.score_sp_po), batches issued in groups of "
+                        "`group` -- one persistent launch per group (kge_score_queries_multi), which also builds the "
+                        "next group's query vectors; group k on HIP stream k % `group_launches_in_flight`; score rows "
+                        "on a 256-byte pitch",
+            "num_entities_per_gpu": E_FB, "num_relations": R_FB, "dim": DIM, "batch": n, "group": L,
+            "group_launches_in_flight": rp["lanes"],
+            "parallelism": "single GPU", "queries": "split (q_hi + q_lo)",
+        },
+    }
+    if not a.full:
+        print(json.dumps(head))
         return
 
     def roofline_of(key, kernel):
@@ -1211,7 +1292,6 @@ def main():
                 "score_row_pitch_floats": 2 * PITCH, "block2_offset_floats": PITCH,
                 "score_bytes_per_launch": L * n * 2 * E_FB * 4}
 
-    total = 2.0 * n * E_FB * a.steps
     extra = {}
     if not a.no_one_sided:
         # ---- one launch per batch (the round-3 step: kge_score_queries, pairs_bf16_v7_kernel, the next batch's queries
@@ -1419,7 +1499,6 @@ def main():
     else:
         extra_f32 = extra_rank = extra_neg = extra_eval = extra_train = None
 
-    rp = res["parity"]
     rt = res["training"]
     # roofline.traffic, measured by this run where it can be: two rocprofv3 --pmc child passes (pmc_traffic_live).  Not
     # when this process is itself being profiled (its own kernel trace would then hold the children's launches too).
@@ -1427,46 +1506,13 @@ def main():
     live = {} if (a.no_pmc or profiled) else pmc_traffic_live(L)
     tr_par, tr_trn = traffic_of("parity", L, live), traffic_of("training", L, live)
     out = {
-        "metric": "scored triples/sec (1vsAll, ComplEx d=512)",
-        "value": total / rp["el"],
-        "unit": "scored triples/s",
-        # `value` / `ms_per_step` come from the contract's timed region: K = `steps` batches = ceil(K / group) launches
-        # behind an idle gap -- a BURST (the first launches of a burst run 25-45 % faster than sustained issue).
-        # `value_settled` is the same step at the settled rate: the average of >= 40 back-to-back group launches.
-        "value_kind": (f"settled: {a.steps} steps = {(a.steps + L - 1) // L} back-to-back group launches per timed region"
-                       if (a.steps + L - 1) // L >= 40 else
-                       f"burst: {a.steps} steps = {(a.steps + L - 1) // L} group launch(es) per timed region"),
+        **head,
         "value_settled": 2.0 * n * E_FB * L / (rp["launch_ms"] * 1e-3),
         "ms_per_step_settled": rp["launch_ms"] / L,
         "value_vs_reference_ranks": "ranks are bit-exact against the oracle (float32 arithmetic on the bf16 tables in the "
                                     "kernels' summation order); against the live reference (torch's summation order) <= 12 "
                                     "of 12,000 ranks differ by one position for ComplEx / DistMult at this shape "
                                     "(tests/test_oracle_golden.py:131-190, tests/test_gpu_bshape_ranks.py)",
-        "value_mode": "parity-compliant: split queries (q = q_hi + q_lo on the matrix cores; ranks equal to float32 "
-                      "arithmetic on the bf16 tables up to its summation noise).  The single-pass mode is "
-                      "`training_tolerance` below",
-        "n_gpus": 1,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "repeats": a.repeats,
-        "ms_per_step": rp["el"] / a.steps * 1e3,
-        "regions_ms_per_step": [r / a.steps * 1e3 for r in rp["regions"]],
-        "host_issue_ms_per_step": rp["host"] / a.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic",
-        "config": {
-            "workload": "FB15k-237 shape ComplEx d=512 1vsAll scoring, bf16 tables, f32 scores: the score_sp and "
-                        "score_po blocks of a batch per step (KgeModel.score_sp_po), batches issued in groups of "
-                        "`group` -- one persistent launch per group (kge_score_queries_multi), which also builds the "
-                        "next group's query vectors; group k on HIP stream k % `group_launches_in_flight`; score rows "
-                        "on a 256-byte pitch",
-            "num_entities_per_gpu": E_FB, "num_relations": R_FB, "dim": DIM, "batch": n, "group": L,
-            "group_launches_in_flight": rp["lanes"],
-            "parallelism": "single GPU", "queries": "split (q_hi + q_lo)",
-        },
         "roofline": {**roofline_of("parity", "pairs_bf16_v8_kernel<ComplEx, SPLIT> (kge_score_queries_multi: one "
                                              "persistent launch = `group` two-sided batches, split queries: twice the "
                                              "matrix-core work per score)"),

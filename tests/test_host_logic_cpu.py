@@ -102,6 +102,22 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
     assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout)
 
 
+def test_bench_plain_run_times_its_steps_once(monkeypatch):
+    """A plain `--gpus 1` run times ONE region of exactly --steps steps; --full (and N > 1) keep the median of five."""
+    import importlib.util
+    import sys as _sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for argv, repeats, full in ((["--gpus", "1"], 1, False), (["--gpus", "1", "--full"], 5, True),
+                                (["--gpus", "2"], 5, False), (["--full", "--repeats", "3"], 3, True)):
+        monkeypatch.setattr(_sys, "argv", ["bench.py", "--steps", "7"] + argv)
+        a = bench.parse()
+        assert (a.steps, a.repeats, a.full, a.dump_outputs) == (7, repeats, full, None)
+    assert bench.DUMP_BYTES > 2 * bench.BATCH * bench.E_FB * 4  # the default batch's two blocks go out whole
+
+
 def test_bench_traffic_falls_back_to_the_committed_counter_passes():
     """`roofline.traffic`: bench.py spawns two rocprofv3 --pmc passes itself (pmc_traffic_live: round 6) and says so in
     `traffic_source`; where it cannot (no rocprofv3, --no-pmc, a failed pass) the figure is read from

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_queries.py -m gpu -q -x --timeout=60
 echo "pytest queries exit: $?" > $OUT/env.log
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_size.py tests/test_gpu_score_rank.py tests/test_gpu_ce.py tests/test_gpu_fuzz_shapes.py -m gpu -q --timeout=600 > $OUT/pytest_parity.log 2>&1
 echo "pytest parity exit: $?" >> $OUT/env.log
-timeout 600 python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench exit: $?" >> $OUT/env.log
 tail -n 3 $OUT/pytest_queries.log
 tail -n 3 $OUT/pytest_parity.log

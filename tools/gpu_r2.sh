@@ -21,7 +21,7 @@ echo "pytest new exit: $?" >> $OUT/env.log
 fi
 timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
 echo "smoke exit: $?" >> $OUT/env.log
-timeout 600 python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench exit: $?" >> $OUT/env.log
 if [ "$MODE" != "lite" ]; then
 timeout 300 python tools/v2_phases.py > $OUT/v2_phases.txt 2>&1
@@ -30,11 +30,11 @@ timeout 200 python tools/gemm16_phases.py > $OUT/gemm16_phases.txt 2>&1
 fi
 # the sharded step with ONE rank (RCCL init, exchange, padded slabs): the code path of bench.py --gpus N
 for SH in wikidata5m fb15k; do
-KGE_BENCH_FORCE_DIST=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 20 --warmup 3 --shape $SH --no-cpu-baseline > $OUT/bench_dist1_$SH.json 2> $OUT/bench_dist1_$SH.err
+KGE_BENCH_FORCE_DIST=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 20 --warmup 3 --shape $SH --no-cpu-baseline > $OUT/bench_dist1_$SH.json 2> $OUT/bench_dist1_$SH.err
 echo "bench dist1 $SH exit: $?" >> $OUT/env.log
 done
 cd /tmp
-B="python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-one-sided"
+B="python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-one-sided"
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof -o bench -- $B > $R/$OUT/prof_bench.json 2> $R/$OUT/prof.err
 echo "rocprof two-sided exit: $?" >> $R/$OUT/env.log
 if [ "$MODE" != "lite" ]; then
@@ -42,7 +42,7 @@ timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof1 -o one -- python $
 echo "rocprof one-sided exit: $?" >> $R/$OUT/env.log
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof1p -o one -- python $R/tools/one_sided.py --pad > $R/$OUT/prof_one_pad.txt 2> $R/$OUT/prof1p.err
 for C in FETCH_SIZE WRITE_SIZE; do
-timeout 300 rocprofv3 --pmc $C -d $R/$OUT/pmc_$C -o bench -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-one-sided > /dev/null 2> $R/$OUT/pmc_$C.err
+timeout 300 rocprofv3 --pmc $C -d $R/$OUT/pmc_$C -o bench -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-one-sided > /dev/null 2> $R/$OUT/pmc_$C.err
 echo "pmc $C exit: $?" >> $R/$OUT/env.log
 timeout 300 rocprofv3 --pmc $C -d $R/$OUT/pmc1_$C -o one -- python $R/tools/one_sided.py --steps 20 > /dev/null 2> $R/$OUT/pmc1_$C.err
 timeout 300 rocprofv3 --pmc $C -d $R/$OUT/pmc1p_$C -o one -- python $R/tools/one_sided.py --steps 20 --pad > /dev/null 2> $R/$OUT/pmc1p_$C.err

@@ -13,15 +13,15 @@ KGE_BSHAPE_LOG=$R/$OUT/bshape_ranks.jsonl KGE_PLUGIN_LOG=$R/$OUT/plugin_gpu.json
 echo "pytest all exit: $?" >> $OUT/env.log
 timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
 echo "smoke exit: $?" >> $OUT/env.log
-timeout 900 python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench exit: $?" >> $OUT/env.log
 cd /tmp
-B="python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-one-sided --streams 1"  # one launch at a time: the trace's average duration is roofline.avg_launch_us
+B="python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-one-sided --streams 1"  # one launch at a time: the trace's average duration is roofline.avg_launch_us
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof -o bench -- $B > $R/$OUT/prof_bench.json 2> $R/$OUT/prof.err
 echo "rocprof two-sided exit: $?" >> $R/$OUT/env.log
 if [ "$MODE" != "nopmc" ]; then
 for C in FETCH_SIZE WRITE_SIZE; do
-timeout 300 rocprofv3 --pmc $C -d $R/$OUT/pmc_$C -o bench -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-one-sided --streams 1 > /dev/null 2> $R/$OUT/pmc_$C.err
+timeout 300 rocprofv3 --pmc $C -d $R/$OUT/pmc_$C -o bench -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-one-sided --streams 1 > /dev/null 2> $R/$OUT/pmc_$C.err
 echo "pmc $C exit: $?" >> $R/$OUT/env.log
 done
 fi

@@ -9,7 +9,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 # (1) per-kernel time of the bench command (the short form: main timed regions + legs)
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kstats -o bench -- python $R/bench.py --steps 40 --warmup 8 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kstats.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kstats -o bench -- python $R/bench.py --full --steps 40 --warmup 8 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kstats.err
 echo "kernel stats exit: $?" > $OUT/env.log
 # (2) HBM bytes of the group launch, separate passes
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -46,7 +46,7 @@ with open(out + "/rank_pmc.txt", "w") as f:
         con = sqlite3.connect(db)
         rows = list(con.execute("select name,total_calls,total_duration,average,percentage from top_kernels"))
         with open(out + "/kernel_stats.txt", "w") as g:
-            g.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 40 --warmup 8 --no-cpu-baseline (durations in us)\n")
+            g.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline (durations in us)\n")
             g.write(f"{'kernel':122s} {'calls':>6s} {'total_us':>11s} {'avg_us':>9s} {'pct':>6s}\n")
             for r in rows[:40]:
                 g.write(f"{r[0][:120]:122s} {r[1]:>6} {float(r[2]):11.1f} {float(r[3]):9.2f} {float(r[4]):6.2f}\n")

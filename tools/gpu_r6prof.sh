@@ -9,12 +9,12 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $R
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench exit: $?" > $OUT/env.log
-timeout 900 env KGE_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err
+timeout 900 env KGE_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err
 echo "bench dist1 exit: $?" >> $OUT/env.log
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kstats -o bench -- python $R/bench.py --steps 40 --warmup 8 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kstats.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kstats -o bench -- python $R/bench.py --full --steps 40 --warmup 8 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kstats.err
 echo "kernel stats exit: $?" >> $OUT/env.log
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $C -d $OUT/pmc_$C -o v8 -- python $R/tools/v8_pmc_target.py > /dev/null 2> $OUT/pmc_$C.err
@@ -46,7 +46,7 @@ for db in glob.glob(f"{out}/kstats/**/*_results.db", recursive=True):
     con = sqlite3.connect(db)
     rows = list(con.execute("select name,total_calls,total_duration,average,percentage from top_kernels"))
     with open(out + "/kernel_stats.txt", "w") as g:
-        g.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 40 --warmup 8 --no-cpu-baseline (durations in us)\n")
+        g.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline (durations in us)\n")
         g.write(f"{'kernel':122s} {'calls':>6s} {'total_us':>11s} {'avg_us':>9s} {'pct':>6s}\n")
         for r in rows[:45]:
             g.write(f"{r[0][:120]:122s} {r[1]:>6} {float(r[2]):11.1f} {float(r[3]):9.2f} {float(r[4]):6.2f}\n")
