@@ -263,6 +263,22 @@ int kge_score_neg(const kge_tables* t, kge_index s, kge_index p, kge_index o,
                   int64_t neg_ld, int64_t num_neg, float* out, int64_t ldo,
                   void* stream);
 
+/* Negative-sampling scores with SHARED samples (negative_sampling.shared: true): the [n, K] block of
+ * NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score, kge/util/sampler.py:428-463, 537-578
+ * (and, for the "triple" implementation TransE / RotatE are forced to, of samples() at sampler.py:412-426, 503-535
+ * scored through BatchNegativeSample.score, sampler.py:291-306), K = num_unique + num_repeat:
+ *   out[i*ldo + c], c < num_unique   score of triple i with `slot` (0 / 2) replaced by unique[c] -- by the spare
+ *                                    unique[num_unique] where drop != NULL and drop[i] == c
+ *   out[i*ldo + num_unique + r]      = column repeat[r] (< num_unique) of the same row
+ * drop == NULL: naive sharing, `unique` has num_unique ids.  drop != NULL: default sharing, `unique` has
+ * num_unique + 1 ids (the last is the spare), drop[i] in [0, num_unique], drop[i] == num_unique uses no spare.
+ * repeat may be NULL when num_repeat == 0.  Every target row is fetched once per workgroup (32 positives x 32
+ * columns) and shared from LDS; the scores are bit-identical to kge_score_neg on the materialised samples; nothing
+ * outside [n, K] is written.  Rows too wide for the LDS tile (f32 dim > 1024, bf16 dim > 2048): KGE_ERR_UNSUPPORTED. */
+int kge_score_neg_shared(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                         const void* unique, int32_t unique_itype, int64_t num_unique, const int64_t* drop,
+                         const int64_t* repeat, int64_t num_repeat, float* out, int64_t ldo, void* stream);
+
 /* ---- embedding-level scoring (dense inputs, no gather) ----------------- */
 /* RelationalScorer.score_emb.  `t` supplies scorer, dtype, dim, rel_dim and
  * l_norm only (t->ent/rel ignored).  SPO: all three [n, *] -> out[n];
@@ -849,6 +865,24 @@ int kge_score_neg_bwd_accum_sorted(const kge_tables* t, kge_index s, kge_index p
                                    const float* gout, int64_t ldg, const float* scores, int64_t lds,
                                    float* grad_ent, int64_t grad_ent_ld, float* grad_rel,
                                    int64_t grad_rel_ld, float* rel_scratch, void* stream);
+
+/* Backward of kge_score_neg_shared (replaces autograd through the sampler's indexing of the score matrix --
+ * kge/util/sampler.py:450-460, 559-575 -- and through the scoring behind it, called at
+ * kge/job/train_negative_sampling.py:142-163): gradients of sum_{i,c} gout[i*ldg + c] * out[i, c] ACCUMULATED into
+ * the dense table gradients like kge_score_neg_bwd_accum.  gout is folded over the repeat columns and the drop rule
+ * into one weight per (positive, physical row); a positive's relation / fixed entity row gradients are summed in
+ * registers over a tile of rows, a physical row's gradient over a tile of positives: one atomic row flush per
+ * (owner, tile), none per occurrence.  `scores` = the forward output (row pitch lds; needed for TransE / RotatE with
+ * l_norm != 1, may be NULL otherwise).  workspace: kge_score_neg_shared_workspace_bytes(t, n, num_unique) bytes of
+ * device scratch, 16-byte aligned (too small: KGE_ERR_WORKSPACE).  f32 tables, dim <= 1024; anything else
+ * KGE_ERR_UNSUPPORTED. */
+int64_t kge_score_neg_shared_workspace_bytes(const kge_tables* t, int64_t n, int64_t num_unique);
+int kge_score_neg_shared_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                                   const void* unique, int32_t unique_itype, int64_t num_unique, const int64_t* drop,
+                                   const int64_t* repeat, int64_t num_repeat, const float* gout, int64_t ldg,
+                                   const float* scores, int64_t lds, float* grad_ent, int64_t grad_ent_ld,
+                                   float* grad_rel, int64_t grad_rel_ld, void* workspace, int64_t workspace_bytes,
+                                   void* stream);
 
 /* Backward of kge_score_emb (dense embeddings).  SPO: g_s,g_o [n,dim], g_p [n,rel_dim].
  * SP_: g_s [n,dim], g_p [n,rel_dim], g_o [m,dim].  PO_: g_o [n,dim], g_p, g_s [m,dim]. */

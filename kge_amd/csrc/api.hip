@@ -11,6 +11,15 @@ int run_spo(int scorer, int dtype, bool neg_mode, const Operand& S, const Operan
             const Operand& O, int d, int dr, long long n, int slot, const void* neg,
             int neg_itype, long long neg_ld, long long K, float lp, float* out,
             long long ldo, hipStream_t st);
+int run_neg_shared(int scorer, int dtype, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                   long long n, int slot, const Index& uniq, long long Uc, const long long* drop, const long long* rep,
+                   long long K, float lp, float* out, long long ldo, hipStream_t st);
+long long neg_shared_workspace_bytes(long long n, long long P);
+int run_neg_shared_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                             long long n, int slot, const Index& uniq, long long Uc, const long long* drop,
+                             const long long* rep, long long nrep, const float* gout, long long ldg,
+                             const float* scores, long long lds, float* ge, long long ge_ld, float* gr, long long gr_ld,
+                             void* ws, long long ws_bytes, hipStream_t st);
 int run_pairs_exact(int scorer, int dtype, bool use_mfma, const Operand& A, const Operand& R,
                     const Operand& TG, int dir, int d, int dr, long long n, long long m,
                     float lp, float* out, long long ldo, hipStream_t st, bool round_query = true,
@@ -723,6 +732,62 @@ int kge_score_neg(const kge_tables* t, kge_index s, kge_index p, kge_index o, in
   return run_spo(t->scorer, t->dtype, true, ent_op(t, s), rel_op(t, p), ent_op(t, o),
                  (int)t->dim, (int)t->rel_dim, n, slot, neg, neg_itype, neg_ld, num_neg,
                  t->l_norm, out, ldo, (hipStream_t)stream);
+}
+
+// ---- shared negative samples (sampler.py:428-463, 537-578) ----
+static int check_shared(const kge_tables* t, int64_t n, int slot, const void* unique, int32_t unique_itype,
+                        int64_t num_unique, const int64_t* repeat, int64_t num_repeat) {
+  int rc = check_tables(t, true);
+  if (rc) return rc;
+  if (n < 0 || num_unique < 0 || num_repeat < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
+  if (unique_itype != KGE_I32 && unique_itype != KGE_I64) return KGE_ERR_INVALID_ARG;
+  if (num_repeat > 0 && (!repeat || num_unique == 0)) return KGE_ERR_INVALID_ARG;
+  if (n * (num_unique + num_repeat) > 0 && !unique) return KGE_ERR_INVALID_ARG;
+  return KGE_OK;
+}
+
+int kge_score_neg_shared(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                         const void* unique, int32_t unique_itype, int64_t num_unique, const int64_t* drop,
+                         const int64_t* repeat, int64_t num_repeat, float* out, int64_t ldo, void* stream) {
+  KGE_RANGE();
+  int rc = check_shared(t, n, slot, unique, unique_itype, num_unique, repeat, num_repeat);
+  if (rc) return rc;
+  const int64_t K = num_unique + num_repeat;
+  if (n * K > 0 && !out) return KGE_ERR_INVALID_ARG;
+  if (ldo < K) return KGE_ERR_INVALID_ARG;
+  if (n == 0 || K == 0) return KGE_OK;
+  if ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false))) return rc;
+  return run_neg_shared(t->scorer, t->dtype, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, (int)t->rel_dim, n,
+                        slot, Index{unique, 1, unique_itype}, num_unique, (const long long*)drop,
+                        (const long long*)repeat, K, t->l_norm, out, ldo, (hipStream_t)stream);
+}
+
+int64_t kge_score_neg_shared_workspace_bytes(const kge_tables* t, int64_t n, int64_t num_unique) {
+  if (check_tables(t, false) != KGE_OK || n <= 0 || num_unique <= 0) return 0;
+  return neg_shared_workspace_bytes(n, num_unique + 1);
+}
+
+int kge_score_neg_shared_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                                   const void* unique, int32_t unique_itype, int64_t num_unique, const int64_t* drop,
+                                   const int64_t* repeat, int64_t num_repeat, const float* gout, int64_t ldg,
+                                   const float* scores, int64_t lds, float* grad_ent, int64_t grad_ent_ld,
+                                   float* grad_rel, int64_t grad_rel_ld, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  KGE_RANGE();
+  int rc = check_shared(t, n, slot, unique, unique_itype, num_unique, repeat, num_repeat);
+  if (rc) return rc;
+  const int64_t K = num_unique + num_repeat;
+  if (n * K > 0 && (!gout || !grad_ent || !grad_rel)) return KGE_ERR_INVALID_ARG;
+  if (ldg < K || (scores && lds < K)) return KGE_ERR_INVALID_ARG;
+  if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
+  if (n == 0 || K == 0) return KGE_OK;
+  if (t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
+  if ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false))) return rc;
+  return run_neg_shared_bwd_accum(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
+                                  (int)t->rel_dim, n, slot, Index{unique, 1, unique_itype}, num_unique,
+                                  (const long long*)drop, (const long long*)repeat, num_repeat, gout, ldg, scores, lds,
+                                  grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, workspace, workspace_bytes,
+                                  (hipStream_t)stream);
 }
 
 // ---- LookupEmbedder.embed: gathered entity rows and relation rows of a batch, one launch

@@ -8,6 +8,7 @@ Function <-> reference map (paths relative to the reference tree):
   score_spo / score_sp / score_po / score_sp_po   KgeModel.score_*     kge/model/kge_model.py:663-789
   score_emb                                        RelationalScorer.score_emb  kge_model.py:151-213
   score_neg                                        BatchNegativeSample.score   kge/util/sampler.py:263-306
+  score_neg_shared                                 Naive/DefaultSharedNegativeSample.score  kge/util/sampler.py:428-463, 537-578
   rank_counts                                      EntityRankingJob._filter_and_rank  kge/job/eval_entity_ranking.py:533-596
 """
 import ctypes
@@ -19,7 +20,7 @@ from . import _lib
 from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT_QUERY, I32, I64, PO_,
                    SCORERS, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
 
-__all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg",
+__all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "shared_samples",
            "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
            "FLAG_SPLIT_QUERY", "reserve_cus", "Queries", "build_queries", "score_queries", "ScorePipeline"]
 
@@ -765,6 +766,117 @@ def score_neg_bwd_accum(t: Tables, s, p, o, slot: int, neg: torch.Tensor, gout, 
         return False
     if rc:
         _lib.check(rc, "kge_score_neg_bwd_accum")
+    return True
+
+
+# ---- shared negative samples (negative_sampling.shared: true; sampler.py:383-585) ----------------------------------
+# the forward kernel's tile (csrc/score_neg_shared.hip: SNS_TN positives x SNS_TU output columns per workgroup)
+NEG_SHARED_TILE_POSITIVES = 32
+NEG_SHARED_TILE_COLUMNS = 32
+
+
+def neg_shared_supported(dtype, d: int, n: int) -> bool:
+    """Does kge_score_neg_shared take rows of `d` elements of `dtype` and `n` positives?  (33 rows of the LDS tile in
+    160 KB: float32 d <= 1024, bfloat16 d <= 2048; at most 65535 tiles of positives.)"""
+    limit = {torch.float32: 1024, torch.bfloat16: 2048}.get(dtype)
+    return limit is not None and d <= limit and n <= 65535 * NEG_SHARED_TILE_POSITIVES
+
+
+def shared_samples(unique, drop, repeat, n: int) -> torch.Tensor:
+    """The [n, K] sample ids a shared negative sample stands for (NaiveSharedNegativeSample.samples /
+    DefaultSharedNegativeSample.samples, sampler.py:412-426, 503-535), pure torch: `unique` = the distinct ids (with
+    `drop`: one more, the spare), `drop` = None (naive) or [n] with drop[i] in [0, Uc] -- column drop[i] < Uc of row i
+    shows the spare --, `repeat` = the columns repeated behind the Uc distinct ones (None or ANY empty tensor -- the
+    sampler passes an empty float tensor -- = none).  Fallbacks and tests; the kernels never materialise it."""
+    unique = unique.reshape(-1).long()
+    if drop is None:
+        neg = unique.unsqueeze(0).expand(n, -1)
+    else:
+        uc = unique.numel() - 1
+        drop = drop.reshape(-1).to(device=unique.device, dtype=torch.long)
+        if drop.numel() != n:
+            raise ValueError("kge_amd: shared_samples: one drop index per positive")
+        hit = torch.arange(uc, device=unique.device).unsqueeze(0) == drop.unsqueeze(1)
+        neg = torch.where(hit, unique[uc], unique[:uc].unsqueeze(0).expand(n, -1))
+    if repeat is not None and repeat.numel() > 0:
+        neg = torch.cat([neg, neg[:, repeat.reshape(-1).to(device=unique.device, dtype=torch.long)]], dim=1)
+    return neg
+
+
+def _shared_args(t, unique, drop, repeat, n, keep):
+    """(unique ptr, itype, Uc, drop ptr or None, repeat ptr or None, number of repeats) of a shared sample."""
+    _require_gpu(unique, "shared negative samples")
+    if unique.dtype not in (torch.int32, torch.int64):
+        unique = unique.long()
+    unique = unique.reshape(-1).contiguous()
+    keep.append(unique)
+    uc = unique.numel()
+    dptr = None
+    if drop is not None:
+        drop = drop.reshape(-1).to(device=t.device, dtype=torch.long).contiguous()
+        if drop.numel() != n or uc < 1:
+            raise ValueError("kge_amd: a shared sample with drop indexes has one per positive and a spare id")
+        keep.append(drop)
+        uc -= 1
+        dptr = drop.data_ptr()
+    rptr, nrep = None, 0
+    if repeat is not None and repeat.numel() > 0:  # (any empty tensor, the sampler's torch.empty(0) included: none)
+        repeat = repeat.reshape(-1).to(device=t.device, dtype=torch.long).contiguous()
+        keep.append(repeat)
+        rptr, nrep = repeat.data_ptr(), repeat.numel()
+    return unique.data_ptr(), (I32 if unique.dtype == torch.int32 else I64), uc, dptr, rptr, nrep
+
+
+def score_neg_shared(t: Tables, s, p, o, slot: int, unique, drop=None, repeat=None, flags=None, out=None) -> torch.Tensor:
+    """[n, K] scores of triple i with `slot` (0 = s, 2 = o) replaced by shared_samples(unique, drop, repeat, n)[i, k],
+    bit-identical to score_neg on those samples, without materialising them: the target rows are staged once per
+    workgroup and shared by its positives (kge_score_neg_shared).  `out`: an [n, K] float32 view with unit inner
+    stride to write into (e.g. columns 1.. of an [n, 1 + K] block)."""
+    keep = []
+    si, pi, oi = (_index(x, t.device, keep) for x in (s, p, o))
+    n = _same_len(keep[:3], "score_neg_shared")
+    uptr, uit, uc, dptr, rptr, nrep = _shared_args(t, unique, drop, repeat, n, keep)
+    K = uc + nrep
+    if out is None:
+        out = _empty((n, K), t.device)
+    elif (out.shape != (n, K) or out.dtype != torch.float32 or out.device != t.device
+          or (K > 1 and out.stride(1) != 1)):
+        raise ValueError("kge_amd: score_neg_shared: out must be an [n, K] float32 view with unit inner stride")
+    with _on_device(t.device):
+        tc = t.c(flags)
+        _lib.check(_lib.lib().kge_score_neg_shared(
+            ctypes.byref(tc), si, pi, oi, n, int(slot), uptr, uit, uc, dptr, rptr, nrep, out.data_ptr(),
+            out.stride(0) if n > 1 else max(K, 1), _stream(t.device)), "kge_score_neg_shared")
+    return out
+
+
+def score_neg_shared_bwd_accum(t: Tables, s, p, o, slot: int, unique, drop, repeat, gout, scores, grad_ent, grad_rel):
+    """Backward of score_neg_shared accumulated straight into the dense table gradients `grad_ent` [E, d] and `grad_rel`
+    [R, d_r] (f32, modified in place); False if the kernel does not take this shape (bf16 tables, d > 1024)."""
+    keep = []
+    si, pi, oi = (_index(x, t.device, keep) for x in (s, p, o))
+    n = _same_len(keep[:3], "score_neg_shared_bwd_accum")
+    uptr, uit, uc, dptr, rptr, nrep = _shared_args(t, unique, drop, repeat, n, keep)
+    K = uc + nrep
+    gout = gout.to(device=t.device, dtype=torch.float32)
+    if gout.dim() != 2 or (K > 1 and gout.stride(1) != 1):
+        gout = gout.contiguous().view(n, K)
+    sc = None
+    if scores is not None:
+        sc = scores if (scores.dim() == 2 and (K <= 1 or scores.stride(1) == 1)) else scores.contiguous().view(n, K)
+    with _on_device(t.device):
+        tc = t.c()
+        need = _lib.lib().kge_score_neg_shared_workspace_bytes(ctypes.byref(tc), n, uc)
+        ws = _empty((max(need, 16),), t.device, torch.uint8)
+        rc = _lib.lib().kge_score_neg_shared_bwd_accum(
+            ctypes.byref(tc), si, pi, oi, n, int(slot), uptr, uit, uc, dptr, rptr, nrep, gout.data_ptr(),
+            gout.stride(0) if n > 1 else max(K, 1), None if sc is None else sc.data_ptr(),
+            0 if sc is None else (sc.stride(0) if n > 1 else max(K, 1)), grad_ent.data_ptr(), grad_ent.stride(0),
+            grad_rel.data_ptr(), grad_rel.stride(0), ws.data_ptr(), ws.numel(), _stream_handle(t.device))
+    if rc == _lib.KGE_ERR_UNSUPPORTED:
+        return False
+    if rc:
+        _lib.check(rc, "kge_score_neg_shared_bwd_accum")
     return True
 
 

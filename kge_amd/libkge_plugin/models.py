@@ -9,7 +9,7 @@ from kge.model.transe import TransE as _RefTransE
 
 from .. import engine
 from ..model import (BF16Shadow, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg,
-                     _ScoreNegBlocks, _ScorePairs, _ScoreSPO, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable)
+                     _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable)
 
 
 class _HipScorer(RelationalScorer):
@@ -141,6 +141,20 @@ class _FusedScoring:
         if not ent.is_cuda:
             return None
         return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), neg)
+
+    def score_neg_shared(self, s: Tensor, p: Tensor, o: Tensor, slot: int, unique: Tensor, drop: Tensor = None,
+                         repeat: Tensor = None):
+        """[n, K] scores of the positives against a SHARED negative sample of slot 0 / 2 (unique ids, drop indexes or
+        None, repeat columns): what NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score return
+        (kge/util/sampler.py:428-463, 537-578), from kge_score_neg_shared -- the target rows staged once per workgroup
+        and shared by its positives; None if the fused path does not apply (the job then calls the sampler's score)."""
+        if not self._fused() or slot not in (0, 2):
+            return None
+        ent, rel = self._w()
+        if not ent.is_cuda or not neg_shared_fusable(ent, s.numel()):
+            return None
+        return _ScoreNegShared.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), unique, drop,
+                                     repeat)
 
     def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None):
         """(positives [n], subject-slot block [n, K_s] or None, object-slot block [n, K_o] or None) as ONE autograd node
@@ -460,6 +474,19 @@ class HipReciprocalRelationsModel(_RefReciprocal):
             return b.score_neg(s, p, o, 2, neg)
         if slot == 0:
             return b.score_neg(o, p + self._R(), s, 2, neg)
+        return None
+
+    def score_neg_shared(self, s: Tensor, p: Tensor, o: Tensor, slot: int, unique: Tensor, drop: Tensor = None,
+                         repeat: Tensor = None):
+        """score_neg for a SHARED sample (unique ids, drop indexes, repeat columns; sampler.py:428-463, 537-578) with the
+        same translation: a corrupted subject is the corrupted object of the reversed triple (o, p + R, s')."""
+        b = self._base_model
+        if not self._base_fused() or not hasattr(b, "score_neg_shared"):
+            return None
+        if slot == 2:
+            return b.score_neg_shared(s, p, o, 2, unique, drop, repeat)
+        if slot == 0:
+            return b.score_neg_shared(o, p + self._R(), s, 2, unique, drop, repeat)
         return None
 
     # ---- the fused-loss hooks of HipTrainingJob1vsAll / HipTrainingJobKvsAll (train_job.py)

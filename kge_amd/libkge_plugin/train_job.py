@@ -523,6 +523,32 @@ class _FusedNegativeScore:
         return scores if scores is not None else self._score(model, indexes=indexes)
 
 
+class _FusedSharedScore:
+    """Stands in for `NaiveSharedNegativeSample.score` / `DefaultSharedNegativeSample.score` (sampler.py:428-463,
+    537-578) of ONE slot's shared sample object for the duration of a subbatch: the same call, the same `forward_time`
+    / `prepare_time` attributes -- the shared sample goes to the model's `score_neg_shared` as (positives, unique ids,
+    drop indexes of the positives or None, repeat columns); nothing per triple is materialised (`samples(indexes)` of
+    the naive object even fails on a slice).  Declined by the model: the sampler's own code."""
+
+    def __init__(self, sample, slot):
+        self._sample, self._slot, self._score = sample, slot, sample.score
+
+    def __call__(self, model, indexes=None):
+        smp = self._sample
+        smp.forward_time = smp.prepare_time = 0.0
+        smp.prepare_time -= time.time()
+        tri = smp.positive_triples if indexes is None else smp.positive_triples[indexes, :]
+        drop = getattr(smp, "_drop_index", None)
+        if drop is not None and indexes is not None:
+            drop = drop[indexes]
+        smp.prepare_time += time.time()
+        smp.forward_time -= time.time()
+        scores = model.score_neg_shared(tri[:, S], tri[:, P], tri[:, O], self._slot, smp._unique_samples, drop,
+                                        smp._repeat_indexes)
+        smp.forward_time += time.time()
+        return scores if scores is not None else self._score(model, indexes=indexes)
+
+
 class _FusedNsBce(torch.autograd.Function):
     """loss = sum of kge_ns_bce_loss's per-row terms; the kernel writes d loss / d scores in the same pass."""
 
@@ -590,8 +616,16 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
     ("triple"), or an [n, U] matrix against the unique samples ("batch" / "all"), the relation row and the
     uncorrupted entity row of each positive are read once and only the corrupted rows stream (kge_score_neg,
     SURVEY 8f N2); the backward accumulates straight into the table gradients (kge_score_neg_bwd_accum).
-    Shared samples (NaiveShared / DefaultShared: their own `score`, which never materialises [n, K] samples)
-    and the relation slot stay the sampler's code."""
+    Shared samples (`negative_sampling.shared: true`: NaiveSharedNegativeSample / DefaultSharedNegativeSample,
+    sampler.py:383-585) of the subject and object slots go to the model's `score_neg_shared` as (unique ids, drop
+    indexes, repeat columns) = kge_score_neg_shared: the U distinct target rows are staged once per workgroup and
+    shared by its positives instead of n K gathered rows (the "triple" implementation TransE / RotatE are forced to)
+    or a subset score matrix and ~ten indexing launches per slot ("batch"); the backward is
+    kge_score_neg_shared_bwd_accum -- with `hip_negative_sampling.fused_shared: true`.  The option is false by default
+    (no probe numbers exist yet: DESIGN.md section 14); false, a model without the hook or a hook that declines (CPU
+    tensors, dropout, a row too wide for the kernel's tile): the sampler's own `score`.  The captured step
+    (graph_step) stays off for shared samples -- their shapes vary with U --, the relation slot stays the sampler's
+    code."""
 
     def __init__(self, config, dataset, parent_job=None, model=None, forward_only=False):
         super().__init__(config, dataset, parent_job, model=model, forward_only=forward_only)
@@ -604,6 +638,11 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             fused_loss = True
         if str(self.device).startswith("cuda") and _fusable_ns_loss(self.loss) and fused_loss:
             self.loss = _HipNsBceLoss(self.loss)
+        # shared samples of the subject / object slot through kge_score_neg_shared (false: the sampler's own score)
+        try:
+            self._fused_shared = bool(config.get("hip_negative_sampling.fused_shared"))
+        except KeyError:
+            self._fused_shared = False
         self._graph_step = None       # kge_amd.train_graph.GraphedStep (hip_negative_sampling.graph_step)
         self._graph_step_ok = None    # decided at the first batch
         self._graph_slots = ()
@@ -698,6 +737,14 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
                 smp = batch["negative_samples"][slot]
                 if self._sampler.num_samples[slot] > 0 and type(smp) is DefaultBatchNegativeSample:
                     smp.score = _FusedNegativeScore(smp, slot)  # instance attribute: shadows the method
+                    swapped.append(smp)
+        if self._fused_shared and hasattr(self.model, "score_neg_shared"):
+            from kge.util.sampler import DefaultSharedNegativeSample, NaiveSharedNegativeSample
+            for slot in (S, O):
+                smp = batch["negative_samples"][slot]
+                if (self._sampler.num_samples[slot] > 0
+                        and type(smp) in (NaiveSharedNegativeSample, DefaultSharedNegativeSample)):
+                    smp.score = _FusedSharedScore(smp, slot)  # instance attribute: shadows the method
                     swapped.append(smp)
         try:
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)

@@ -180,6 +180,16 @@ class KgeModel(torch.nn.Module):
         tr[slot] = neg.reshape(-1).long()
         return self.score_spo(tr[0], tr[1], tr[2]).view(-1, K)
 
+    def score_neg_shared(self, s: Tensor, p: Tensor, o: Tensor, slot: int, unique: Tensor, drop: Tensor = None,
+                         repeat: Tensor = None) -> Tensor:
+        """[n, K]: score of triple i with slot (0 = s, 2 = o) replaced by the shared sample (unique, drop, repeat) --
+        NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score (kge/util/sampler.py:428-463, 537-578);
+        equals score_neg on engine.shared_samples(unique, drop, repeat, n)."""
+        if self._fused() and slot in (0, 2) and neg_shared_fusable(self._entity_embedder.weight, s.numel()):
+            return _ScoreNegShared.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
+                                         self._relation_embedder.weight, s, p, o, int(slot), unique, drop, repeat)
+        return self.score_neg(s, p, o, slot, engine.shared_samples(unique, drop, repeat, s.reshape(-1).numel()))
+
     def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None):
         """(positives [n], [n, K_s] scores with the subject replaced by neg_s[i, k] or None, [n, K_o] with the object
         replaced or None): score_spo + score_neg per slot as ONE autograd node (one pair of table gradients in the
@@ -456,6 +466,43 @@ class _ScoreNeg(torch.autograd.Function):
         return None, None, ge, gr, None, None, None, None, None
 
 
+class _ScoreNegShared(torch.autograd.Function):
+    """[n, K] scores of the positives against a SHARED negative sample (unique ids, drop indexes or None, repeat
+    columns): what NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score return (sampler.py:428-463,
+    537-578), from kge_score_neg_shared -- the target rows staged once per workgroup, no [n, K] sample tensor and no
+    [n, Uc + 1] intermediate score matrix; backward = kge_score_neg_shared_bwd_accum (complete table gradients, one
+    row flush per (positive, tile) and (unique row, tile) instead of one atomic per occurrence)."""
+
+    @staticmethod
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, slot, unique, drop, repeat):
+        t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
+        out = engine.score_neg_shared(t, s, p, o, slot, unique, drop, repeat)
+        ctx.t, ctx.idx, ctx.slot = t, (s, p, o, unique, drop, repeat), slot
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        s, p, o, unique, drop, repeat = ctx.idx
+        (scores,) = ctx.saved_tensors
+        ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
+        if not engine.score_neg_shared_bwd_accum(ctx.t, s, p, o, ctx.slot, unique, drop, repeat, gout, scores, ge, gr):
+            # shapes the shared accumulate kernel does not take: the per-triple route on the materialised samples
+            neg = engine.shared_samples(unique, drop, repeat, scores.shape[0]).contiguous()
+            if not engine.score_neg_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr):
+                K = neg.shape[1]
+                tr = [x.reshape(-1).long().repeat_interleave(K) for x in (s, p, o)]
+                tr[ctx.slot] = neg.reshape(-1).long()
+                g_s, g_p, g_o = engine.score_spo_bwd(ctx.t, tr[0], tr[1], tr[2], gout.reshape(-1).contiguous(),
+                                                     scores.reshape(-1))
+                ge, gr = ge.float(), gr.float()
+                _scatter_rows(ge, tr[0], g_s)
+                _scatter_rows(ge, tr[2], g_o)
+                _scatter_rows(gr, tr[1], g_p)
+                ge, gr = ge.to(ctx.t.ent.dtype), gr.to(ctx.t.rel.dtype)
+        return None, None, ge, gr, None, None, None, None, None, None, None
+
+
 class _ScoreNegBlocks(torch.autograd.Function):
     """What TrainingJobNegativeSampling._process_subbatch scores for a subbatch (train_negative_sampling.py:120-151) in
     ONE autograd node: the positives (score_spo) and the negative blocks of the subject and the object slot
@@ -487,6 +534,12 @@ class _ScoreNegBlocks(torch.autograd.Function):
                 if not engine.score_neg_bwd_accum(ctx.t, s, p, o, slot, neg, g, sc, ge, gr):
                     raise RuntimeError("kge_amd: kge_score_neg_bwd_accum declined a shape score_neg_blocks admitted")
         return None, None, ge, gr, None, None, None, None, None
+
+
+def neg_shared_fusable(ent: torch.Tensor, n: int) -> bool:
+    """The shapes kge_score_neg_shared takes (a row that fits its LDS tile, a grid that fits): anything else goes the
+    per-triple way on engine.shared_samples -- or, in the plugin, back to the sampler's own score."""
+    return engine.neg_shared_supported(ent.dtype, ent.shape[1], n)
 
 
 def neg_blocks_fusable(ent: torch.Tensor, rel: torch.Tensor) -> bool:
