@@ -556,6 +556,35 @@ int kge_ce_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index
                float* g_p, float* g_tgt, void* workspace, int64_t workspace_bytes,
                void* stream);
 
+/* ---- the same loss for the distance scorers on float32 tables ---------------- */
+/* kge_ce_dist_fwd / kge_ce_dist_bwd: loss_rows, lse and the gradients exactly as kge_ce_fwd / kge_ce_bwd define
+ * them, for TransE and RotatE (transe.py:18-34, rotate.py:30-64) with l_norm 1 or 2 on float32 tables: the step of
+ * TrainingJob1vsAll (kge/job/train_1vsAll.py:64-81) with KLDivWithSoftmaxKgeLoss on index labels
+ * (kge/util/loss.py:192-207) without an [n, num_ent] matrix.  The forward folds every score tile into a per-row
+ * running (max, sum exp) and merges the partial results in a fixed order (no atomics: the same bits on every run);
+ * every score inside is bit-identical to kge_score_sp / kge_score_po on the same tables.  The backward walks the
+ * entity columns in chunks: the scoring kernels write one [n, chunk] block of scores into the workspace, the
+ * gradient kernels form d loss / d score from it, lse and label while they read it.
+ *   g_rows, g_scalar, g_a [n, dim], g_p [n, rel_dim], g_tgt [num_ent, dim]: as for kge_ce_bwd (f32, OVERWRITTEN).
+ *   A label outside [0, num_ent) gives loss_rows[i] = NaN.
+ * kge_ce_dist_workspace_bytes(t, n, chunk_cols): chunk_cols = columns per chunk of the backward, a multiple of 64
+ * (>= 64), or 0 = the library's default (a score chunk of at most 32 MB, at least 64 columns, clamped to num_ent
+ * rounded up to 64); returns 0 for tables the calls do not take.  The workspace holds the forward's records
+ * (12 bytes per row and column group, at most 256 groups), an [n, dim] buffer and the [n, chunk] score block:
+ * 256-byte aligned device scratch, no initialisation, stream-ordered use, not shared by concurrent calls.  The
+ * backward derives its chunk width from `workspace_bytes` (any size from chunk_cols = 64 up is valid: a smaller
+ * workspace only means more chunks; below that, and for the forward below its records, KGE_ERR_WORKSPACE).
+ * ComplEx / DistMult, bf16 tables or another l_norm: KGE_ERR_UNSUPPORTED, nothing is launched.  No allocation, no
+ * host wait, no library call: both are stream-ordered and capturable into a hipGraph. */
+int64_t kge_ce_dist_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols);
+int kge_ce_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label,
+                    int64_t n, float* loss_rows, float* lse, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+int kge_ce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label,
+                    int64_t n, const float* lse, const float* g_rows, float g_scalar, float* g_a,
+                    float* g_p, float* g_tgt, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+
 /* The same pair with DENSE query rows (a_rows [n, dim], p_rows [n, rel_dim], row-major, bf16) scored
  * against ALL rows of t->ent: the per-shard step of entity-sharded 1vsAll training:
  * the query rows of a batch come out of the exchange between the shards, t->ent is this rank's shard,

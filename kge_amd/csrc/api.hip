@@ -24,6 +24,14 @@ int run_pairs_exact(int scorer, int dtype, bool use_mfma, const Operand& A, cons
                     const Operand& TG, int dir, int d, int dr, long long n, long long m,
                     float lp, float* out, long long ldo, hipStream_t st, bool round_query = true,
                     const RankArgs* rk = nullptr);
+long long ce_dist_records_bytes(long long n, long long m);
+long long ce_dist_workspace_bytes(long long n, long long m, int d, long long chunk_cols);
+int run_ce_dist_fwd(int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
+                    long long n, long long m, const Index& label, float* loss_rows, float* lse, void* ws,
+                    long long ws_bytes, hipStream_t st);
+int run_ce_dist_bwd(int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
+                    long long n, long long m, const Index& label, const float* lse, const float* g_rows, float g_scalar,
+                    float* g_a, float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st);
 bool pairs_bf16_v3_supported(int scorer, int dtype, int d, const Operand& A, const Operand& R,
                              const Operand& TG);
 int run_pairs_bf16_v3(int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir,
@@ -1547,6 +1555,59 @@ int kge_ce_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index
   return run_ce_bwd(t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
                     make_index(label), lse, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
                     (hipStream_t)stream);
+}
+
+// ---- the same loss for the distance scorers on float32 tables (ce_dist.hip): train_1vsAll.py:64-81, loss.py:192-207,
+// transe.py:18-34, rotate.py:30-64 ------------------------------------------------------------------------------
+namespace {
+bool ce_dist_tables_ok(const kge_tables* t) {
+  if (t->scorer != KGE_TRANSE && t->scorer != KGE_ROTATE) return false;
+  if (t->dtype != KGE_F32) return false;
+  return t->l_norm == 1.0f || t->l_norm == 2.0f;
+}
+int ce_dist_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, const kge_index& label,
+                  int64_t n) {
+  int rc = check_tables(t, true);
+  if (rc) return rc;
+  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
+  if (n < 0) return KGE_ERR_INVALID_ARG;
+  if (!ce_dist_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
+  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n)) || (rc = check_index(label, false, n)))
+    return rc;
+  return KGE_OK;
+}
+}  // namespace
+
+int64_t kge_ce_dist_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
+  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_dist_tables_ok(t)) return 0;
+  if (chunk_cols < 0 || chunk_cols % 64) return 0;
+  return ce_dist_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+}
+
+int kge_ce_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label, int64_t n,
+                    float* loss_rows, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ce_dist_check(t, dir, a, p, label, n);
+  if (rc) return rc;
+  if (n == 0) return KGE_OK;
+  if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ce_dist_fwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+                         (int)t->rel_dim, n, t->num_ent, make_index(label), loss_rows, lse, workspace, workspace_bytes,
+                         (hipStream_t)stream);
+}
+
+int kge_ce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label, int64_t n,
+                    const float* lse, const float* g_rows, float g_scalar, float* g_a, float* g_p, float* g_tgt,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ce_dist_check(t, dir, a, p, label, n);
+  if (rc) return rc;
+  if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ce_dist_bwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+                         (int)t->rel_dim, n, t->num_ent, make_index(label), lse, g_rows, g_scalar, g_a, g_p, g_tgt,
+                         workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- the same with DENSE query rows (entity-sharded training: the query rows of a batch come out of

@@ -20,11 +20,6 @@ namespace kge {
 
 constexpr int BW_TR = 64, BW_TC = 32, BW_KY = 16;
 
-__device__ __forceinline__ float ldf(const float* row, int k, int limit) {
-  return k < limit ? row[k] : 0.0f;
-}
-
-
 template <int SCORER, int NORM, int WHICH>
 __global__ __launch_bounds__(256) void bwd_pairs_kernel(Operand A, Operand R, Operand TG, int dir,
                                                         int d, int dr, long long n, long long m,

@@ -1,9 +1,14 @@
 // bwd_device.hpp -- the per-coordinate-pair gradient arithmetic shared by the backward kernels (bwd.hip,
-// score_neg_shared.hip).
+// score_neg_shared.hip, ce_dist.hip).
 #pragma once
 #include "common.hpp"
 
 namespace kge {
+
+// element k of a float32 row, 0 beyond its valid length
+__device__ __forceinline__ float ldf(const float* row, int k, int limit) {
+  return k < limit ? row[k] : 0.0f;
+}
 
 // weight of one distance component e (TransE) given the pair's distance
 template <int NORM>

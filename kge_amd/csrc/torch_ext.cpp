@@ -201,6 +201,59 @@ void score_queries_group(const at::Tensor& ent, const at::Tensor& rel, int64_t s
         "kge_score_queries_multi");
 }
 
+// ---- fused 1vsAll loss of TransE / RotatE on float32 tables (kge_ce_dist_*; direction: 1 = sp_, 2 = _po).  The
+// workspace is the caller's (engine.py caches one per device and stream); its first `workspace_bytes` bytes are used.
+int64_t ce_dist_workspace_bytes(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t n,
+                                int64_t chunk_cols) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  return kge_ce_dist_workspace_bytes(&t, n, chunk_cols);
+}
+
+void* ce_dist_ws(const at::Tensor& workspace, int64_t workspace_bytes) {
+  TORCH_CHECK(workspace.is_cuda() && workspace.is_contiguous() &&
+                  workspace.numel() * workspace.element_size() >= workspace_bytes,
+              "kge_amd: workspace must be a contiguous GPU tensor of at least workspace_bytes bytes");
+  return workspace.data_ptr();
+}
+
+std::vector<at::Tensor> ce_dist_fwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                    int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& label,
+                                    const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n), li = index_of(label, ent, keep, &n);
+  at::Tensor loss_rows = empty_f32({n}, ent), lse = empty_f32({n}, ent);
+  check(kge_ce_dist_fwd(&t, (int)direction, ai, pi, li, n, loss_rows.data_ptr<float>(), lse.data_ptr<float>(),
+                        ce_dist_ws(workspace, workspace_bytes), workspace_bytes, stream_of(ent)),
+        "kge_ce_dist_fwd");
+  return {loss_rows, lse};
+}
+
+std::vector<at::Tensor> ce_dist_bwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                    int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& label,
+                                    const at::Tensor& lse, const c10::optional<at::Tensor>& g_rows, double g_scalar,
+                                    const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n), li = index_of(label, ent, keep, &n);
+  const at::Tensor lse_c = lse.to(at::kFloat).contiguous();
+  TORCH_CHECK_VALUE(lse_c.numel() == n, "kge_amd: lse must have one entry per row");
+  at::Tensor gr;
+  if (g_rows.has_value() && g_rows->defined()) {
+    gr = g_rows->to(at::kFloat).contiguous();
+    TORCH_CHECK_VALUE(gr.numel() == n, "kge_amd: g_rows must have one entry per row");
+  }
+  at::Tensor g_a = empty_f32({n, t.dim}, ent), g_p = empty_f32({n, t.rel_dim}, ent), g_t = empty_f32({t.num_ent, t.dim}, ent);
+  check(kge_ce_dist_bwd(&t, (int)direction, ai, pi, li, n, lse_c.data_ptr<float>(),
+                        gr.defined() ? gr.data_ptr<float>() : nullptr, (float)g_scalar, g_a.data_ptr<float>(),
+                        g_p.data_ptr<float>(), g_t.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes),
+                        workspace_bytes, stream_of(ent)),
+        "kge_ce_dist_bwd");
+  return {g_a, g_p, g_t};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -211,4 +264,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("queries_bytes", &queries_bytes);
   mod.def("build_queries_group", &build_queries_group);
   mod.def("score_queries_group", &score_queries_group);
+  mod.def("ce_dist_workspace_bytes", &ce_dist_workspace_bytes);
+  mod.def("ce_dist_fwd", &ce_dist_fwd, "1vsAll cross entropy of TransE / RotatE without a score matrix: (loss_rows, lse)");
+  mod.def("ce_dist_bwd", &ce_dist_bwd, "its backward: (g_a, g_p, g_entities)");
 }

@@ -1486,6 +1486,83 @@ def ce_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scalar: f
     return g_a, g_p, g_t
 
 
+def ce_dist_supported(t: Tables) -> bool:
+    """Can the fused 1vsAll loss of the distance scorers run on these tables (kge_ce_dist_workspace_bytes > 0):
+    TransE / RotatE, float32, l_norm 1 or 2, on a GPU?"""
+    if not t.ent.is_cuda:
+        return False
+    return _lib.lib().kge_ce_dist_workspace_bytes(ctypes.byref(t.c()), 1, 0) > 0
+
+
+def _ce_dist_args(t: Tables, a, p, label, chunk_cols, what):
+    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths."""
+    chunk_cols = int(chunk_cols)
+    if chunk_cols < 0 or chunk_cols % 64:
+        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 64, got {chunk_cols}")
+    if t.scorer not in (_lib.TRANSE, _lib.ROTATE) or t.ent.dtype != torch.float32 or t.l_norm not in (1.0, 2.0):
+        raise RuntimeError(f"kge_amd: {what}: TransE / RotatE on float32 tables with l_norm 1 or 2 only "
+                           "(ComplEx / DistMult on bf16 tables: ce_fwd / ce_bwd)")
+    keep = []
+    ixs = tuple(_index(x, t.device, keep) for x in (a, p, label))
+    n = _same_len(keep[:3], what)
+    _require_gpu(t.ent, "entity table")
+    return ixs, n, chunk_cols, keep
+
+
+def _ce_dist_workspace(tc, n, chunk_cols, device, st):
+    """(ptr, bytes): the per-(device, stream) scratch of kge_ce_dist_fwd / _bwd; `bytes` is exactly what the chunk width
+    asks for (the backward derives its chunk width from it), the buffer may be larger."""
+    need = _lib.lib().kge_ce_dist_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
+    if need <= 0:
+        raise RuntimeError("kge_ce_dist_fwd/kge_ce_dist_bwd: float32 TransE / RotatE tables with l_norm 1 or 2 only")
+    key = (device.index, st, "ce_dist")
+    buf = _WORKSPACES.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
+    return buf.data_ptr(), need
+
+
+def ce_dist_fwd(t: Tables, direction: str, a, p, label, chunk_cols: int = 0):
+    """ce_fwd for TransE / RotatE on float32 tables (kge_ce_dist_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
+    a = s, label = o) / score_po ('po': a = o, label = s) against all entities, no [n, E] matrix."""
+    (ai, pi, li), n, chunk_cols, keep = _ce_dist_args(t, a, p, label, chunk_cols, "ce_dist_fwd")
+    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
+    if n == 0:
+        return loss_rows, lse
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ce_dist_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_ce_dist_fwd(ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n,
+                                              loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_ce_dist_fwd")
+    return loss_rows, lse
+
+
+def ce_dist_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scalar: float = 1.0, chunk_cols: int = 0):
+    """Backward of ce_dist_fwd (kge_ce_dist_bwd): gradients of sum_i g_i * loss_rows[i] w.r.t. the gathered query rows
+    and all entity rows: (g_a [n, d], g_p [n, d_r], g_entities [E, d]).  chunk_cols: entity columns per chunk of the
+    backward (a multiple of 64; 0 = the library's default, a score chunk of at most 32 MB)."""
+    (ai, pi, li), n, chunk_cols, keep = _ce_dist_args(t, a, p, label, chunk_cols, "ce_dist_bwd")
+    d, dr = t.ent.shape[1], t.rel.shape[1]
+    lse = _f32c(lse, t.device)
+    gr = None if g_rows is None else _f32c(g_rows, t.device)
+    if lse.numel() != n or (gr is not None and gr.numel() != n):
+        raise ValueError("kge_amd: ce_dist_bwd: lse and g_rows must have one entry per row")
+    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
+    if n == 0:
+        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
+    g_t = _empty((t.num_ent, d), t.device)
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ce_dist_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_ce_dist_bwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n, lse.data_ptr(),
+            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(),
+            g_t.data_ptr(), ws, wsb, st), "kge_ce_dist_bwd")
+    return g_a, g_p, g_t
+
+
 def ce_emb_fwd(t: Tables, direction: str, a_rows, p_rows, label):
     """ce_fwd with dense bf16 query rows against ALL rows of t.ent (the per-shard step of entity-sharded
     1vsAll training): (loss_rows [n] -- NaN where `label` (local row ids) is outside [0, num_ent) --, lse [n])."""

@@ -8,7 +8,7 @@ from kge.model.rotate import RotatE as _RefRotatE
 from kge.model.transe import TransE as _RefTransE
 
 from .. import engine
-from ..model import (BF16Shadow, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg,
+from ..model import (BF16Shadow, _FusedCE, _FusedCEDist, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg,
                      _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable)
 
 
@@ -253,6 +253,21 @@ class _FusedScoring:
             t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
         return t if (t is not None and ent.is_cuda and engine.ce_supported(t)) else None
 
+    # `hip_1vsAll.fused_dist_loss: true` (set by HipTrainingJob1vsAll; false by default): the 1vsAll loss of hip_transe /
+    # hip_rotate on float32 tables without an [n, E] matrix (kge_ce_dist_fwd / kge_ce_dist_bwd)
+    _fused_dist_loss = False
+
+    def _ce_dist_tables(self):
+        """float32 tables for the distance scorers' fused loss, or None (the composed path): the option on, TransE /
+        RotatE with l_norm 1 or 2, `_fused()` (plain lookup embedders, no active dropout, parameters on a GPU)."""
+        if not self._fused_dist_loss or not self._fused() or self._scorer.name not in ("transe", "rotate"):
+            return None
+        ent, rel = self._w()
+        if not ent.is_cuda or ent.dtype != torch.float32 or self._scorer._norm not in (1.0, 2.0):
+            return None
+        t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
+        return t if engine.ce_dist_supported(t) else None
+
     def _rank_tables(self):
         """The tables HipEntityRankingJob counts on (kge_score_rank_sp_po: scoring + _filter_and_rank counts in one
         kernel) -- the ones score_sp_po scores on under no_grad, so that fused and two-step counts agree bit for bit:
@@ -268,7 +283,8 @@ class _FusedScoring:
         t = self._ce_tables()
         dp = self._dropout_only() if t is None else None
         if t is None and dp is None:
-            return None
+            td = self._ce_dist_tables()
+            return None if td is None else _FusedCEDist.apply("sp", *self._w(), s, p, o, td)
         ent, rel = self._w()
         if dp is not None:  # embedder dropout in training: the masks applied here, the fused kernels on dense rows
             return ce_fused_dropout(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, o, dp[0], dp[1])
@@ -278,7 +294,8 @@ class _FusedScoring:
         t = self._ce_tables()
         dp = self._dropout_only() if t is None else None
         if t is None and dp is None:
-            return None
+            td = self._ce_dist_tables()
+            return None if td is None else _FusedCEDist.apply("po", *self._w(), o, p, s, td)
         ent, rel = self._w()
         if dp is not None:  # embedder dropout in training: the masks applied here, the fused kernels on dense rows
             return ce_fused_dropout(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, s, dp[0], dp[1])
@@ -289,7 +306,9 @@ class _FusedScoring:
         t = self._ce_tables()
         if t is None:
             if self._dropout_only() is None:
-                return None
+                if self._ce_dist_tables() is None:
+                    return None
+                return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))  # (the distance scorers: one-sided calls)
             # independent masks per direction, as the reference's two score_* calls draw them
             return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))
         ent, rel = self._w()
@@ -496,6 +515,10 @@ class HipReciprocalRelationsModel(_RefReciprocal):
 
     def _dropout_only(self):
         f = getattr(self._base_model, "_dropout_only", None)
+        return f() if f is not None else None
+
+    def _ce_dist_tables(self):
+        f = getattr(self._base_model, "_ce_dist_tables", None)
         return f() if f is not None else None
 
     def loss_sp(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:

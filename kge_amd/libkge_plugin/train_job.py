@@ -31,6 +31,14 @@ def _model_takes_fused_loss(model, with_dropout: bool = False) -> bool:
     return bool(with_dropout and g is not None and g() is not None)
 
 
+def _model_takes_dist_loss(model) -> bool:
+    """The fused 1vsAll loss of the distance scorers (hip_transe / hip_rotate, `hip_1vsAll.fused_dist_loss: true`):
+    decided once per subbatch like _model_takes_fused_loss.  The two one-sided calls loss_sp / loss_po; no captured
+    step, no two-sided launch."""
+    f = getattr(model, "_ce_dist_tables", None)
+    return f is not None and f() is not None
+
+
 def _declined_late(what):
     raise RuntimeError(f"kge_amd: {what} declined after part of the subbatch was already back-propagated "
                        "(tables or options changed inside a subbatch)")
@@ -181,6 +189,15 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
         self._graph_step = None       # kge_amd.train_graph.GraphedStep, built at the first batch that qualifies
         self._graph_step_ok = None    # decided at the first batch (None: not yet)
         self._skip_optimizer_step = False
+        # hip_1vsAll.fused_dist_loss (false by default): the models learn it here and decide per subbatch
+        # (_FusedScoring._ce_dist_tables); under hip_reciprocal_relations_model the base model is the one that scores
+        try:
+            fused_dist = bool(config.get_default("hip_1vsAll.fused_dist_loss"))
+        except KeyError:
+            fused_dist = False
+        for m in (self.model, getattr(self.model, "_base_model", None)):
+            if m is not None and hasattr(type(m), "_fused_dist_loss"):
+                m._fused_dist_loss = fused_dist
         if self.__class__ == HipTrainingJob1vsAll:
             for f in Job.job_created_hooks:
                 f(self)
@@ -194,6 +211,7 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
         if self._graph_step_ok is None:
             ok = bool(self.config.get_default("hip_1vsAll.graph_step")) and str(self.device).startswith("cuda")
             ok = ok and _model_takes_fused_loss(self.model) and hasattr(self.model, "loss_sp_po")
+            ok = ok and not _model_takes_dist_loss(self.model)  # (no captured step for the distance scorers)
             ok = ok and _optimizer_is_capturable(self.optimizer)
             ok = ok and (_fold_penalties(self) or _no_penalty(self, batch_index, batch))
             self._graph_step_ok = ok
@@ -235,7 +253,9 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
 
     def _process_subbatch(self, batch_index, batch, subbatch_slice, result):
         kl = isinstance(self.loss, KLDivWithSoftmaxKgeLoss) and hasattr(self.model, "loss_sp")
-        if not _model_takes_fused_loss(self.model, with_dropout=kl):
+        takes = _model_takes_fused_loss(self.model, with_dropout=kl)
+        dist = kl and not takes and _model_takes_dist_loss(self.model)  # hip_1vsAll.fused_dist_loss: loss_sp, then loss_po
+        if not takes and not dist:
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)
         offset = _plain_bce(self.loss)
         if offset is not None and hasattr(self.model, "bce_loss_sp"):
@@ -246,7 +266,7 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
         if not fused:
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)
         batch_size = result.size
-        if hasattr(self.model, "loss_sp_po"):
+        if hasattr(self.model, "loss_sp_po") and not dist:
             gs = self._graph_step_for(batch_index, batch, subbatch_slice)
             if gs is not None and gs.enabled:
                 result.forward_time -= time.time()
@@ -260,7 +280,7 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
         result.prepare_time -= time.time()
         triples = batch["triples"][subbatch_slice].to(self.device)
         result.prepare_time += time.time()
-        if hasattr(self.model, "loss_sp_po"):
+        if hasattr(self.model, "loss_sp_po") and not dist:
             # both directions from one scoring launch and one pair of gradient products; the sum of
             # the two losses is back-propagated once (the reference does it in two passes:
             # the same gradients, accumulated)

@@ -112,8 +112,11 @@ class KgeModel(torch.nn.Module):
 
     def __init__(self, num_entities: int, num_relations: int, dim: int, l_norm: float = 1.0,
                  dtype=torch.float32, device=None, entity_args=None, relation_args=None,
-                 score_dtype=None):
+                 score_dtype=None, fused_dist_loss: bool = False):
         super().__init__()
+        # fused_dist_loss=True (TransE / RotatE, float32 parameters on a GPU, l_norm 1 or 2): loss_sp / loss_po /
+        # loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_dist_fwd / _bwd); off by default
+        self.fused_dist_loss = bool(fused_dist_loss)
         # score_dtype=torch.bfloat16 with f32 parameters (ComplEx / DistMult): sp_/_po scores from
         # the bf16 matrix-core kernel on bf16 copies of the tables, gradients w.r.t. the f32 masters
         self._shadow = BF16Shadow() if (score_dtype == torch.bfloat16 and dtype == torch.float32 and
@@ -236,12 +239,26 @@ class KgeModel(torch.nn.Module):
             t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach())
         return t if (t is not None and w.is_cuda and engine.ce_supported(t)) else None
 
+    def _ce_dist_tables(self):
+        """float32 tables for the distance scorers' fused loss (`fused_dist_loss=True`), or None (then the loss is
+        composed from score_sp / score_po): TransE / RotatE, l_norm 1 or 2, pure lookups, parameters on a GPU."""
+        if not self.fused_dist_loss or not self._fused() or self._scorer.name not in ("transe", "rotate"):
+            return None
+        w = self._entity_embedder.weight
+        if not w.is_cuda or w.dtype != torch.float32 or self._scorer._norm not in (1.0, 2.0):
+            return None
+        t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach(), self._scorer._norm)
+        return t if engine.ce_dist_supported(t) else None
+
     def loss_sp(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
         """Per-row cross entropy of score_sp(s, p) against the true objects o ([n]); its sum is the
         reference's `self.loss(scores_sp, triples[:, 2])` with train.loss=kl (loss.py:192-207)."""
         t = self._ce_tables()
         if t is not None:
             return _FusedCE.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, t)
+        td = self._ce_dist_tables()
+        if td is not None:
+            return _FusedCEDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, td)
         return torch.nn.functional.cross_entropy(self.score_sp(s, p), o.long(), reduction="none")
 
     def loss_sp_po(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
@@ -269,6 +286,9 @@ class KgeModel(torch.nn.Module):
         t = self._ce_tables()
         if t is not None:
             return _FusedCE.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p, s, t)
+        td = self._ce_dist_tables()
+        if td is not None:
+            return _FusedCEDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p, s, td)
         return torch.nn.functional.cross_entropy(self.score_po(p, o), s.long(), reduction="none")
 
     # -- KvsAll loss: train_KvsAll.py:274-294 with train.loss=kl
@@ -635,6 +655,30 @@ class _FusedCE(torch.autograd.Function):
         _scatter_rows(gr, p, g_p)
         _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
         return None, ge, gr, None, None, None, None
+
+
+class _FusedCEDist(torch.autograd.Function):
+    """_FusedCE for TransE / RotatE on float32 tables (kge_ce_dist_fwd / kge_ce_dist_bwd): `tables` are the
+    parameters themselves; the backward walks the entity columns in chunks of `chunk_cols` (0: the library's default)."""
+
+    @staticmethod
+    def forward(ctx, direction, ent, rel, a, p, label, tables, chunk_cols=0):
+        loss_rows, lse = engine.ce_dist_fwd(tables, direction, a, p, label, chunk_cols)
+        ctx.t, ctx.direction, ctx.idx, ctx.chunk_cols = tables, direction, (a, p, label), chunk_cols
+        ctx.rel_shape = rel.shape
+        ctx.save_for_backward(lse)
+        return loss_rows
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        a, p, label = ctx.idx
+        (lse,) = ctx.saved_tensors
+        g_a, g_p, ge = engine.ce_dist_bwd(ctx.t, ctx.direction, a, p, label, lse, g_rows=g_rows.contiguous(),
+                                          chunk_cols=ctx.chunk_cols)
+        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
+        _scatter_rows(gr, p, g_p)
+        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
+        return None, ge, gr, None, None, None, None, None
 
 
 class _FusedCE2(torch.autograd.Function):
