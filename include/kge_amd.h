@@ -727,6 +727,55 @@ int kge_bce_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t 
                 const float* g_rows, float g_scalar, float* g_a, float* g_p, float* g_tgt,
                 void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the KvsAll losses for the distance scorers on float32 tables ------------- */
+/* kge_kl_dist_fwd / _bwd and kge_bce_dist_fwd / _bwd: the losses of kge_kl_fwd / kge_kl_weighted_fwd and kge_bce_fwd
+ * above, for TransE and RotatE with l_norm 1 or 2 on float32 tables, without an [n, num_ent] matrix: the step of
+ * TrainingJobKvsAll for sp_ / _po queries (kge/job/train_KvsAll.py:216-294) with KLDivWithSoftmaxKgeLoss on a label
+ * matrix (kge/util/loss.py:192-213) or BCEWithLogitsKgeLoss with bce_type None (kge/util/loss.py:137-159), built on
+ * the kernels of kge_ce_dist_fwd / kge_ce_dist_bwd.
+ *   kl, label_weight == NULL:  loss_rows[i] = lse[i] - (1/k_i) sum_{j in labels_i} score(i, j) - log k_i   (0 if k_i = 0)
+ *   kl, label_weight [n]:      loss_rows[i] = lse[i] - w_i sum_{j in labels_i} score(i, j)      (k_i = 0: lse[i])
+ *   bce:  loss_rows[i] = sum over ALL entities j of max(x, 0) - x y_ij + log1p(exp(-|x|)),  x = score(i, j) + offset
+ *   d / d score(i, j) of sum_i g_i loss_rows[i]:  kl  g_i (softmax_ij - w_i [j in labels_i])   (w_i = 1/k_i without a
+ *   weight, and then 0 for a row without labels);  bce  g_i (sigmoid(score(i, j) + offset) - [j in labels_i])
+ * No label-smoothing bias term (kge_kl_weighted_bwd's label_bias): the uniform term of smoothed labels is not linear
+ * in the table for a distance scorer.
+ * Labels: lbl_col[lbl_rowptr[i] .. lbl_rowptr[i+1]), an int64 CSR on the device, entity ids unique per row, in ANY
+ * order within a row.  A label outside [0, num_ent) gives loss_rows[i] = NaN and leaves the other rows (and lse)
+ * untouched; the backward ignores it.  The forward folds every score tile into a per-row running (max, sum exp) (kl)
+ * or sum of softplus (bce) and merges the partial results in a fixed order; the label scores are summed in CSR order:
+ * no atomics, the same bits on every run.  Every score inside -- the label scores too -- is bit-identical to
+ * kge_score_sp / kge_score_po on the same tables.  The backward walks the entity columns in chunks as
+ * kge_ce_dist_bwd does; a bit mask of n x chunk bits per chunk (set from the CSR with atomic OR) says which columns
+ * are labels.
+ *   g_rows, g_scalar, g_a [n, dim], g_p [n, rel_dim], g_tgt [num_ent, dim]: as for kge_ce_dist_bwd (f32, OVERWRITTEN).
+ * kge_multilabel_dist_workspace_bytes(t, n, chunk_cols): chunk_cols as for kge_ce_dist_workspace_bytes; returns 0 for
+ * tables the calls do not take.  The workspace holds the forward's records (12 bytes per row and column group, at most
+ * 256 groups; the backward keeps two floats per row there), an [n, dim] buffer, the [n, chunk] score block and
+ * n x chunk / 8 bytes of label bits: 256-byte aligned device scratch, no initialisation, stream-ordered use, not shared
+ * by concurrent calls.  The backward derives its chunk width from `workspace_bytes` (any size from chunk_cols = 64 up
+ * is valid; below that, and for the forward below its records, KGE_ERR_WORKSPACE) and leaves the label bits all zero.
+ * Row count limits as for kge_ce_dist_*.  ComplEx / DistMult, bf16 tables or another l_norm: KGE_ERR_UNSUPPORTED,
+ * nothing is launched.  No allocation, no host wait, no library call: all four are stream-ordered and capturable into
+ * a hipGraph. */
+int64_t kge_multilabel_dist_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols);
+int kge_kl_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                    const int64_t* lbl_rowptr, const int64_t* lbl_col,
+                    const float* label_weight /* [n] or NULL */, float* loss_rows, float* lse,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int kge_kl_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                    const int64_t* lbl_rowptr, const int64_t* lbl_col,
+                    const float* label_weight /* [n] or NULL */, const float* lse, const float* g_rows,
+                    float g_scalar, float* g_a, float* g_p, float* g_tgt, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+int kge_bce_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                     const int64_t* lbl_rowptr, const int64_t* lbl_col, float offset, float* loss_rows,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+int kge_bce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                     const int64_t* lbl_rowptr, const int64_t* lbl_col, float offset, const float* g_rows,
+                     float g_scalar, float* g_a, float* g_p, float* g_tgt, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 /* Both query types of a KvsAll batch, backward, with COMPLETE table gradients.  TrainingJobKvsAll scores the sp_ and
  * the _po queries of a batch one after the other and back-propagates each loss on its own
  * (kge/job/train_KvsAll.py:274-294): two d loss / d score passes, four gradient products, and autograd's index_add and

@@ -32,6 +32,15 @@ int run_ce_dist_fwd(int scorer, float lp, const Operand& A, const Operand& R, co
 int run_ce_dist_bwd(int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
                     long long n, long long m, const Index& label, const float* lse, const float* g_rows, float g_scalar,
                     float* g_a, float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st);
+long long ml_dist_workspace_bytes(long long n, long long m, int d, long long chunk_cols);
+int run_ml_dist_fwd(int fold, int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                    int dr, long long n, long long m, const long long* rowptr, const long long* col,
+                    const float* label_weight, float offset, float* loss_rows, float* lse, void* ws, long long ws_bytes,
+                    hipStream_t st);
+int run_ml_dist_bwd(int fold, int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                    int dr, long long n, long long m, const long long* rowptr, const long long* col,
+                    const float* label_weight, float offset, const float* lse, const float* g_rows, float g_scalar,
+                    float* g_a, float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st);
 bool pairs_bf16_v3_supported(int scorer, int dtype, int d, const Operand& A, const Operand& R,
                              const Operand& TG);
 int run_pairs_bf16_v3(int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir,
@@ -1608,6 +1617,85 @@ int kge_ce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_
   return run_ce_dist_bwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, make_index(label), lse, g_rows, g_scalar, g_a, g_p, g_tgt,
                          workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- the KvsAll losses of the distance scorers on float32 tables (ce_dist.hip, the folds FOLD_KL = 1 / FOLD_BCE = 2):
+// train_KvsAll.py:216-294, loss.py:137-159 and :192-213 ----------------------------------------------------------------
+namespace {
+int ml_dist_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, int64_t n,
+                  const int64_t* lbl_rowptr, const int64_t* lbl_col) {
+  int rc = check_tables(t, true);
+  if (rc) return rc;
+  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
+  if (n < 0) return KGE_ERR_INVALID_ARG;
+  if (!ce_dist_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
+  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n))) return rc;
+  if (n > 0 && (!lbl_rowptr || !lbl_col)) return KGE_ERR_INVALID_ARG;
+  return KGE_OK;
+}
+}  // namespace
+
+int64_t kge_multilabel_dist_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
+  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_dist_tables_ok(t)) return 0;
+  if (chunk_cols < 0 || chunk_cols % 64) return 0;
+  return ml_dist_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+}
+
+int kge_kl_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                    const int64_t* lbl_col, const float* label_weight, float* loss_rows, float* lse, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ml_dist_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (n == 0) return KGE_OK;
+  if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_dist_fwd(1, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+                         (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col,
+                         label_weight, 0.0f, loss_rows, lse, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int kge_kl_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                    const int64_t* lbl_col, const float* label_weight, const float* lse, const float* g_rows,
+                    float g_scalar, float* g_a, float* g_p, float* g_tgt, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+  KGE_RANGE();
+  const int rc = ml_dist_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_dist_bwd(1, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+                         (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col,
+                         label_weight, 0.0f, lse, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
+                         (hipStream_t)stream);
+}
+
+int kge_bce_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                     const int64_t* lbl_col, float offset, float* loss_rows, void* workspace, int64_t workspace_bytes,
+                     void* stream) {
+  KGE_RANGE();
+  const int rc = ml_dist_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (n == 0) return KGE_OK;
+  if (!loss_rows) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_dist_fwd(2, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+                         (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr,
+                         offset, loss_rows, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int kge_bce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                     const int64_t* lbl_col, float offset, const float* g_rows, float g_scalar, float* g_a, float* g_p,
+                     float* g_tgt, void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ml_dist_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (!g_tgt || (n > 0 && (!g_a || !g_p))) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_dist_bwd(2, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+                         (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr,
+                         offset, nullptr, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
+                         (hipStream_t)stream);
 }
 
 // ---- the same with DENSE query rows (entity-sharded training: the query rows of a batch come out of

@@ -22,6 +22,19 @@
 //
 // Extra device memory: 4 n C bytes (the score chunk) + 4 n d (dQ) + 12 n G (the forward's records, G <= 256 column
 // groups): nothing that grows with n E.  No allocation, no host wait, no library call: stream-ordered and capturable.
+//
+// The KvsAll losses of the same scorers (kge_kl_dist_* / kge_bce_dist_*; train_KvsAll.py:216-294, loss.py:137-159 and
+// :192-213) run on the same kernels with another FOLD: labels are an int64 CSR per row instead of one index.
+//   forward   FOLD_KL keeps the running (max, sum exp) and tracks no label, FOLD_BCE folds sum softplus(score + offset);
+//             ml_dist_finish_kernel -- one wave per row -- scores the row's CSR entries with the tile's arithmetic (the
+//             same operations per coordinate pair in the same order: the bits of kge_score_sp / kge_score_po), sums them
+//             in CSR order and merges the row's records in column-group order.
+//   backward  per chunk a bit mask of n x C bits (ml_mask_kernel: one vector atomicOr per CSR entry whose column falls
+//             into the chunk) tells the gradient kernels whether (i, j) is a label: the weight becomes
+//             g_i (exp(S_ij - lse_i) - w_i [j in labels_i]) or g_i (sigmoid(S_ij + offset) - [j in labels_i]); g_i and
+//             w_i per row come from ml_rows_kernel (they live where the forward's records were).  Everything else --
+//             the chunk loop, dQ, the chain rule -- is the 1vsAll code.  The mask is cleared before every chunk and
+//             after the last one.
 #include "bwd_device.hpp"
 #include "pairs_device.hpp"
 
@@ -30,6 +43,18 @@ namespace kge {
 int run_pairs_exact(int scorer, int dtype, bool use_mfma, const Operand& A, const Operand& R, const Operand& TG, int dir,
                     int d, int dr, long long n, long long m, float lp, float* out, long long ldo, hipStream_t st,
                     bool round_query, const RankArgs* rk = nullptr);
+
+enum { FOLD_CE = 0, FOLD_KL = 1, FOLD_BCE = 2 };  // index label + log-sum-exp | CSR labels + log-sum-exp | + softplus
+
+// what the KvsAll folds of the backward read besides S: the chunk's label bits (row pitch `maskw` words), the per-row
+// upstream gradient (0 for a row without labels under the unweighted kl loss) and label weight, the bce offset
+struct MlArgs {
+  const unsigned int* mask;
+  long long maskw;
+  const float* grow;
+  const float* wrow;
+  float offset;
+};
 
 constexpr int CD_MAX_GROUPS = 256;                  // column groups per row (records of the forward)
 constexpr long long CD_CHUNK_BYTES = 32LL << 20;    // default score chunk of the backward
@@ -77,13 +102,44 @@ long long ce_dist_workspace_bytes(long long n, long long m, int d, long long chu
   return ce_dist_records_bytes(n, m) + ce_dist_dq_bytes(n, d) + cd_align(4 * n * c);
 }
 
+// KvsAll: records | dQ | S [n, C] | label bits [n, C / 32] words.  The backward keeps its per-row g_i and w_i (2 n floats)
+// where the forward's records were (12 n G bytes >= 8 n).
+static inline long long ml_chunk_bytes(long long n, long long c) { return cd_align(4 * n * c) + cd_align(n * c / 8); }
+
+long long ml_dist_chunk_cols(long long n, long long m, int d, long long bytes) {
+  const long long left = bytes - ce_dist_records_bytes(n, m) - ce_dist_dq_bytes(n, d);
+  if (left <= 0 || n <= 0) return 0;
+  long long c = left / n * 8 / 33 / 64 * 64;  // 4 + 1/8 bytes per row and column
+  const long long cap = (m + 63) / 64 * 64;
+  if (c > cap) c = cap;
+  while (c >= 64 && ml_chunk_bytes(n, c) > left) c -= 64;
+  return c < 64 ? 0 : c;
+}
+
+long long ml_dist_workspace_bytes(long long n, long long m, int d, long long chunk_cols) {
+  const long long cap = (m + 63) / 64 * 64;
+  long long c = chunk_cols;
+  if (c == 0) {
+    c = CD_CHUNK_BYTES / (4 * n) / 64 * 64;
+    if (c < 64) c = 64;
+  }
+  if (c > cap) c = cap;
+  return ce_dist_records_bytes(n, m) + ce_dist_dq_bytes(n, d) + ml_chunk_bytes(n, c);
+}
+
 // ---- forward ------------------------------------------------------------------------------------------------------
 // rec[(row * groups + g) * 3 + {0, 1, 2}] = max, sum exp(score - max), score(row, label_row) (0 where the label's
 // column is not in group g) over the group's valid columns.  A group of padding alone cannot exist (groups cover [0, m)).
-template <int SCORER, int NORM, bool VEC>
+// FOLD_KL: the same without a label (`label` is not read; rec[.. + 2] is not written).  FOLD_BCE: rec[.. + 0] =
+// sum softplus(score + offset) over the group's valid columns.
+__device__ __forceinline__ float softplus_f(float x) {  // max(x, 0) + log1p(exp(-|x|)) (loss.py:137-159)
+  return __builtin_fmaxf(x, 0.0f) + log1pf(expf(-__builtin_fabsf(x)));
+}
+
+template <int SCORER, int NORM, bool VEC, int FOLD>
 __global__ __launch_bounds__(256) void ce_dist_fwd_kernel(Operand A, Operand R, Operand TG, int dir, int d, int dr,
                                                           long long n, long long m, float lp, Index label, int col_tiles,
-                                                          int groups, float* __restrict__ rec) {
+                                                          int groups, float* __restrict__ rec, float offset) {
   __shared__ __attribute__((aligned(16))) float QT[2][2][PT_KC][PT_LD];  // operands; then the finished score tile
   auto& Qs = QT[0];
   auto& Ts = QT[1];
@@ -106,7 +162,7 @@ __global__ __launch_bounds__(256) void ce_dist_fwd_kernel(Operand A, Operand R, 
 
   // fold role: row fr of the tile (the staging row: qrow), columns 16 * fq .. + 15
   const int fr = sr, fq = scq;
-  const long long lbl = index_at(label, qrow);
+  const long long lbl = FOLD == FOLD_CE ? index_at(label, qrow) : -1;
   float run_m = -__builtin_inff(), run_s = 0.0f, lbl_score = 0.0f;
 
   for (int ct = 0; ct < col_tiles; ++ct) {
@@ -189,22 +245,32 @@ __global__ __launch_bounds__(256) void ce_dist_fwd_kernel(Operand A, Operand R, 
         const f32x4 x = *reinterpret_cast<const f32x4*>(&tile[fr * PT_LD + fq * 16 + q * 4]);
         v[q * 4 + 0] = x[0]; v[q * 4 + 1] = x[1]; v[q * 4 + 2] = x[2]; v[q * 4 + 3] = x[3];
       }
-      float tm = v[0];
-#pragma unroll
-      for (int k = 1; k < 16; ++k)
-        if (k < valid) tm = __builtin_fmaxf(tm, v[k]);
-      const float nm = __builtin_fmaxf(run_m, tm);
-      float s = run_s * expf(run_m - nm);  // (first tile: 0 * exp(-inf) = 0)
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < valid) s += expf(v[k] - nm);
-      run_m = nm;
-      run_s = s;
-      const long long off = lbl - cbase;
-      if (off >= 0 && off < valid) {
+      if (FOLD == FOLD_BCE) {
+        float s = run_s;
 #pragma unroll
         for (int k = 0; k < 16; ++k)
-          if (k == (int)off) lbl_score = v[k];
+          if (k < valid) s += softplus_f(v[k] + offset);
+        run_s = s;
+      } else {
+        float tm = v[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k)
+          if (k < valid) tm = __builtin_fmaxf(tm, v[k]);
+        const float nm = __builtin_fmaxf(run_m, tm);
+        float s = run_s * expf(run_m - nm);  // (first tile: 0 * exp(-inf) = 0)
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+          if (k < valid) s += expf(v[k] - nm);
+        run_m = nm;
+        run_s = s;
+      }
+      if (FOLD == FOLD_CE) {
+        const long long off = lbl - cbase;
+        if (off >= 0 && off < valid) {
+#pragma unroll
+          for (int k = 0; k < 16; ++k)
+            if (k == (int)off) lbl_score = v[k];
+        }
       }
     }
   }
@@ -217,6 +283,10 @@ __global__ __launch_bounds__(256) void ce_dist_fwd_kernel(Operand A, Operand R, 
     pm[k] = __shfl(run_m, src, 64);
     ps[k] = __shfl(run_s, src, 64);
     pl[k] = __shfl(lbl_score, src, 64);
+  }
+  if (FOLD == FOLD_BCE) {
+    if (fq == 0 && row0 + fr < n) rec[((row0 + fr) * groups + blockIdx.x) * 3] = ((ps[0] + ps[1]) + ps[2]) + ps[3];
+    return;
   }
   if (fq == 0 && row0 + fr < n) {
     float mm = pm[0];
@@ -231,7 +301,7 @@ __global__ __launch_bounds__(256) void ce_dist_fwd_kernel(Operand A, Operand R, 
     float* out = rec + ((row0 + fr) * groups + blockIdx.x) * 3;
     out[0] = mm;
     out[1] = ss;
-    out[2] = ll;
+    if (FOLD == FOLD_CE) out[2] = ll;
   }
 }
 
@@ -263,13 +333,124 @@ static int launch_fwd(bool vec, const Operand& A, const Operand& R, const Operan
   cd_groups(n, m, ct, groups);
   const dim3 grid((unsigned)groups, (unsigned)((n + PT_BM - 1) / PT_BM));
   if (vec)
-    hipLaunchKernelGGL((ce_dist_fwd_kernel<SCORER, NORM, true>), grid, dim3(256), 0, st, A, R, TG, dir, d, dr, n, m, lp,
-                       label, ct, groups, rec);
+    hipLaunchKernelGGL((ce_dist_fwd_kernel<SCORER, NORM, true, FOLD_CE>), grid, dim3(256), 0, st, A, R, TG, dir, d, dr, n, m,
+                       lp, label, ct, groups, rec, 0.0f);
   else
-    hipLaunchKernelGGL((ce_dist_fwd_kernel<SCORER, NORM, false>), grid, dim3(256), 0, st, A, R, TG, dir, d, dr, n, m, lp,
-                       label, ct, groups, rec);
+    hipLaunchKernelGGL((ce_dist_fwd_kernel<SCORER, NORM, false, FOLD_CE>), grid, dim3(256), 0, st, A, R, TG, dir, d, dr, n, m,
+                       lp, label, ct, groups, rec, 0.0f);
   hipLaunchKernelGGL(ce_dist_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rec, groups, ct, n, m,
                      label, loss_rows, lse);
+  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+}
+
+// score(i, j) with the bits the tile stores at (i, j): the operations of dist_micro_tile on one live element, coordinate
+// pairs 0 .. hh - 1 in order (the tile's padding pairs add |0 - 0| = 0: no change), then dist_score.  RotatE takes the
+// IEEE square root: both branches of the micro-tile are correctly rounded, so the bits do not depend on the branch.
+template <int SCORER, int NORM>
+__device__ __forceinline__ float dist_label_score(const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                                                  int dr, long long i, long long j, float lp) {
+  const int hh = (d + 1) / 2, lim1 = d - hh;
+  const int rl0 = (SCORER == KGE_ROTATE) ? dr : hh;
+  const int rl1 = (SCORER == KGE_ROTATE) ? 0 : lim1;
+  const float* arow = (const float*)A.base + index_at(A.idx, i) * A.ld;
+  const float* rrow = (const float*)R.base + index_at(R.idx, i) * R.ld;
+  const float* trow = (const float*)TG.base + index_at(TG.idx, j) * TG.ld;
+  float acc = 0.0f;
+  for (int c = 0; c < hh; ++c) {
+    const f32x4 a0v{ldf(arow, c, hh), 0, 0, 0}, a1v{ldf(arow + hh, c, lim1), 0, 0, 0};
+    f32x4 r0v{ldf(rrow, c, rl0), 0, 0, 0}, r1v{0, 0, 0, 0};
+    if (SCORER != KGE_ROTATE) r1v[0] = ldf(rrow + hh, c, rl1);
+    f32x4 q0v, q1v;
+    build_q4<SCORER>(dir, a0v, a1v, r0v, r1v, q0v, q1v);
+    const float t0 = ldf(trow, c, hh), t1 = ldf(trow + hh, c, lim1);
+    if (SCORER == KGE_TRANSE) {
+      acc = norm_acc<NORM>(acc, __builtin_fabsf(q0v[0] - t0), lp);
+      acc = norm_acc<NORM>(acc, __builtin_fabsf(q1v[0] - t1), lp);
+    } else {
+      const float dre = q0v[0] - t0, dim_ = q1v[0] - t1;
+      acc = norm_acc<NORM>(acc, __builtin_sqrtf(__builtin_fmaf(dim_, dim_, dre * dre)), lp);
+    }
+  }
+  return dist_score<NORM>(acc, lp);
+}
+
+// One WAVE per row: the scores of the row's CSR entries (64 at a time, one per lane), summed in CSR order, and the
+// row's records merged in column-group order.
+//   FOLD_KL   lse[i] as ce_dist_merge_kernel; loss_rows[i] = lse - w_i sum (label_weight given: every row) or
+//             lse - sum / k_i - log k_i (0 for k_i = 0): kl_combine_kernel's expressions (ce_loss.hip)
+//   FOLD_BCE  loss_rows[i] = sum_g rec - sum over the labels of (score + offset)
+// A label outside [0, m) is not scored: loss_rows[i] = NaN.
+template <int SCORER, int NORM, int FOLD>
+__global__ __launch_bounds__(256) void ml_dist_finish_kernel(Operand A, Operand R, Operand TG, int dir, int d, int dr,
+                                                             long long n, long long m, float lp,
+                                                             const float* __restrict__ rec, int groups,
+                                                             const long long* __restrict__ rowptr,
+                                                             const long long* __restrict__ col,
+                                                             const float* __restrict__ label_weight, float offset,
+                                                             float* __restrict__ loss_rows, float* __restrict__ lse) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;  // (the whole wave)
+  const long long b = rowptr[i], e = rowptr[i + 1];
+  float sum = 0.0f;
+  bool bad = false;
+  for (long long base = b; base < e; base += 64) {
+    const long long x = base + lane;
+    float sc = 0.0f;
+    bool oob = false;
+    if (x < e) {
+      const long long j = col[x];
+      oob = j < 0 || j >= m;
+      if (!oob) {
+        sc = dist_label_score<SCORER, NORM>(A, R, TG, dir, d, dr, i, j, lp);
+        if (FOLD == FOLD_BCE) sc += offset;
+      }
+    }
+    bad = bad || __ballot(oob) != 0ULL;
+    const int cnt = e - base < 64 ? (int)(e - base) : 64;
+    for (int l = 0; l < cnt; ++l) sum += __shfl(sc, l, 64);
+  }
+  if (lane != 0) return;
+  const float* r = rec + i * groups * 3;
+  const long long k = e - b;
+  const float nan = __builtin_nanf("");
+  if (FOLD == FOLD_BCE) {
+    float tot = 0.0f;
+    for (int g = 0; g < groups; ++g) tot += r[g * 3];
+    loss_rows[i] = bad ? nan : tot - sum;
+    return;
+  }
+  float mm = -__builtin_inff();
+  for (int g = 0; g < groups; ++g)
+    if (r[g * 3 + 1] > 0.0f) mm = __builtin_fmaxf(mm, r[g * 3]);
+  float ss = 0.0f;
+  for (int g = 0; g < groups; ++g)
+    if (r[g * 3 + 1] > 0.0f) ss += r[g * 3 + 1] * expf(r[g * 3] - mm);
+  const float z = mm + logf(ss);
+  lse[i] = z;
+  float out;
+  if (label_weight != nullptr) out = z - label_weight[i] * (k > 0 ? sum : 0.0f);
+  else out = k > 0 ? z - sum / (float)k - logf((float)k) : 0.0f;
+  loss_rows[i] = bad ? nan : out;
+}
+
+template <int SCORER, int NORM, int FOLD>
+static int launch_ml_fwd(bool vec, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
+                         long long n, long long m, float lp, const long long* rowptr, const long long* col,
+                         const float* label_weight, float offset, float* loss_rows, float* lse, float* rec,
+                         hipStream_t st) {
+  int ct, groups;
+  cd_groups(n, m, ct, groups);
+  const dim3 grid((unsigned)groups, (unsigned)((n + PT_BM - 1) / PT_BM));
+  const Index none{nullptr, 1, KGE_I64};  // (not read by these folds)
+  if (vec)
+    hipLaunchKernelGGL((ce_dist_fwd_kernel<SCORER, NORM, true, FOLD>), grid, dim3(256), 0, st, A, R, TG, dir, d, dr, n, m, lp,
+                       none, ct, groups, rec, offset);
+  else
+    hipLaunchKernelGGL((ce_dist_fwd_kernel<SCORER, NORM, false, FOLD>), grid, dim3(256), 0, st, A, R, TG, dir, d, dr, n, m,
+                       lp, none, ct, groups, rec, offset);
+  hipLaunchKernelGGL((ml_dist_finish_kernel<SCORER, NORM, FOLD>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, A, R, TG,
+                     dir, d, dr, n, m, lp, rec, groups, rowptr, col, label_weight, offset, loss_rows, lse);
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 
@@ -303,6 +484,32 @@ int run_ce_dist_fwd(int scorer, float lp, const Operand& A, const Operand& R, co
 #undef KGE_CDF
 }
 
+// fold: FOLD_KL (lse written, label_weight or NULL) or FOLD_BCE (lse not touched, offset)
+int run_ml_dist_fwd(int fold, int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                    int dr, long long n, long long m, const long long* rowptr, const long long* col,
+                    const float* label_weight, float offset, float* loss_rows, float* lse, void* ws, long long ws_bytes,
+                    hipStream_t st) {
+  if (n == 0) return KGE_OK;
+  const int norm = norm_mode(lp);
+  if (norm == NORM_LP || (scorer != KGE_TRANSE && scorer != KGE_ROTATE)) return KGE_ERR_UNSUPPORTED;
+  if (n > 65535LL * PT_BM) return KGE_ERR_UNSUPPORTED;
+  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < ce_dist_records_bytes(n, m)) return KGE_ERR_WORKSPACE;
+  const bool vec = cd_vec_ok(scorer, d, dr, A, R, TG);
+  float* rec = (float*)ws;
+#define KGE_MLF(SC, NM)                                                                                                  \
+  return fold == FOLD_KL ? launch_ml_fwd<SC, NM, FOLD_KL>(vec, A, R, TG, dir, d, dr, n, m, lp, rowptr, col, label_weight, \
+                                                          offset, loss_rows, lse, rec, st)                               \
+                         : launch_ml_fwd<SC, NM, FOLD_BCE>(vec, A, R, TG, dir, d, dr, n, m, lp, rowptr, col, label_weight, \
+                                                           offset, loss_rows, lse, rec, st)
+  if (scorer == KGE_TRANSE) {
+    if (norm == NORM_L1) KGE_MLF(KGE_TRANSE, NORM_L1);
+    KGE_MLF(KGE_TRANSE, NORM_L2);
+  }
+  if (norm == NORM_L1) KGE_MLF(KGE_ROTATE, NORM_L1);
+  KGE_MLF(KGE_ROTATE, NORM_L2);
+#undef KGE_MLF
+}
+
 // ---- backward -----------------------------------------------------------------------------------------------------
 constexpr int CB_TR = 64, CB_TC = 32, CB_KY = 16;
 
@@ -311,14 +518,15 @@ constexpr int CB_TR = 64, CB_TC = 32, CB_KY = 16;
 // WHICH == 1: rows = the chunk's targets (entity col_lo + x), the reduction runs over all n queries in order;
 //             g_tgt rows col_lo .. col_lo + mc - 1 are OVERWRITTEN.
 // S [n, lds]: the chunk's scores, column y = entity col_lo + y; mc valid columns.
-template <int SCORER, int NORM, int WHICH>
+// FOLD_KL / FOLD_BCE: `lse` as before (unused for bce), `label`, `g_rows` and `g_scalar` are not read: ml carries the rows.
+template <int SCORER, int NORM, int WHICH, int FOLD>
 __global__ __launch_bounds__(256) void ce_dist_bwd_kernel(Operand A, Operand R, Operand TG, int dir, int d, int dr,
                                                           long long n, long long col_lo, long long mc, float lp,
                                                           const float* __restrict__ S, long long lds,
                                                           const float* __restrict__ lse, Index label,
                                                           const float* __restrict__ g_rows, float g_scalar,
                                                           float* __restrict__ dq, float* __restrict__ g_tgt,
-                                                          long long ychunk) {
+                                                          long long ychunk, MlArgs ml) {
   constexpr bool NEED_DIST = NORM != NORM_L1;
   __shared__ float Gs[CB_KY][CB_TR + 4];
   __shared__ float Ds[CB_KY][CB_TR + 4];
@@ -374,10 +582,18 @@ __global__ __launch_bounds__(256) void ce_dist_bwd_kernel(Operand A, Operand R, 
   // the weight of (query i, chunk column y): g_i (softmax_ij - [j == label_i]) from the stored score
   auto weight = [&](long long i, long long y, float& g, float& dist) {
     const float s = S[i * lds + y];
-    const float gi = g_rows != nullptr ? g_rows[i] : g_scalar;
-    float w = expf(s - lse[i]);
-    if (index_at(label, i) == col_lo + y) w -= 1.0f;
-    g = gi * w;
+    if (FOLD == FOLD_CE) {
+      const float gi = g_rows != nullptr ? g_rows[i] : g_scalar;
+      float w = expf(s - lse[i]);
+      if (index_at(label, i) == col_lo + y) w -= 1.0f;
+      g = gi * w;
+    } else {
+      // KvsAll: g_i (exp(S_ij - lse_i) - w_i [j in labels_i]) or g_i (sigmoid(S_ij + offset) - [j in labels_i])
+      const bool in = (ml.mask[i * ml.maskw + (y >> 5)] >> (y & 31)) & 1u;
+      float w = FOLD == FOLD_KL ? expf(s - lse[i]) : 1.0f / (1.0f + expf(-(s + ml.offset)));
+      if (in) w -= FOLD == FOLD_KL ? ml.wrow[i] : 1.0f;
+      g = ml.grow[i] * w;
+    }
     dist = -s;
   };
 
@@ -520,11 +736,11 @@ __global__ __launch_bounds__(256) void ce_dist_chain_kernel(Operand A, Operand R
   if (SCORER != KGE_ROTATE && has1) g_p[x * dr + hh + c] = dr1;
 }
 
-template <int SCORER, int NORM>
+template <int SCORER, int NORM, int FOLD>
 static int launch_bwd_chunk(const Operand& A, const Operand& R, const Operand& TGall, int dir, int d, int dr, long long n,
                             long long col_lo, long long mc, float lp, const float* S, long long lds, const float* lse,
                             const Index& label, const float* g_rows, float g_scalar, float* dq, float* g_tgt,
-                            hipStream_t st) {
+                            hipStream_t st, const MlArgs& ml) {
   const int hh = (d + 1) / 2;
   const unsigned gc = (unsigned)((hh + CB_TC - 1) / CB_TC);
   const unsigned gr = (unsigned)((n + CB_TR - 1) / CB_TR);
@@ -534,18 +750,58 @@ static int launch_bwd_chunk(const Operand& A, const Operand& R, const Operand& T
   if (ys < 1) ys = 1;
   long long ychunk = ((mc + ys - 1) / ys + CB_KY - 1) / CB_KY * CB_KY;
   ys = (mc + ychunk - 1) / ychunk;
-  hipLaunchKernelGGL((ce_dist_bwd_kernel<SCORER, NORM, 0>), dim3(gc, gr, (unsigned)ys), dim3(256), 0, st, A, R, TGall, dir,
-                     d, dr, n, col_lo, mc, lp, S, lds, lse, label, g_rows, g_scalar, dq, g_tgt, ychunk);
-  hipLaunchKernelGGL((ce_dist_bwd_kernel<SCORER, NORM, 1>), dim3(gc, (unsigned)((mc + CB_TR - 1) / CB_TR)), dim3(256), 0,
-                     st, A, R, TGall, dir, d, dr, n, col_lo, mc, lp, S, lds, lse, label, g_rows, g_scalar, dq, g_tgt,
-                     (long long)n);
+  hipLaunchKernelGGL((ce_dist_bwd_kernel<SCORER, NORM, 0, FOLD>), dim3(gc, gr, (unsigned)ys), dim3(256), 0, st, A, R, TGall,
+                     dir, d, dr, n, col_lo, mc, lp, S, lds, lse, label, g_rows, g_scalar, dq, g_tgt, ychunk, ml);
+  hipLaunchKernelGGL((ce_dist_bwd_kernel<SCORER, NORM, 1, FOLD>), dim3(gc, (unsigned)((mc + CB_TR - 1) / CB_TR)), dim3(256),
+                     0, st, A, R, TGall, dir, d, dr, n, col_lo, mc, lp, S, lds, lse, label, g_rows, g_scalar, dq, g_tgt,
+                     (long long)n, ml);
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 
+// ---- KvsAll: the rows' g_i / w_i and the chunk's label bits -----------------------------------------------------------
+// grow[i] = the upstream gradient of row i (0 for a row without labels under the unweighted kl loss: its loss is the
+// constant 0), wrow[i] = label_weight[i] or 1 / k_i (kl only).
+__global__ __launch_bounds__(256) void ml_rows_kernel(long long n, const long long* __restrict__ rowptr,
+                                                      const float* __restrict__ label_weight, int fold,
+                                                      const float* __restrict__ g_rows, float g_scalar,
+                                                      float* __restrict__ grow, float* __restrict__ wrow) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float gi = g_rows != nullptr ? g_rows[i] : g_scalar;
+  float w = 1.0f;
+  if (fold == FOLD_KL) {
+    const long long k = rowptr[i + 1] - rowptr[i];
+    if (label_weight != nullptr) w = label_weight[i];
+    else if (k > 0) w = 1.0f / (float)k;
+    else gi = 0.0f;
+  }
+  grow[i] = gi;
+  wrow[i] = w;
+}
+
+// One wave per row: bit (i, j - col_lo) of the mask for every CSR entry (i, j) with col_lo <= j < col_lo + mc.  Labels
+// outside the chunk -- outside [0, m) among them -- set nothing.
+__global__ __launch_bounds__(256) void ml_mask_kernel(long long n, const long long* __restrict__ rowptr,
+                                                      const long long* __restrict__ col, long long col_lo, long long mc,
+                                                      unsigned int* __restrict__ mask, long long maskw) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const long long e = rowptr[i + 1];
+  for (long long x = rowptr[i] + lane; x < e; x += 64) {
+    const long long y = col[x] - col_lo;
+    if (y < 0 || y >= mc) continue;
+    atomicOr(mask + i * maskw + (y >> 5), 1u << (y & 31));
+  }
+}
+
+// The chunk loop of both losses.  fold == FOLD_CE: label / g_rows / g_scalar; else the CSR, label_weight and offset.
 // TG: ALL rows of the entity table (identity index)
-int run_ce_dist_bwd(int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
-                    long long n, long long m, const Index& label, const float* lse, const float* g_rows, float g_scalar,
-                    float* g_a, float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st) {
+static int run_dist_bwd(int fold, int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir,
+                        int d, int dr, long long n, long long m, const Index& label, const long long* rowptr,
+                        const long long* col, const float* label_weight, float offset, const float* lse,
+                        const float* g_rows, float g_scalar, float* g_a, float* g_p, float* g_tgt, void* ws,
+                        long long ws_bytes, hipStream_t st) {
   if (n == 0) {  // no query: the entity rows get a zero gradient
     return fill_words_async(g_tgt, 0, (size_t)m * d * sizeof(float), st) ? KGE_OK : KGE_ERR_LAUNCH;
   }
@@ -553,19 +809,39 @@ int run_ce_dist_bwd(int scorer, float lp, const Operand& A, const Operand& R, co
   if (norm == NORM_LP || (scorer != KGE_TRANSE && scorer != KGE_ROTATE)) return KGE_ERR_UNSUPPORTED;
   if (n > 65535LL * CB_TR) return KGE_ERR_UNSUPPORTED;
   if (!ws || ((uintptr_t)ws & 255)) return KGE_ERR_WORKSPACE;
-  const long long C = ce_dist_chunk_cols(n, m, d, ws_bytes);
+  const long long C = fold == FOLD_CE ? ce_dist_chunk_cols(n, m, d, ws_bytes) : ml_dist_chunk_cols(n, m, d, ws_bytes);
   if (C < 64) return KGE_ERR_WORKSPACE;
   if (C > 65535LL * CB_TR) return KGE_ERR_UNSUPPORTED;
   float* dq = (float*)((char*)ws + ce_dist_records_bytes(n, m));
   float* S = (float*)((char*)dq + ce_dist_dq_bytes(n, d));
+  MlArgs ml{};
+  unsigned int* mask = nullptr;
+  const size_t mask_bytes = (size_t)(n * C / 8);
+  if (fold != FOLD_CE) {
+    mask = (unsigned int*)((char*)S + cd_align(4 * n * C));
+    float* rows = (float*)ws;  // (where the forward's records were)
+    ml = MlArgs{mask, C / 32, rows, rows + n, offset};
+    hipLaunchKernelGGL(ml_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, rowptr, label_weight, fold,
+                       g_rows, g_scalar, rows, rows + n);
+  }
   if (!fill_words_async(dq, 0, (size_t)n * d * sizeof(float), st)) return KGE_ERR_LAUNCH;
   for (long long lo = 0; lo < m; lo += C) {
     const long long mc = m - lo < C ? m - lo : C;
     const Operand TGc{(const char*)TG.base + lo * TG.ld * (long long)sizeof(float), TG.ld, Index{nullptr, 1, KGE_I64}};
     int rc = run_pairs_exact(scorer, KGE_F32, false, A, R, TGc, dir, d, dr, n, mc, lp, S, C, st, true);
     if (rc != KGE_OK) return rc;
-#define KGE_CDB(SC, NM)                                                                                             \
-  rc = launch_bwd_chunk<SC, NM>(A, R, TG, dir, d, dr, n, lo, mc, lp, S, C, lse, label, g_rows, g_scalar, dq, g_tgt, st)
+    if (fold != FOLD_CE) {
+      if (!fill_words_async(mask, 0, mask_bytes, st)) return KGE_ERR_LAUNCH;
+      hipLaunchKernelGGL(ml_mask_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, n, rowptr, col, lo, mc, mask,
+                         C / 32);
+    }
+#define KGE_CDB(SC, NM)                                                                                                   \
+  rc = fold == FOLD_CE   ? launch_bwd_chunk<SC, NM, FOLD_CE>(A, R, TG, dir, d, dr, n, lo, mc, lp, S, C, lse, label, g_rows, \
+                                                             g_scalar, dq, g_tgt, st, ml)                                 \
+       : fold == FOLD_KL ? launch_bwd_chunk<SC, NM, FOLD_KL>(A, R, TG, dir, d, dr, n, lo, mc, lp, S, C, lse, label, g_rows, \
+                                                             g_scalar, dq, g_tgt, st, ml)                                 \
+                         : launch_bwd_chunk<SC, NM, FOLD_BCE>(A, R, TG, dir, d, dr, n, lo, mc, lp, S, C, lse, label, g_rows, \
+                                                              g_scalar, dq, g_tgt, st, ml)
     if (scorer == KGE_TRANSE) {
       if (norm == NORM_L1) KGE_CDB(KGE_TRANSE, NORM_L1);
       else KGE_CDB(KGE_TRANSE, NORM_L2);
@@ -576,6 +852,8 @@ int run_ce_dist_bwd(int scorer, float lp, const Operand& A, const Operand& R, co
 #undef KGE_CDB
     if (rc != KGE_OK) return rc;
   }
+  // (the mask is left all-zero: a workspace handed on holds no label of this call)
+  if (fold != FOLD_CE && !fill_words_async(mask, 0, mask_bytes, st)) return KGE_ERR_LAUNCH;
   const long long cells = n * ((d + 1) / 2);
   const dim3 cgrid((unsigned)((cells + 255) / 256));
   if (scorer == KGE_TRANSE)
@@ -583,6 +861,22 @@ int run_ce_dist_bwd(int scorer, float lp, const Operand& A, const Operand& R, co
   else
     hipLaunchKernelGGL((ce_dist_chain_kernel<KGE_ROTATE>), cgrid, dim3(256), 0, st, A, R, dir, d, dr, n, dq, g_a, g_p);
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+}
+
+int run_ce_dist_bwd(int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
+                    long long n, long long m, const Index& label, const float* lse, const float* g_rows, float g_scalar,
+                    float* g_a, float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st) {
+  return run_dist_bwd(FOLD_CE, scorer, lp, A, R, TG, dir, d, dr, n, m, label, nullptr, nullptr, nullptr, 0.0f, lse, g_rows,
+                      g_scalar, g_a, g_p, g_tgt, ws, ws_bytes, st);
+}
+
+// fold: FOLD_KL (lse, label_weight or NULL) or FOLD_BCE (offset)
+int run_ml_dist_bwd(int fold, int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                    int dr, long long n, long long m, const long long* rowptr, const long long* col,
+                    const float* label_weight, float offset, const float* lse, const float* g_rows, float g_scalar,
+                    float* g_a, float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st) {
+  return run_dist_bwd(fold, scorer, lp, A, R, TG, dir, d, dr, n, m, Index{nullptr, 1, KGE_I64}, rowptr, col, label_weight,
+                      offset, lse, g_rows, g_scalar, g_a, g_p, g_tgt, ws, ws_bytes, st);
 }
 
 }  // namespace kge

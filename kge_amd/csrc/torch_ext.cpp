@@ -254,6 +254,112 @@ std::vector<at::Tensor> ce_dist_bwd(const at::Tensor& ent, const at::Tensor& rel
   return {g_a, g_p, g_t};
 }
 
+// ---- the KvsAll losses of TransE / RotatE on float32 tables (kge_kl_dist_* / kge_bce_dist_*): labels as an int64 CSR
+// (rowptr [n + 1], col [nnz]) on the tables' device; workspace as above (kge_multilabel_dist_workspace_bytes).
+int64_t multilabel_dist_workspace_bytes(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                        int64_t n, int64_t chunk_cols) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  return kge_multilabel_dist_workspace_bytes(&t, n, chunk_cols);
+}
+
+struct DistLabels {
+  at::Tensor rowptr, col, weight, g_rows;
+  const float* w = nullptr;
+  const float* g = nullptr;
+};
+
+DistLabels dist_labels(const at::Tensor& ent, int64_t n, const at::Tensor& rowptr, const at::Tensor& col,
+                       const c10::optional<at::Tensor>& weight, const c10::optional<at::Tensor>& g_rows) {
+  DistLabels l;
+  TORCH_CHECK(rowptr.is_cuda() && col.is_cuda() && rowptr.get_device() == ent.get_device() &&
+                  col.get_device() == ent.get_device(), "kge_amd: the label CSR must live on the tables' device");
+  l.rowptr = rowptr.to(at::kLong).contiguous();
+  l.col = col.to(at::kLong).contiguous();
+  if (l.col.numel() == 0) l.col = at::zeros({1}, l.col.options());
+  TORCH_CHECK_VALUE(l.rowptr.numel() == n + 1, "kge_amd: label rowptr has ", l.rowptr.numel(), " entries for ", n, " rows");
+  if (weight.has_value() && weight->defined()) {
+    l.weight = weight->to(at::kFloat).contiguous();
+    TORCH_CHECK_VALUE(l.weight.numel() == n, "kge_amd: label_weight must have one entry per row");
+    l.w = l.weight.data_ptr<float>();
+  }
+  if (g_rows.has_value() && g_rows->defined()) {
+    l.g_rows = g_rows->to(at::kFloat).contiguous();
+    TORCH_CHECK_VALUE(l.g_rows.numel() == n, "kge_amd: g_rows must have one entry per row");
+    l.g = l.g_rows.data_ptr<float>();
+  }
+  return l;
+}
+
+std::vector<at::Tensor> kl_dist_fwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                    int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr,
+                                    const at::Tensor& col, const c10::optional<at::Tensor>& label_weight,
+                                    const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, label_weight, c10::nullopt);
+  at::Tensor loss_rows = empty_f32({n}, ent), lse = empty_f32({n}, ent);
+  check(kge_kl_dist_fwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(), l.w,
+                        loss_rows.data_ptr<float>(), lse.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes),
+                        workspace_bytes, stream_of(ent)),
+        "kge_kl_dist_fwd");
+  return {loss_rows, lse};
+}
+
+std::vector<at::Tensor> kl_dist_bwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                    int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr,
+                                    const at::Tensor& col, const c10::optional<at::Tensor>& label_weight,
+                                    const at::Tensor& lse, const c10::optional<at::Tensor>& g_rows, double g_scalar,
+                                    const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, label_weight, g_rows);
+  const at::Tensor lse_c = lse.to(at::kFloat).contiguous();
+  TORCH_CHECK_VALUE(lse_c.numel() == n, "kge_amd: lse must have one entry per row");
+  at::Tensor g_a = empty_f32({n, t.dim}, ent), g_p = empty_f32({n, t.rel_dim}, ent), g_t = empty_f32({t.num_ent, t.dim}, ent);
+  check(kge_kl_dist_bwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(), l.w,
+                        lse_c.data_ptr<float>(), l.g, (float)g_scalar, g_a.data_ptr<float>(), g_p.data_ptr<float>(),
+                        g_t.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes), workspace_bytes, stream_of(ent)),
+        "kge_kl_dist_bwd");
+  return {g_a, g_p, g_t};
+}
+
+at::Tensor bce_dist_fwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t direction,
+                        const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr, const at::Tensor& col,
+                        double offset, const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, c10::nullopt, c10::nullopt);
+  at::Tensor loss_rows = empty_f32({n}, ent);
+  check(kge_bce_dist_fwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(),
+                         (float)offset, loss_rows.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes),
+                         workspace_bytes, stream_of(ent)),
+        "kge_bce_dist_fwd");
+  return loss_rows;
+}
+
+std::vector<at::Tensor> bce_dist_bwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                     int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr,
+                                     const at::Tensor& col, double offset, const c10::optional<at::Tensor>& g_rows,
+                                     double g_scalar, const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, c10::nullopt, g_rows);
+  at::Tensor g_a = empty_f32({n, t.dim}, ent), g_p = empty_f32({n, t.rel_dim}, ent), g_t = empty_f32({t.num_ent, t.dim}, ent);
+  check(kge_bce_dist_bwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(),
+                         (float)offset, l.g, (float)g_scalar, g_a.data_ptr<float>(), g_p.data_ptr<float>(),
+                         g_t.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes), workspace_bytes, stream_of(ent)),
+        "kge_bce_dist_bwd");
+  return {g_a, g_p, g_t};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -267,4 +373,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ce_dist_workspace_bytes", &ce_dist_workspace_bytes);
   mod.def("ce_dist_fwd", &ce_dist_fwd, "1vsAll cross entropy of TransE / RotatE without a score matrix: (loss_rows, lse)");
   mod.def("ce_dist_bwd", &ce_dist_bwd, "its backward: (g_a, g_p, g_entities)");
+  mod.def("multilabel_dist_workspace_bytes", &multilabel_dist_workspace_bytes);
+  mod.def("kl_dist_fwd", &kl_dist_fwd, "KvsAll kl loss of TransE / RotatE without a score matrix: (loss_rows, lse)");
+  mod.def("kl_dist_bwd", &kl_dist_bwd, "its backward: (g_a, g_p, g_entities)");
+  mod.def("bce_dist_fwd", &bce_dist_fwd, "KvsAll bce loss of TransE / RotatE without a score matrix: loss_rows");
+  mod.def("bce_dist_bwd", &bce_dist_bwd, "its backward: (g_a, g_p, g_entities)");
 }

@@ -1563,6 +1563,132 @@ def ce_dist_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scal
     return g_a, g_p, g_t
 
 
+# ---- KvsAll losses of the distance scorers (kge_kl_dist_* / kge_bce_dist_*): labels as an int64 CSR per row -------------
+def _ml_dist_args(t: Tables, a, p, lbl_rowptr, lbl_col, chunk_cols, what):
+    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths, the CSR."""
+    chunk_cols = int(chunk_cols)
+    if chunk_cols < 0 or chunk_cols % 64:
+        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 64, got {chunk_cols}")
+    if t.scorer not in (_lib.TRANSE, _lib.ROTATE) or t.ent.dtype != torch.float32 or t.l_norm not in (1.0, 2.0):
+        raise RuntimeError(f"kge_amd: {what}: TransE / RotatE on float32 tables with l_norm 1 or 2 only "
+                           "(ComplEx / DistMult on bf16 tables: kl_fwd / bce_fwd)")
+    keep = []
+    ixs = tuple(_index(x, t.device, keep) for x in (a, p))
+    n = _same_len(keep[:2], what)
+    if not torch.is_tensor(lbl_rowptr) or not torch.is_tensor(lbl_col) or lbl_rowptr.dim() != 1 or lbl_col.dim() != 1:
+        raise ValueError(f"kge_amd: {what}: the labels are a CSR of two 1-d tensors (rowptr [n + 1], col [nnz])")
+    if lbl_rowptr.is_floating_point() or lbl_col.is_floating_point():
+        raise TypeError(f"kge_amd: {what}: the label CSR holds integers")
+    if lbl_rowptr.numel() != n + 1:
+        raise ValueError(f"kge_amd: {what}: label rowptr has {lbl_rowptr.numel()} entries for {n} rows")
+    _require_gpu(t.ent, "entity table")
+    rp, cl = _csr64(lbl_rowptr, lbl_col, t.device)
+    return ixs, n, chunk_cols, rp, cl, keep
+
+
+def _ml_dist_rows(x, n, dev, what, name):
+    if x is None:
+        return None
+    x = _f32c(x, dev)
+    if x.numel() != n:
+        raise ValueError(f"kge_amd: {what}: {name} has {x.numel()} entries for {n} rows")
+    return x
+
+
+def _ml_dist_workspace(tc, n, chunk_cols, device, st):
+    """(ptr, bytes): the per-(device, stream) scratch of kge_kl_dist_* / kge_bce_dist_*; `bytes` is exactly what the
+    chunk width asks for (the backward derives its chunk width from it), the buffer may be larger."""
+    need = _lib.lib().kge_multilabel_dist_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
+    if need <= 0:
+        raise RuntimeError("kge_kl_dist_* / kge_bce_dist_*: float32 TransE / RotatE tables with l_norm 1 or 2 only")
+    key = (device.index, st, "ml_dist")
+    buf = _WORKSPACES.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
+    return buf.data_ptr(), need
+
+
+def kl_dist_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, label_weight=None, chunk_cols: int = 0):
+    """kl_fwd for TransE / RotatE on float32 tables (kge_kl_dist_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
+    a = s) / score_po ('po': a = o) against all entities with the rows' labels as an int64 CSR (ids in any order), no
+    [n, E] matrix.  label_weight [n]: loss_rows[i] = lse[i] - label_weight[i] * (sum of row i's label scores)."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_dist_fwd")
+    lw = _ml_dist_rows(label_weight, n, t.device, "kl_dist_fwd", "label_weight")
+    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
+    if n == 0:
+        return loss_rows, lse
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_kl_dist_fwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
+            None if lw is None else lw.data_ptr(), loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_kl_dist_fwd")
+    return loss_rows, lse
+
+
+def kl_dist_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, lse, g_rows=None, g_scalar: float = 1.0,
+                label_weight=None, chunk_cols: int = 0):
+    """Backward of kl_dist_fwd (kge_kl_dist_bwd): (g_a [n, d], g_p [n, d_r], g_entities [E, d]).  chunk_cols: entity
+    columns per chunk (a multiple of 64; 0 = the library's default, a score chunk of at most 32 MB)."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_dist_bwd")
+    d, dr = t.ent.shape[1], t.rel.shape[1]
+    lse = _ml_dist_rows(lse, n, t.device, "kl_dist_bwd", "lse")
+    gr = _ml_dist_rows(g_rows, n, t.device, "kl_dist_bwd", "g_rows")
+    lw = _ml_dist_rows(label_weight, n, t.device, "kl_dist_bwd", "label_weight")
+    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
+    if n == 0:
+        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
+    g_t = _empty((t.num_ent, d), t.device)
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_kl_dist_bwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
+            None if lw is None else lw.data_ptr(), lse.data_ptr(), None if gr is None else gr.data_ptr(),
+            float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(), ws, wsb, st), "kge_kl_dist_bwd")
+    return g_a, g_p, g_t
+
+
+def bce_dist_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, chunk_cols: int = 0):
+    """bce_fwd for TransE / RotatE on float32 tables (kge_bce_dist_fwd): loss_rows [n], the sum over ALL entities of
+    BCEWithLogits(score + offset, multi-hot labels), no [n, E] matrix."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_dist_fwd")
+    loss_rows = _empty((n,), t.device)
+    if n == 0:
+        return loss_rows
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_bce_dist_fwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
+            loss_rows.data_ptr(), ws, wsb, st), "kge_bce_dist_fwd")
+    return loss_rows
+
+
+def bce_dist_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, g_rows=None,
+                 g_scalar: float = 1.0, chunk_cols: int = 0):
+    """Backward of bce_dist_fwd (kge_bce_dist_bwd): (g_a [n, d], g_p [n, d_r], g_entities [E, d])."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_dist_bwd")
+    d, dr = t.ent.shape[1], t.rel.shape[1]
+    gr = _ml_dist_rows(g_rows, n, t.device, "bce_dist_bwd", "g_rows")
+    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
+    if n == 0:
+        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
+    g_t = _empty((t.num_ent, d), t.device)
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_bce_dist_bwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
+            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(),
+            ws, wsb, st), "kge_bce_dist_bwd")
+    return g_a, g_p, g_t
+
+
 def ce_emb_fwd(t: Tables, direction: str, a_rows, p_rows, label):
     """ce_fwd with dense bf16 query rows against ALL rows of t.ent (the per-shard step of entity-sharded
     1vsAll training): (loss_rows [n] -- NaN where `label` (local row ids) is outside [0, num_ent) --, lse [n])."""

@@ -8,8 +8,9 @@ from kge.model.rotate import RotatE as _RefRotatE
 from kge.model.transe import TransE as _RefTransE
 
 from .. import engine
-from ..model import (BF16Shadow, _FusedCE, _FusedCEDist, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg,
-                     _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable)
+from ..model import (BF16Shadow, _FusedBCEDist, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedKLDist,
+                     _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
+                     bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable)
 
 
 class _HipScorer(RelationalScorer):
@@ -254,8 +255,15 @@ class _FusedScoring:
         return t if (t is not None and ent.is_cuda and engine.ce_supported(t)) else None
 
     # `hip_1vsAll.fused_dist_loss: true` (set by HipTrainingJob1vsAll; false by default): the 1vsAll loss of hip_transe /
-    # hip_rotate on float32 tables without an [n, E] matrix (kge_ce_dist_fwd / kge_ce_dist_bwd)
+    # hip_rotate on float32 tables without an [n, E] matrix (kge_ce_dist_fwd / kge_ce_dist_bwd).
+    # `hip_KvsAll.fused_dist_loss: true` (set by HipTrainingJobKvsAll): the same for the KvsAll kl and bce losses without
+    # label smoothing (kge_kl_dist_* / kge_bce_dist_*); also the bce loss under hip_1vsAll.
     _fused_dist_loss = False
+
+    def _ml_dist_tables(self, label_smoothing):
+        """_ce_dist_tables() for a multi-label loss, None under label smoothing (its uniform term is not linear in the
+        table for a distance scorer: the composed path)."""
+        return self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
 
     def _ce_dist_tables(self):
         """float32 tables for the distance scorers' fused loss, or None (the composed path): the option on, TransE /
@@ -333,7 +341,8 @@ class _FusedScoring:
         fused path does not apply (HipTrainingJobKvsAll; kge_kl_fwd / kge_kl_weighted_fwd)."""
         t = self._ce_tables()
         if t is None:
-            return None
+            td = self._ml_dist_tables(label_smoothing)
+            return None if td is None else _FusedKLDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, None, td)
         ent, rel = self._w()
         return kl_fused(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, lbl_rowptr, lbl_col,
                         float(label_smoothing), t)
@@ -342,7 +351,8 @@ class _FusedScoring:
                    label_smoothing: float = 0.0) -> Tensor:
         t = self._ce_tables()
         if t is None:
-            return None
+            td = self._ml_dist_tables(label_smoothing)
+            return None if td is None else _FusedKLDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, None, td)
         ent, rel = self._w()
         return kl_fused(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, lbl_rowptr, lbl_col,
                         float(label_smoothing), t)
@@ -353,7 +363,8 @@ class _FusedScoring:
         None if the fused path does not apply (kge_bce_fwd)."""
         t = self._ce_tables()
         if t is None:
-            return None
+            td = self._ml_dist_tables(label_smoothing)
+            return None if td is None else _FusedBCEDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, float(offset), td)
         ent, rel = self._w()
         return bce_fused(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, lbl_rowptr, lbl_col,
                          float(offset), float(label_smoothing), t)
@@ -362,7 +373,8 @@ class _FusedScoring:
                     label_smoothing: float = 0.0):
         t = self._ce_tables()
         if t is None:
-            return None
+            td = self._ml_dist_tables(label_smoothing)
+            return None if td is None else _FusedBCEDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, float(offset), td)
         ent, rel = self._w()
         return bce_fused(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, lbl_rowptr, lbl_col,
                          float(offset), float(label_smoothing), t)

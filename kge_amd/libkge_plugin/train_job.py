@@ -34,9 +34,34 @@ def _model_takes_fused_loss(model, with_dropout: bool = False) -> bool:
 def _model_takes_dist_loss(model) -> bool:
     """The fused 1vsAll loss of the distance scorers (hip_transe / hip_rotate, `hip_1vsAll.fused_dist_loss: true`):
     decided once per subbatch like _model_takes_fused_loss.  The two one-sided calls loss_sp / loss_po; no captured
-    step, no two-sided launch."""
+    step, no two-sided launch.  The same question for `hip_KvsAll.fused_dist_loss` (kl_loss_* / bce_loss_* per query
+    type; the job adds `label_smoothing == 0`)."""
     f = getattr(model, "_ce_dist_tables", None)
     return f is not None and f() is not None
+
+
+def _set_fused_dist_loss(job, key):
+    """`<key>.fused_dist_loss` (false by default): the models learn it here and decide per subbatch
+    (_FusedScoring._ce_dist_tables); under hip_reciprocal_relations_model the base model is the one that scores."""
+    try:
+        fused_dist = bool(job.config.get_default(key + ".fused_dist_loss"))
+    except KeyError:
+        fused_dist = False
+    for m in (job.model, getattr(job.model, "_base_model", None)):
+        if m is not None and hasattr(type(m), "_fused_dist_loss"):
+            m._fused_dist_loss = fused_dist
+
+
+def _has_repeated_labels(coords) -> bool:
+    """Does a batch's `label_coords` ([nnz, 2]: batch row, label) hold the same (row, label) twice?  A training split
+    that repeats a triple does that: the reference's dense label row then carries a 2, while kge_kl_dist_* /
+    kge_bce_dist_* take ids that are unique per row (the forward would count the id twice, the backward's bit mask
+    once).  One sort of nnz keys and one host read per subbatch, on the fused_dist_loss path only."""
+    if coords.shape[0] < 2:
+        return False
+    c = coords.long()
+    key, _ = torch.sort(c[:, 0] * (c[:, 1].max() + 1) + c[:, 1])
+    return bool((key[1:] == key[:-1]).any())
 
 
 def _declined_late(what):
@@ -189,15 +214,7 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
         self._graph_step = None       # kge_amd.train_graph.GraphedStep, built at the first batch that qualifies
         self._graph_step_ok = None    # decided at the first batch (None: not yet)
         self._skip_optimizer_step = False
-        # hip_1vsAll.fused_dist_loss (false by default): the models learn it here and decide per subbatch
-        # (_FusedScoring._ce_dist_tables); under hip_reciprocal_relations_model the base model is the one that scores
-        try:
-            fused_dist = bool(config.get_default("hip_1vsAll.fused_dist_loss"))
-        except KeyError:
-            fused_dist = False
-        for m in (self.model, getattr(self.model, "_base_model", None)):
-            if m is not None and hasattr(type(m), "_fused_dist_loss"):
-                m._fused_dist_loss = fused_dist
+        _set_fused_dist_loss(self, "hip_1vsAll")
         if self.__class__ == HipTrainingJob1vsAll:
             for f in Job.job_created_hooks:
                 f(self)
@@ -254,12 +271,14 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
     def _process_subbatch(self, batch_index, batch, subbatch_slice, result):
         kl = isinstance(self.loss, KLDivWithSoftmaxKgeLoss) and hasattr(self.model, "loss_sp")
         takes = _model_takes_fused_loss(self.model, with_dropout=kl)
-        dist = kl and not takes and _model_takes_dist_loss(self.model)  # hip_1vsAll.fused_dist_loss: loss_sp, then loss_po
+        offset = _plain_bce(self.loss)
+        bce = offset is not None and hasattr(self.model, "bce_loss_sp")
+        # hip_1vsAll.fused_dist_loss: loss_sp, then loss_po (kl); bce_loss_sp, then bce_loss_po (bce)
+        dist = (kl or bce) and not takes and _model_takes_dist_loss(self.model)
         if not takes and not dist:
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)
-        offset = _plain_bce(self.loss)
-        if offset is not None and hasattr(self.model, "bce_loss_sp"):
-            if not _model_takes_fused_loss(self.model):  # (the bce loss has no dropout form)
+        if bce:
+            if not dist and not _model_takes_fused_loss(self.model):  # (the bce loss has no dropout form)
                 return super()._process_subbatch(batch_index, batch, subbatch_slice, result)
             return self._process_subbatch_bce(batch_index, batch, subbatch_slice, result, offset)
         fused = kl
@@ -322,7 +341,9 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
     that offers `kl_loss_sp` / `kl_loss_po` (`bce_loss_sp` / `bce_loss_po`), the sp_ and _po queries of a
     subbatch get their loss from one fused kernel each (kge_kl_fwd / kge_kl_weighted_fwd /
     kge_bce_fwd: scores never written; labels as a CSR cut out of the batch's `label_coords`); s_o
-    queries and every other configuration run the reference's code."""
+    queries and every other configuration run the reference's code.  `hip_KvsAll.fused_dist_loss: true`: hip_transe /
+    hip_rotate on float32 tables take the same hooks without label smoothing (kge_kl_dist_* / kge_bce_dist_*), one call
+    per query type, no captured step."""
 
     def __init__(self, config, dataset, parent_job=None, model=None, forward_only=False):
         super().__init__(config, dataset, parent_job, model=model, forward_only=forward_only)
@@ -332,6 +353,7 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         self._graph_overflows = 0     # batches in a row that did not fit the capacities
         self.graph_batches = 0        # batches that went through the GraphedStep (replayed or eager)
         self._skip_optimizer_step = False
+        _set_fused_dist_loss(self, "hip_KvsAll")
         if self.__class__ == HipTrainingJobKvsAll:
             for f in Job.job_created_hooks:
                 f(self)
@@ -421,7 +443,13 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         return _plain_bce(self.loss) is not None and hasattr(self.model, "bce_loss_sp")
 
     def _process_subbatch(self, batch_index, batch, subbatch_slice, result):
-        if not self._fused_ok() or not _model_takes_fused_loss(self.model):
+        takes = _model_takes_fused_loss(self.model)
+        # hip_KvsAll.fused_dist_loss (hip_transe / hip_rotate, no label smoothing): decided once, here; the per-type loop
+        # only -- no captured step, no multilabel_loss_sp_po
+        dist = not takes and float(self.label_smoothing) == 0.0 and _model_takes_dist_loss(self.model)
+        # (a batch with a repeated (query, label) pair -- a split that repeats a triple -- takes the composed path)
+        dist = dist and self._fused_ok() and not _has_repeated_labels(batch["label_coords"])
+        if not self._fused_ok() or not (takes or dist):
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)
         batch_size = result.size
         result.prepare_time -= time.time()
@@ -470,7 +498,8 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         # both query types of the subbatch: their loss rows with ONE backward (two d loss / d score passes, the gradient
         # products once over all rows, no index_add / accumulation passes of autograd in between); the reference
         # back-propagates the two losses one after the other -- the same gradients, accumulated
-        if ls == 0.0 and len(per_type) >= 1 and hasattr(self.model, "multilabel_loss_sp_po") and "s_o" not in self.query_types:
+        if (not dist and ls == 0.0 and len(per_type) >= 1 and hasattr(self.model, "multilabel_loss_sp_po")
+                and "s_o" not in self.query_types):
             gs = self._graph_step_for(batch_index, batch, subbatch_slice, per_type, totals)
             if gs is not None and gs.enabled:
                 result.prepare_time -= time.time()
@@ -487,7 +516,7 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
                     result.avg_loss += loss_value.item()
                     result.forward_time += time.time()
                     return
-        if ls == 0.0 and len(per_type) == 2 and hasattr(self.model, "multilabel_loss_sp_po"):
+        if not dist and ls == 0.0 and len(per_type) == 2 and hasattr(self.model, "multilabel_loss_sp_po"):
             result.forward_time -= time.time()
             (s_, p_sp, rp_sp, cl_sp), (p_po, o_, rp_po, cl_po) = per_type["sp_"], per_type["_po"]
             # (averaged over the batch, not the subbatch)

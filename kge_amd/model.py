@@ -115,7 +115,8 @@ class KgeModel(torch.nn.Module):
                  score_dtype=None, fused_dist_loss: bool = False):
         super().__init__()
         # fused_dist_loss=True (TransE / RotatE, float32 parameters on a GPU, l_norm 1 or 2): loss_sp / loss_po /
-        # loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_dist_fwd / _bwd); off by default
+        # loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_dist_fwd / _bwd), and kl_loss_sp / kl_loss_po /
+        # bce_loss_sp / bce_loss_po without label smoothing (kge_kl_dist_* / kge_bce_dist_*); off by default
         self.fused_dist_loss = bool(fused_dist_loss)
         # score_dtype=torch.bfloat16 with f32 parameters (ComplEx / DistMult): sp_/_po scores from
         # the bf16 matrix-core kernel on bf16 copies of the tables, gradients w.r.t. the f32 masters
@@ -317,6 +318,10 @@ class KgeModel(torch.nn.Module):
         t = self._ce_tables()
         if t is not None:
             return self._kl_fused("sp", s, p, lbl_rowptr, lbl_col, float(label_smoothing), t)
+        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
+        if td is not None:
+            return _FusedKLDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p,
+                                      lbl_rowptr, lbl_col, None, td)
         return self._kl_composed(self.score_sp(s, p), lbl_rowptr, lbl_col, label_smoothing)
 
     def kl_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
@@ -324,6 +329,10 @@ class KgeModel(torch.nn.Module):
         t = self._ce_tables()
         if t is not None:
             return self._kl_fused("po", o, p, lbl_rowptr, lbl_col, float(label_smoothing), t)
+        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
+        if td is not None:
+            return _FusedKLDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p,
+                                      lbl_rowptr, lbl_col, None, td)
         return self._kl_composed(self.score_po(p, o), lbl_rowptr, lbl_col, label_smoothing)
 
     def multilabel_loss_sp_po(self, kind: str, s: Tensor, p_sp: Tensor, rowptr_sp: Tensor, col_sp: Tensor, o: Tensor,
@@ -367,6 +376,10 @@ class KgeModel(torch.nn.Module):
             return bce_fused(self._scorer.name, self._scorer._norm, "sp", self._entity_embedder.weight,
                              self._relation_embedder.weight, s, p, lbl_rowptr, lbl_col, float(offset),
                              float(label_smoothing), t)
+        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
+        if td is not None:
+            return _FusedBCEDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p,
+                                       lbl_rowptr, lbl_col, float(offset), td)
         return self._bce_composed(self.score_sp(s, p), lbl_rowptr, lbl_col, offset, label_smoothing)
 
     def bce_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor, offset: float = 0.0,
@@ -376,6 +389,10 @@ class KgeModel(torch.nn.Module):
             return bce_fused(self._scorer.name, self._scorer._norm, "po", self._entity_embedder.weight,
                              self._relation_embedder.weight, o, p, lbl_rowptr, lbl_col, float(offset),
                              float(label_smoothing), t)
+        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
+        if td is not None:
+            return _FusedBCEDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p,
+                                       lbl_rowptr, lbl_col, float(offset), td)
         return self._bce_composed(self.score_po(p, o), lbl_rowptr, lbl_col, offset, label_smoothing)
 
     def score_so(self, s: Tensor, o: Tensor, p: Tensor = None) -> Tensor:
@@ -679,6 +696,52 @@ class _FusedCEDist(torch.autograd.Function):
         _scatter_rows(gr, p, g_p)
         _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
         return None, ge, gr, None, None, None, None, None
+
+
+class _FusedKLDist(torch.autograd.Function):
+    """_FusedKL for TransE / RotatE on float32 tables (kge_kl_dist_fwd / kge_kl_dist_bwd): `tables` are the parameters
+    themselves, labels an int64 CSR (rowptr [n + 1], col [nnz]; ids in any order); no label-smoothing bias.  The
+    backward walks the entity columns in chunks of `chunk_cols` (0: the library's default)."""
+
+    @staticmethod
+    def forward(ctx, direction, ent, rel, a, p, rowptr, col, label_weight, tables, chunk_cols=0):
+        loss_rows, lse = engine.kl_dist_fwd(tables, direction, a, p, rowptr, col, label_weight, chunk_cols)
+        ctx.t, ctx.direction, ctx.idx, ctx.chunk_cols = tables, direction, (a, p, rowptr, col, label_weight), chunk_cols
+        ctx.rel_shape = rel.shape
+        ctx.save_for_backward(lse)
+        return loss_rows
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        a, p, rowptr, col, label_weight = ctx.idx
+        (lse,) = ctx.saved_tensors
+        g_a, g_p, ge = engine.kl_dist_bwd(ctx.t, ctx.direction, a, p, rowptr, col, lse, g_rows=g_rows.contiguous(),
+                                          label_weight=label_weight, chunk_cols=ctx.chunk_cols)
+        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
+        _scatter_rows(gr, p, g_p)
+        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
+        return None, ge, gr, None, None, None, None, None, None, None
+
+
+class _FusedBCEDist(torch.autograd.Function):
+    """_FusedBCE for TransE / RotatE on float32 tables (kge_bce_dist_fwd / kge_bce_dist_bwd)."""
+
+    @staticmethod
+    def forward(ctx, direction, ent, rel, a, p, rowptr, col, offset, tables, chunk_cols=0):
+        loss_rows = engine.bce_dist_fwd(tables, direction, a, p, rowptr, col, offset, chunk_cols)
+        ctx.t, ctx.direction, ctx.idx, ctx.offset, ctx.chunk_cols = tables, direction, (a, p, rowptr, col), offset, chunk_cols
+        ctx.rel_shape = rel.shape
+        return loss_rows
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        a, p, rowptr, col = ctx.idx
+        g_a, g_p, ge = engine.bce_dist_bwd(ctx.t, ctx.direction, a, p, rowptr, col, ctx.offset,
+                                           g_rows=g_rows.contiguous(), chunk_cols=ctx.chunk_cols)
+        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
+        _scatter_rows(gr, p, g_p)
+        _scatter_rows(ge, a, g_a)
+        return None, ge, gr, None, None, None, None, None, None, None
 
 
 class _FusedCE2(torch.autograd.Function):
