@@ -585,6 +585,41 @@ int kge_ce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_
                     float* g_p, float* g_tgt, void* workspace, int64_t workspace_bytes,
                     void* stream);
 
+/* ---- the same loss for ComplEx / DistMult on FLOAT32 tables -------------------- */
+/* kge_ce_f32_fwd / kge_ce_f32_bwd: loss_rows, lse and the gradients exactly as kge_ce_fwd / kge_ce_bwd define them, for
+ * ComplEx and DistMult (complex.py:30-39, distmult.py:15-21) on float32 tables -- the reference's own precision: the
+ * step of TrainingJob1vsAll (kge/job/train_1vsAll.py:64-81) with KLDivWithSoftmaxKgeLoss on index labels
+ * (kge/util/loss.py:192-207) without an [n, num_ent] matrix.  The forward is the exact f32 matrix-core scoring kernel
+ * with a fold epilogue: every score inside is bit-identical to kge_score_sp / kge_score_po on the same tables, one
+ * (max, sum exp, label score) record per row and column group is merged in a fixed order (no atomics: the same bits
+ * on every run).  The backward walks the entity columns in chunks: per chunk the scoring kernel writes
+ * d loss / d score [n, chunk] into the workspace, and the two f32 matrix-core products of kge_score_pairs_bwd turn
+ * it into the chunk's rows of g_tgt (OVERWRITTEN: bit-equal whatever the chunk width) and a further addend of the
+ * query-side gradient, summed in chunk order, then split-K order (no float atomics).
+ *   g_rows, g_scalar, g_a [n, dim], g_p [n, rel_dim], g_tgt [num_ent, dim]: as for kge_ce_bwd (f32, OVERWRITTEN).
+ *   A label outside [0, num_ent) gives loss_rows[i] = NaN.
+ * kge_ce_f32_workspace_bytes(t, n, chunk_cols) (train_1vsAll.py:64-81, loss.py:192-207): chunk_cols = columns per
+ * chunk of the backward, a multiple of 128 (>= 128), or 0 = the library's default (a gradient chunk of at most 32 MB,
+ * at least 128 columns, clamped to num_ent rounded up to 128); returns more than 0 only for ComplEx / DistMult,
+ * KGE_F32 tables, dim % 8 == 0, rel_dim == dim and 16-byte aligned rows (base pointers and row pitches).  The
+ * workspace holds the forward's records (12 bytes per row and column group, at most 256 groups), two [n, dim]
+ * buffers, at most 8 MB of split-K partials and the [n, chunk] gradient block: 256-byte aligned device scratch, no
+ * initialisation, stream-ordered use, not shared by concurrent calls.  The backward derives its chunk width from
+ * `workspace_bytes` (any size from chunk_cols = 128 up is valid; below that, and for the forward below its records,
+ * KGE_ERR_WORKSPACE).
+ * kge_ce_f32_fwd (train_1vsAll.py:64-81, loss.py:192-207: the two loss values of a batch) and
+ * kge_ce_f32_bwd (train_1vsAll.py:64-81, loss.py:192-207 under loss_value.backward(): their gradients):
+ * other scorers, bf16 tables or another layout: KGE_ERR_UNSUPPORTED, nothing is launched.  No allocation, no host
+ * wait, no library call: both are stream-ordered and capturable into a hipGraph. */
+int64_t kge_ce_f32_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols);
+int kge_ce_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label,
+                   int64_t n, float* loss_rows, float* lse, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+int kge_ce_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label,
+                   int64_t n, const float* lse, const float* g_rows, float g_scalar, float* g_a,
+                   float* g_p, float* g_tgt, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+
 /* The same pair with DENSE query rows (a_rows [n, dim], p_rows [n, rel_dim], row-major, bf16) scored
  * against ALL rows of t->ent: the per-shard step of entity-sharded 1vsAll training:
  * the query rows of a batch come out of the exchange between the shards, t->ent is this rank's shard,

@@ -189,6 +189,11 @@ PROTOTYPES = {
                                        c_i64, c_vp]),
     "kge_ce_dist_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_vp,
                                        ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "kge_ce_f32_workspace_bytes": (c_i64, [_PT, c_i64, c_i64]),
+    "kge_ce_f32_fwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, c_vp,
+                                      c_i64, c_vp]),
+    "kge_ce_f32_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_vp,
+                                      ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "kge_multilabel_dist_workspace_bytes": (c_i64, [_PT, c_i64, c_i64]),
     "kge_kl_dist_fwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_i64, c_vp]),

@@ -25,6 +25,14 @@ int run_pairs_exact(int scorer, int dtype, bool use_mfma, const Operand& A, cons
                     float lp, float* out, long long ldo, hipStream_t st, bool round_query = true,
                     const RankArgs* rk = nullptr);
 long long ce_dist_records_bytes(long long n, long long m);
+long long ce_f32_workspace_bytes(long long n, long long m, int d, long long chunk_cols);
+bool ce_f32_layout_ok(int d, const Operand& A, const Operand& R, const Operand& TG);
+int run_ce_f32_fwd(int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n,
+                   long long m, const Index& label, float* loss_rows, float* lse, void* ws, long long ws_bytes,
+                   hipStream_t st);
+int run_ce_f32_bwd(int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n,
+                   long long m, const Index& label, const float* lse, const float* g_rows, float g_scalar, float* g_a,
+                   float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st);
 long long ce_dist_workspace_bytes(long long n, long long m, int d, long long chunk_cols);
 int run_ce_dist_fwd(int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
                     long long n, long long m, const Index& label, float* loss_rows, float* lse, void* ws,
@@ -1617,6 +1625,60 @@ int kge_ce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_
   return run_ce_dist_bwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, make_index(label), lse, g_rows, g_scalar, g_a, g_p, g_tgt,
                          workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- the same loss for ComplEx / DistMult on FLOAT32 tables (ce_f32.hip): train_1vsAll.py:64-81, loss.py:192-207,
+// complex.py:30-39, distmult.py:15-21 ------------------------------------------------------------------------------
+namespace {
+// what run_pairs_f32 accepts: the layout every gathered row shares with the table it comes from
+bool ce_f32_tables_ok(const kge_tables* t) {
+  if (t->scorer != KGE_COMPLEX && t->scorer != KGE_DISTMULT) return false;
+  if (t->dtype != KGE_F32 || t->rel_dim != t->dim) return false;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return ce_f32_layout_ok((int)t->dim, ent_op(t, all), rel_op(t, all), ent_op(t, all));
+}
+int ce_f32_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, const kge_index& label,
+                 int64_t n) {
+  int rc = check_tables(t, true);
+  if (rc) return rc;
+  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
+  if (n < 0) return KGE_ERR_INVALID_ARG;
+  if (!ce_f32_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
+  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n)) || (rc = check_index(label, false, n)))
+    return rc;
+  return KGE_OK;
+}
+}  // namespace
+
+int64_t kge_ce_f32_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
+  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_f32_tables_ok(t)) return 0;
+  if (chunk_cols < 0 || chunk_cols % 128) return 0;
+  return ce_f32_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+}
+
+int kge_ce_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label, int64_t n,
+                   float* loss_rows, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ce_f32_check(t, dir, a, p, label, n);
+  if (rc) return rc;
+  if (n == 0) return KGE_OK;
+  if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ce_f32_fwd(t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+                        make_index(label), loss_rows, lse, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int kge_ce_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label, int64_t n,
+                   const float* lse, const float* g_rows, float g_scalar, float* g_a, float* g_p, float* g_tgt,
+                   void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ce_f32_check(t, dir, a, p, label, n);
+  if (rc) return rc;
+  if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ce_f32_bwd(t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+                        make_index(label), lse, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
+                        (hipStream_t)stream);
 }
 
 // ---- the KvsAll losses of the distance scorers on float32 tables (ce_dist.hip, the folds FOLD_KL = 1 / FOLD_BCE = 2):

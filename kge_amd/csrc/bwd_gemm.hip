@@ -27,7 +27,7 @@ bool run_gemm16_dt(int d, long long rows, long long m, const unsigned short* Q16
 // bwd_gemm32.hip: C[M, N] = A * B on the f32 matrix cores (float32 operands, or bf16 widened)
 bool run_gemm32(bool a_kcont, int in16, long long M, long long N, long long K, const void* A, long long lda,
                 const void* B, long long ldb, float* C, long long ldc, float* scratch, size_t scratch_bytes,
-                hipStream_t st);
+                hipStream_t st, int* parts = nullptr);
 
 // Q[i, :] = q(a_i, r_i), f32, ld = d.  One thread per (row, coordinate of the first half).
 template <int SCORER>
@@ -117,12 +117,38 @@ __global__ __launch_bounds__(256) void bwdg_reduce_kernel(const float* __restric
   *reinterpret_cast<f32x4*>(out + i) = acc;
 }
 
+// The two elementwise kernels on their own (bwdg_run below; ce_f32.hip, which runs them around its chunk loop).
+// Q [n, d] = the query vectors; g_a holds dQ on entry, g_a / g_p the row gradients on return.
+int run_bwdg_build_q(int scorer, const Operand& A, const Operand& R, int dir, int d, long long n, float* Q,
+                     hipStream_t st) {
+  const int half = scorer == KGE_COMPLEX ? d / 2 : d;
+  const dim3 grid((unsigned)((n * half + 255) / 256));
+  if (scorer == KGE_COMPLEX)
+    hipLaunchKernelGGL((bwdg_build_q_kernel<KGE_COMPLEX>), grid, dim3(256), 0, st, A, R, dir, d, n, Q);
+  else if (scorer == KGE_DISTMULT)
+    hipLaunchKernelGGL((bwdg_build_q_kernel<KGE_DISTMULT>), grid, dim3(256), 0, st, A, R, dir, d, n, Q);
+  else
+    return KGE_ERR_UNSUPPORTED;
+  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+}
+
+int run_bwdg_chain(int scorer, const Operand& A, const Operand& R, int dir, int d, long long n, float* g_a, float* g_p,
+                   hipStream_t st) {
+  const int half = scorer == KGE_COMPLEX ? d / 2 : d;
+  const dim3 grid((unsigned)((n * half + 255) / 256));
+  if (scorer == KGE_COMPLEX)
+    hipLaunchKernelGGL((bwdg_chain_kernel<KGE_COMPLEX>), grid, dim3(256), 0, st, A, R, dir, d, n, g_a, g_p);
+  else if (scorer == KGE_DISTMULT)
+    hipLaunchKernelGGL((bwdg_chain_kernel<KGE_DISTMULT>), grid, dim3(256), 0, st, A, R, dir, d, n, g_a, g_p);
+  else
+    return KGE_ERR_UNSUPPORTED;
+  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+}
+
 template <int SCORER>
 static int bwdg_run(int dir, const Operand& A, const Operand& R, const Operand& TG, int d,
                     long long n, long long m, const float* gout, long long ldg, float* g_a,
                     float* g_p, float* g_tgt, hipStream_t st) {
-  const int half = SCORER == KGE_COMPLEX ? d / 2 : d;
-  const unsigned qblocks = (unsigned)((n * half + 255) / 256);
   // target rows as a dense [m, d] matrix: the table itself, or gathered into g_tgt for now
   const float* T = (const float*)TG.base;
   long long ldt = TG.ld;
@@ -138,10 +164,10 @@ static int bwdg_run(int dir, const Operand& A, const Operand& R, const Operand& 
   const size_t ws_bytes = TG.idx.ptr == nullptr ? (size_t)m * d * sizeof(float) : 0;
   if (!run_gemm32(true, 0, n, d, m, gout, ldg, T, ldt, g_a, d, ws, ws_bytes, st)) return KGE_ERR_UNSUPPORTED;
   // Q -> g_p, then dT = G^T * Q  ([m, d]; K = n)
-  hipLaunchKernelGGL((bwdg_build_q_kernel<SCORER>), dim3(qblocks), dim3(256), 0, st, A, R, dir, d, n, g_p);
+  int rc = run_bwdg_build_q(SCORER, A, R, dir, d, n, g_p, st);
+  if (rc != KGE_OK) return rc;
   if (!run_gemm32(false, 0, m, d, n, gout, ldg, g_p, d, g_tgt, d, nullptr, 0, st)) return KGE_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((bwdg_chain_kernel<SCORER>), dim3(qblocks), dim3(256), 0, st, A, R, dir, d, n, g_a, g_p);
-  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+  return run_bwdg_chain(SCORER, A, R, dir, d, n, g_a, g_p, st);
 }
 
 // ---- bf16 tables (mixed-precision training): the same two products on the bf16 matrix cores.

@@ -179,9 +179,17 @@ __global__ __launch_bounds__(2 * BM) void gemm32_kernel(const T* __restrict__ A,
 
 // C[M, N] (row-major, ldc) = A * B (see the top).  in16: bf16 operands (widened: the products are exact).  Split-K
 // needs `scratch` (P * M * N floats) and ldc == N; without it the reduction runs in one workgroup per tile.
+// parts != NULL (ce_f32.hip: dQ accumulated over column chunks): the P >= 1 partial outputs [P][M * N] are LEFT in
+// `scratch` for the caller to sum in its own fixed order, *parts = P and C is not touched; needs scratch for one
+// partial at least and (M * N) % 4 == 0.
 bool run_gemm32(bool a_kcont, int in16, long long M, long long N, long long K, const void* A, long long lda,
                 const void* B, long long ldb, float* C, long long ldc, float* scratch, size_t scratch_bytes,
-                hipStream_t st) {
+                hipStream_t st, int* parts) {
+  if (parts != nullptr) {
+    *parts = 0;
+    if (M <= 0 || N <= 0 || scratch == nullptr || (M * N) % 4 || scratch_bytes < (size_t)M * N * 4) return false;
+    ldc = N;
+  }
   if (M <= 0 || N <= 0) return true;
   if (M >= (1LL << 37) || N >= (1LL << 22)) return false;
   // 256-row tiles (eight waves) whenever the output has that many rows: at a tile count near the number of compute
@@ -204,7 +212,7 @@ bool run_gemm32(bool a_kcont, int in16, long long M, long long N, long long K, c
       P = (K + kc - 1) / kc;
     }
   }
-  float* out = P > 1 ? scratch : C;
+  float* out = (P > 1 || parts != nullptr) ? scratch : C;
   const long long oldc = P > 1 ? N : ldc;
   dim3 grid((unsigned)tn, (unsigned)tm, (unsigned)P);
 #define KGE_G32(TT, KC_, BM_)                                                                                      \
@@ -221,7 +229,9 @@ bool run_gemm32(bool a_kcont, int in16, long long M, long long N, long long K, c
   }
 #undef KGE_G32B
 #undef KGE_G32
-  if (P > 1) {
+  if (parts != nullptr) {
+    *parts = (int)P;
+  } else if (P > 1) {
     const long long cnt = M * N;
     hipLaunchKernelGGL(bwdg_reduce_kernel, dim3((unsigned)((cnt / 4 + 255) / 256)), dim3(256), 0, st, scratch, cnt,
                        (int)P, C, (float*)nullptr, 0LL);

@@ -477,6 +477,18 @@ struct RankArgs {
   int col_tiles;                      // column tiles a workgroup walks (its counts leave it once)
 };
 
+// ---- loss epilogues of pairs_f32_kernel (score_pairs_f32.hip, driven by ce_f32.hip): kge_ce_f32_fwd / kge_ce_f32_bwd
+struct F32LossArgs {
+  Index label;          // [n] entity id of row i's true target
+  float* rec;           // fold: records [n][groups][3] = max, sum exp(score - max), label score (ce_dist.hip's layout)
+  int groups;           // fold: column groups per row = gridDim.x
+  int col_tiles;        // fold: column tiles a workgroup walks (one record per row leaves it)
+  const float* lse;     // gradient: log-sum-exp of row i (the forward's)
+  const float* g_rows;  // gradient: upstream gradient per row, or NULL: g_scalar
+  float g_scalar;
+  long long col_lo;     // gradient: entity id of the chunk's column 0
+};
+
 // A finished ROWS x COLS score tile sits in LDS (`tile`, row pitch LDT floats).  256 threads: thread t takes the W =
 // COLS * ROWS / 256 columns [seg * W, ...) of tile row t / SEGS -- W in {16, 64} divides 64 and the tile's first
 // column is a multiple of COLS, so the thread's columns lie inside ONE 64-bit filter word per filter set -- and

@@ -25,20 +25,36 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // RANK: the finished tile is not stored but counted against the rows' true scores (rank_tile_rows, common.hpp):
 // the accumulators go through the operand buffers (free behind the last chunk: 128 x 132 floats, exactly their
 // size) so that a thread sees 64 consecutive columns of ONE row = one filter word per filter set.
-template <int SCORER, typename T, bool RANK>
+//
+// F3_CE (kge_ce_f32_fwd): the same walk, and the tile is folded into a per-thread running (max, sum exp) of ONE row --
+// two threads per row, 64 columns each, 16 at a time -- with the label's score kept where its column passes; at the end
+// the row's two threads are merged in lane order and one (max, sum, label score) record per (row, blockIdx.x) leaves
+// the workgroup (ce_dist.hip's record layout, merged by ce_dist_merge_kernel).  Padding columns (>= m) take no part.
+// F3_GRAD (kge_ce_f32_bwd): one tile per workgroup; out[i, j] = g_i (exp(S_ij - lse_i) - [col_lo + j == label_i]) in
+// whole 16-byte pieces, 0 in the padding columns of the tile (`out` has them: its pitch is a multiple of 128).
+enum { F3_STORE = 0, F3_RANK = 1, F3_CE = 2, F3_GRAD = 3 };
+
+template <int SCORER, typename T, int MODE>
 __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Operand TG, int dir, int d,
                                                         long long n, long long m, int round_q,
-                                                        float* __restrict__ out, long long ldo, RankArgs rk) {
+                                                        float* __restrict__ out, long long ldo, RankArgs rk,
+                                                        F32LossArgs ce) {
+  constexpr bool RANK = MODE == F3_RANK;
   // [buffer][q|t][half][pair][row]
   __shared__ __attribute__((aligned(16))) float lds[2][2][2][F3_KC][F3_LD];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // RANK: this workgroup walks CT consecutive column tiles of its 128 rows and keeps the counts in registers
-  const int CT = RANK ? rk.col_tiles : 1;
+  const int CT = RANK ? rk.col_tiles : MODE == F3_CE ? ce.col_tiles : 1;
   const long long row0 = (long long)blockIdx.y * F3_BM;
   const int hh = d / 2;
   const int nchunk = (hh + F3_KC - 1) / F3_KC;
   RankAcc racc{};
+  // F3_CE: row fr of the tile, columns 64 * fseg .. + 63; the running fold of that row over the tiles walked
+  const int fr = tid >> 1, fseg = tid & 1;
+  float run_m = -__builtin_inff(), run_s = 0.0f, lbl_score = 0.0f;
+  long long lbl = -1;
+  if constexpr (MODE == F3_CE) lbl = index_at(ce.label, row0 + fr >= n ? n - 1 : row0 + fr);
   for (int ct = 0; ct < CT; ++ct) {
   const long long col0 = ((long long)blockIdx.x * CT + ct) * F3_BN;
   if (col0 >= m) break;
@@ -161,7 +177,7 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
   }
 
   // D[i][j]: lane holds column j = lane & 31, rows (r & 3) + 8 (r >> 2) + 4 mh
-  if constexpr (RANK) {
+  if constexpr (MODE != F3_STORE) {
     static_assert(sizeof(lds) >= F3_BM * F3_LD * 4, "the score tile fits the operand buffers");
     float* const tile = &lds[0][0][0][0][0];  // [128][F3_LD]; the loop ended with a barrier
 #pragma unroll
@@ -176,7 +192,62 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
         }
       }
     __syncthreads();
-    rank_acc_add<F3_BM, F3_BN, F3_LD>(racc, tile, row0, col0, n, m, rk, tid);
+    if constexpr (RANK) rank_acc_add<F3_BM, F3_BN, F3_LD>(racc, tile, row0, col0, n, m, rk, tid);
+    if constexpr (MODE == F3_CE) {
+      // 16 columns at a time; a thread that has seen only padding keeps (-inf, 0), which the merges skip
+#pragma unroll 1
+      for (int q16 = 0; q16 < 4; ++q16) {
+        const long long cbase = col0 + fseg * 64 + q16 * 16;
+        long long valid = m - cbase;
+        if (valid > 16) valid = 16;
+        if (valid <= 0) break;
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 x = *reinterpret_cast<const f32x4*>(&tile[fr * F3_LD + fseg * 64 + q16 * 16 + q * 4]);
+          v[q * 4 + 0] = x[0]; v[q * 4 + 1] = x[1]; v[q * 4 + 2] = x[2]; v[q * 4 + 3] = x[3];
+        }
+        float tm = v[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k)
+          if (k < valid) tm = __builtin_fmaxf(tm, v[k]);
+        const float nm = __builtin_fmaxf(run_m, tm);
+        float s = run_s * expf(run_m - nm);  // (first columns: 0 * exp(-inf) = 0)
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+          if (k < valid) s += expf(v[k] - nm);
+        run_m = nm;
+        run_s = s;
+        const long long off = lbl - cbase;
+        if (off >= 0 && off < valid) {
+#pragma unroll
+          for (int k = 0; k < 16; ++k)
+            if (k == (int)off) lbl_score = v[k];
+        }
+      }
+    }
+    if constexpr (MODE == F3_GRAD) {
+      // thread t: tile rows (t >> 5) + 8 k, columns 4 (t & 31) .. + 3: a wave stores two whole 512-byte row pieces
+      const int gc = (tid & 31) * 4;
+#pragma unroll 4
+      for (int k = 0; k < 16; ++k) {
+        const int lr = (tid >> 5) + 8 * k;
+        const long long orow = row0 + lr;
+        if (orow >= n) break;  // (rows ascend with k)
+        const float gi = ce.g_rows != nullptr ? ce.g_rows[orow] : ce.g_scalar;
+        const float l = ce.lse[orow];
+        const long long lb = index_at(ce.label, orow) - ce.col_lo - col0 - gc;
+        const f32x4 x = *reinterpret_cast<const f32x4*>(&tile[lr * F3_LD + gc]);
+        f32x4 g;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float w = expf(x[e] - l);
+          if (lb == e) w -= 1.0f;
+          g[e] = col0 + gc + e < m ? gi * w : 0.0f;
+        }
+        *reinterpret_cast<f32x4*>(out + orow * ldo + col0 + gc) = g;
+      }
+    }
     continue;
   }
 #pragma unroll
@@ -192,6 +263,28 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
     }
   }  // column tiles
   if constexpr (RANK) rank_acc_flush<F3_BM>(racc, row0, n, rk, tid);
+  if constexpr (MODE == F3_CE) {
+    // merge the row's two threads (neighbouring lanes) in lane order
+    float pm[2], ps[2], pl[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int src = (lane & ~1) | k;
+      pm[k] = __shfl(run_m, src, 64);
+      ps[k] = __shfl(run_s, src, 64);
+      pl[k] = __shfl(lbl_score, src, 64);
+    }
+    if (fseg == 0 && row0 + fr < n) {
+      const float mm = __builtin_fmaxf(pm[0], pm[1]);
+      float ss = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        if (ps[k] > 0.0f) ss += ps[k] * expf(pm[k] - mm);
+      float* o = ce.rec + ((row0 + fr) * ce.groups + blockIdx.x) * 3;
+      o[0] = mm;
+      o[1] = ss;
+      o[2] = pl[0] + pl[1];  // (at most one of the two is not zero)
+    }
+  }
 }
 
 template <int SCORER, typename T>
@@ -206,11 +299,11 @@ static int launch_pairs_f32(const Operand& A, const Operand& R, const Operand& T
     long long ct = (long long)grid.x * grid.y / 512;
     r2.col_tiles = (int)(ct < 1 ? 1 : (ct > 16 ? 16 : ct));
     grid.x = (grid.x + r2.col_tiles - 1) / r2.col_tiles;
-    hipLaunchKernelGGL((pairs_f32_kernel<SCORER, T, true>), grid, dim3(256), 0, st, A, R, TG, dir, d, n, m, round_q,
-                       out, ldo, r2);
+    hipLaunchKernelGGL((pairs_f32_kernel<SCORER, T, F3_RANK>), grid, dim3(256), 0, st, A, R, TG, dir, d, n, m, round_q,
+                       out, ldo, r2, F32LossArgs{});
   } else
-    hipLaunchKernelGGL((pairs_f32_kernel<SCORER, T, false>), grid, dim3(256), 0, st, A, R, TG, dir, d, n, m, round_q,
-                       out, ldo, RankArgs{});
+    hipLaunchKernelGGL((pairs_f32_kernel<SCORER, T, F3_STORE>), grid, dim3(256), 0, st, A, R, TG, dir, d, n, m, round_q,
+                       out, ldo, RankArgs{}, F32LossArgs{});
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 
@@ -229,6 +322,28 @@ int run_pairs_f32(int scorer, int dtype, const Operand& A, const Operand& R, con
                ? launch_pairs_f32<KGE_DISTMULT, unsigned short>(A, R, TG, dir, d, n, m, round_q, out, ldo, st, rk)
                : launch_pairs_f32<KGE_DISTMULT, float>(A, R, TG, dir, d, n, m, round_q, out, ldo, st, rk);
   return KGE_ERR_UNSUPPORTED;
+}
+
+// The loss epilogues on float32 tables (ce_f32.hip; the caller checked the layout run_pairs_f32 takes).
+// fold: records of the n rows over all m columns, grid = ce.groups x row tiles, ce.col_tiles tiles per workgroup.
+// !fold: out [n, ldo] = d loss / d score of the m columns from ce.col_lo on; ldo % 128 == 0, ldo >= m rounded up to 128.
+int run_pairs_f32_loss(int scorer, bool fold, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                       long long n, long long m, float* out, long long ldo, const F32LossArgs& ce, hipStream_t st) {
+  if (n > 65535LL * F3_BM) return KGE_ERR_UNSUPPORTED;
+  if (scorer != KGE_COMPLEX && scorer != KGE_DISTMULT) return KGE_ERR_UNSUPPORTED;
+  const long long tiles = (m + F3_BN - 1) / F3_BN;
+  if (!fold && (ldo % F3_BN || ldo < tiles * F3_BN)) return KGE_ERR_INVALID_ARG;
+  const dim3 grid((unsigned)(fold ? ce.groups : tiles), (unsigned)((n + F3_BM - 1) / F3_BM));
+#define KGE_F3L(SC, MD) \
+  hipLaunchKernelGGL((pairs_f32_kernel<SC, float, MD>), grid, dim3(256), 0, st, A, R, TG, dir, d, n, m, 0, out, ldo, \
+                     RankArgs{}, ce)
+  if (scorer == KGE_COMPLEX) {
+    if (fold) KGE_F3L(KGE_COMPLEX, F3_CE); else KGE_F3L(KGE_COMPLEX, F3_GRAD);
+  } else {
+    if (fold) KGE_F3L(KGE_DISTMULT, F3_CE); else KGE_F3L(KGE_DISTMULT, F3_GRAD);
+  }
+#undef KGE_F3L
+  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 
 }  // namespace kge

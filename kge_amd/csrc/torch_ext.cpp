@@ -254,6 +254,51 @@ std::vector<at::Tensor> ce_dist_bwd(const at::Tensor& ent, const at::Tensor& rel
   return {g_a, g_p, g_t};
 }
 
+// ---- fused 1vsAll loss of ComplEx / DistMult on FLOAT32 tables (kge_ce_f32_*): the same signatures; l_norm is not read
+int64_t ce_f32_workspace_bytes(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t n,
+                                int64_t chunk_cols) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  return kge_ce_f32_workspace_bytes(&t, n, chunk_cols);
+}
+
+std::vector<at::Tensor> ce_f32_fwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                    int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& label,
+                                    const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n), li = index_of(label, ent, keep, &n);
+  at::Tensor loss_rows = empty_f32({n}, ent), lse = empty_f32({n}, ent);
+  check(kge_ce_f32_fwd(&t, (int)direction, ai, pi, li, n, loss_rows.data_ptr<float>(), lse.data_ptr<float>(),
+                        ce_dist_ws(workspace, workspace_bytes), workspace_bytes, stream_of(ent)),
+        "kge_ce_f32_fwd");
+  return {loss_rows, lse};
+}
+
+std::vector<at::Tensor> ce_f32_bwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                    int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& label,
+                                    const at::Tensor& lse, const c10::optional<at::Tensor>& g_rows, double g_scalar,
+                                    const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n), li = index_of(label, ent, keep, &n);
+  const at::Tensor lse_c = lse.to(at::kFloat).contiguous();
+  TORCH_CHECK_VALUE(lse_c.numel() == n, "kge_amd: lse must have one entry per row");
+  at::Tensor gr;
+  if (g_rows.has_value() && g_rows->defined()) {
+    gr = g_rows->to(at::kFloat).contiguous();
+    TORCH_CHECK_VALUE(gr.numel() == n, "kge_amd: g_rows must have one entry per row");
+  }
+  at::Tensor g_a = empty_f32({n, t.dim}, ent), g_p = empty_f32({n, t.rel_dim}, ent), g_t = empty_f32({t.num_ent, t.dim}, ent);
+  check(kge_ce_f32_bwd(&t, (int)direction, ai, pi, li, n, lse_c.data_ptr<float>(),
+                        gr.defined() ? gr.data_ptr<float>() : nullptr, (float)g_scalar, g_a.data_ptr<float>(),
+                        g_p.data_ptr<float>(), g_t.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes),
+                        workspace_bytes, stream_of(ent)),
+        "kge_ce_f32_bwd");
+  return {g_a, g_p, g_t};
+}
+
 // ---- the KvsAll losses of TransE / RotatE on float32 tables (kge_kl_dist_* / kge_bce_dist_*): labels as an int64 CSR
 // (rowptr [n + 1], col [nnz]) on the tables' device; workspace as above (kge_multilabel_dist_workspace_bytes).
 int64_t multilabel_dist_workspace_bytes(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
@@ -373,6 +418,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ce_dist_workspace_bytes", &ce_dist_workspace_bytes);
   mod.def("ce_dist_fwd", &ce_dist_fwd, "1vsAll cross entropy of TransE / RotatE without a score matrix: (loss_rows, lse)");
   mod.def("ce_dist_bwd", &ce_dist_bwd, "its backward: (g_a, g_p, g_entities)");
+  mod.def("ce_f32_workspace_bytes", &ce_f32_workspace_bytes);
+  mod.def("ce_f32_fwd", &ce_f32_fwd, "1vsAll cross entropy of float32 ComplEx / DistMult without a score matrix: (loss_rows, lse)");
+  mod.def("ce_f32_bwd", &ce_f32_bwd, "its backward: (g_a, g_p, g_entities)");
   mod.def("multilabel_dist_workspace_bytes", &multilabel_dist_workspace_bytes);
   mod.def("kl_dist_fwd", &kl_dist_fwd, "KvsAll kl loss of TransE / RotatE without a score matrix: (loss_rows, lse)");
   mod.def("kl_dist_bwd", &kl_dist_bwd, "its backward: (g_a, g_p, g_entities)");

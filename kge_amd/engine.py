@@ -1563,6 +1563,87 @@ def ce_dist_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scal
     return g_a, g_p, g_t
 
 
+def ce_f32_supported(t: Tables) -> bool:
+    """Can the fused 1vsAll loss of float32 ComplEx / DistMult tables run (kge_ce_f32_workspace_bytes > 0): float32,
+    dim % 8 == 0, 16-byte aligned rows, on a GPU?"""
+    if not t.ent.is_cuda:
+        return False
+    return _lib.lib().kge_ce_f32_workspace_bytes(ctypes.byref(t.c()), 1, 0) > 0
+
+
+def _ce_f32_args(t: Tables, a, p, label, chunk_cols, what, per_row=()):
+    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths, the
+    lengths of the `per_row` vectors (None: not given)."""
+    chunk_cols = int(chunk_cols)
+    if chunk_cols < 0 or chunk_cols % 128:
+        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 128, got {chunk_cols}")
+    if t.scorer not in (_lib.COMPLEX, _lib.DISTMULT) or t.ent.dtype != torch.float32 or t.rel.dtype != torch.float32:
+        raise RuntimeError(f"kge_amd: {what}: ComplEx / DistMult on float32 tables only "
+                           "(bf16 tables: ce_fwd / ce_bwd; TransE / RotatE: ce_dist_fwd / ce_dist_bwd)")
+    if t.ent.shape[1] % 8:
+        raise RuntimeError(f"kge_amd: {what}: the dimension must be a multiple of 8, got {t.ent.shape[1]}")
+    keep = []
+    ixs = tuple(_index(x, t.device, keep) for x in (a, p, label))
+    n = _same_len(keep[:3], what)
+    if any(x is not None and x.numel() != n for x in per_row):
+        raise ValueError(f"kge_amd: {what}: lse and g_rows must have one entry per row")
+    _require_gpu(t.ent, "entity table")
+    return ixs, n, chunk_cols, keep
+
+
+def _ce_f32_workspace(tc, n, chunk_cols, device, st):
+    """(ptr, bytes): the per-(device, stream) scratch of kge_ce_f32_fwd / _bwd; `bytes` is exactly what the chunk width
+    asks for (the backward derives its chunk width from it), the buffer may be larger."""
+    need = _lib.lib().kge_ce_f32_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
+    if need <= 0:
+        raise RuntimeError("kge_ce_f32_fwd/kge_ce_f32_bwd: float32 ComplEx / DistMult tables, dim % 8 == 0, "
+                           "16-byte aligned rows only")
+    key = (device.index, st, "ce_f32")
+    buf = _WORKSPACES.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
+    return buf.data_ptr(), need
+
+
+def ce_f32_fwd(t: Tables, direction: str, a, p, label, chunk_cols: int = 0):
+    """ce_fwd for ComplEx / DistMult on float32 tables (kge_ce_f32_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
+    a = s, label = o) / score_po ('po': a = o, label = s) against all entities, no [n, E] matrix."""
+    (ai, pi, li), n, chunk_cols, keep = _ce_f32_args(t, a, p, label, chunk_cols, "ce_f32_fwd")
+    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
+    if n == 0:
+        return loss_rows, lse
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ce_f32_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_ce_f32_fwd(ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n,
+                                             loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_ce_f32_fwd")
+    return loss_rows, lse
+
+
+def ce_f32_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scalar: float = 1.0, chunk_cols: int = 0):
+    """Backward of ce_f32_fwd (kge_ce_f32_bwd): gradients of sum_i g_i * loss_rows[i] w.r.t. the gathered query rows
+    and all entity rows: (g_a [n, d], g_p [n, d], g_entities [E, d]).  chunk_cols: entity columns per chunk of the
+    backward (a multiple of 128; 0 = the library's default, a gradient chunk of at most 32 MB)."""
+    (ai, pi, li), n, chunk_cols, keep = _ce_f32_args(t, a, p, label, chunk_cols, "ce_f32_bwd", (lse, g_rows))
+    d, dr = t.ent.shape[1], t.rel.shape[1]
+    lse = _f32c(lse, t.device)
+    gr = None if g_rows is None else _f32c(g_rows, t.device)
+    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
+    if n == 0:
+        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
+    g_t = _empty((t.num_ent, d), t.device)
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ce_f32_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_ce_f32_bwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n, lse.data_ptr(),
+            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(),
+            g_t.data_ptr(), ws, wsb, st), "kge_ce_f32_bwd")
+    return g_a, g_p, g_t
+
+
 # ---- KvsAll losses of the distance scorers (kge_kl_dist_* / kge_bce_dist_*): labels as an int64 CSR per row -------------
 def _ml_dist_args(t: Tables, a, p, lbl_rowptr, lbl_col, chunk_cols, what):
     """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths, the CSR."""

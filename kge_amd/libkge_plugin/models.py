@@ -8,7 +8,7 @@ from kge.model.rotate import RotatE as _RefRotatE
 from kge.model.transe import TransE as _RefTransE
 
 from .. import engine
-from ..model import (BF16Shadow, _FusedBCEDist, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedKLDist,
+from ..model import (BF16Shadow, _FusedBCEDist, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32, _FusedKLDist,
                      _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
                      bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable)
 
@@ -276,6 +276,30 @@ class _FusedScoring:
         t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
         return t if engine.ce_dist_supported(t) else None
 
+    # `hip_1vsAll.fused_f32_loss: true` (set by HipTrainingJob1vsAll; false by default): the 1vsAll kl loss of hip_complex /
+    # hip_distmult scoring in float32 without an [n, E] matrix (kge_ce_f32_fwd / kge_ce_f32_bwd).
+    _fused_f32_loss = False
+
+    def _ce_f32_tables(self):
+        """float32 tables for the fused loss of ComplEx / DistMult, or None (the composed path): the option on, float32
+        parameters scored in float32 (no `score_dtype: bfloat16` copies), `_fused()` (plain lookup embedders, no active
+        dropout, parameters on a GPU), a layout kge_ce_f32_workspace_bytes takes (dim % 8 == 0)."""
+        if not self._fused_f32_loss or not self._fused() or self._scorer.name not in ("complex", "distmult"):
+            return None
+        ent, rel = self._w()
+        if ent.dtype != torch.float32 or self._fwd_tables() is not None:  # (`_fused()`: the parameters are on a GPU)
+            return None
+        t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
+        return t if engine.ce_f32_supported(t) else None
+
+    def _loss_one_sided(self, direction, a, p, label):
+        """loss_sp / loss_po where neither _ce_tables() nor _dropout_only() applies: the float32 fused losses, or None."""
+        td = self._ce_dist_tables()
+        if td is not None:
+            return _FusedCEDist.apply(direction, *self._w(), a, p, label, td)
+        tf = self._ce_f32_tables()
+        return None if tf is None else _FusedCEF32.apply(direction, *self._w(), a, p, label, tf)
+
     def _rank_tables(self):
         """The tables HipEntityRankingJob counts on (kge_score_rank_sp_po: scoring + _filter_and_rank counts in one
         kernel) -- the ones score_sp_po scores on under no_grad, so that fused and two-step counts agree bit for bit:
@@ -291,8 +315,7 @@ class _FusedScoring:
         t = self._ce_tables()
         dp = self._dropout_only() if t is None else None
         if t is None and dp is None:
-            td = self._ce_dist_tables()
-            return None if td is None else _FusedCEDist.apply("sp", *self._w(), s, p, o, td)
+            return self._loss_one_sided("sp", s, p, o)
         ent, rel = self._w()
         if dp is not None:  # embedder dropout in training: the masks applied here, the fused kernels on dense rows
             return ce_fused_dropout(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, o, dp[0], dp[1])
@@ -302,8 +325,7 @@ class _FusedScoring:
         t = self._ce_tables()
         dp = self._dropout_only() if t is None else None
         if t is None and dp is None:
-            td = self._ce_dist_tables()
-            return None if td is None else _FusedCEDist.apply("po", *self._w(), o, p, s, td)
+            return self._loss_one_sided("po", o, p, s)
         ent, rel = self._w()
         if dp is not None:  # embedder dropout in training: the masks applied here, the fused kernels on dense rows
             return ce_fused_dropout(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, s, dp[0], dp[1])
@@ -314,9 +336,9 @@ class _FusedScoring:
         t = self._ce_tables()
         if t is None:
             if self._dropout_only() is None:
-                if self._ce_dist_tables() is None:
+                if self._ce_dist_tables() is None and self._ce_f32_tables() is None:
                     return None
-                return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))  # (the distance scorers: one-sided calls)
+                return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))  # (float32 tables: one-sided calls)
             # independent masks per direction, as the reference's two score_* calls draw them
             return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))
         ent, rel = self._w()
@@ -531,6 +553,10 @@ class HipReciprocalRelationsModel(_RefReciprocal):
 
     def _ce_dist_tables(self):
         f = getattr(self._base_model, "_ce_dist_tables", None)
+        return f() if f is not None else None
+
+    def _ce_f32_tables(self):
+        f = getattr(self._base_model, "_ce_f32_tables", None)
         return f() if f is not None else None
 
     def loss_sp(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:

@@ -40,6 +40,24 @@ def _model_takes_dist_loss(model) -> bool:
     return f is not None and f() is not None
 
 
+def _model_takes_f32_loss(model) -> bool:
+    """The fused 1vsAll kl loss of hip_complex / hip_distmult scoring in float32 (`hip_1vsAll.fused_f32_loss: true`):
+    decided once per subbatch; the two one-sided calls loss_sp / loss_po, no captured step, no two-sided launch."""
+    f = getattr(model, "_ce_f32_tables", None)
+    return f is not None and f() is not None
+
+
+def _set_fused_f32_loss(job, key):
+    """`<key>.fused_f32_loss` (false by default), handed to the models like `fused_dist_loss` below."""
+    try:
+        fused_f32 = bool(job.config.get_default(key + ".fused_f32_loss"))
+    except KeyError:
+        fused_f32 = False
+    for m in (job.model, getattr(job.model, "_base_model", None)):
+        if m is not None and hasattr(type(m), "_fused_f32_loss"):
+            m._fused_f32_loss = fused_f32
+
+
 def _set_fused_dist_loss(job, key):
     """`<key>.fused_dist_loss` (false by default): the models learn it here and decide per subbatch
     (_FusedScoring._ce_dist_tables); under hip_reciprocal_relations_model the base model is the one that scores."""
@@ -215,6 +233,7 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
         self._graph_step_ok = None    # decided at the first batch (None: not yet)
         self._skip_optimizer_step = False
         _set_fused_dist_loss(self, "hip_1vsAll")
+        _set_fused_f32_loss(self, "hip_1vsAll")
         if self.__class__ == HipTrainingJob1vsAll:
             for f in Job.job_created_hooks:
                 f(self)
@@ -275,6 +294,8 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
         bce = offset is not None and hasattr(self.model, "bce_loss_sp")
         # hip_1vsAll.fused_dist_loss: loss_sp, then loss_po (kl); bce_loss_sp, then bce_loss_po (bce)
         dist = (kl or bce) and not takes and _model_takes_dist_loss(self.model)
+        # hip_1vsAll.fused_f32_loss (kl only): the same two one-sided calls
+        dist = dist or (kl and not takes and _model_takes_f32_loss(self.model))
         if not takes and not dist:
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)
         if bce:

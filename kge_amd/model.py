@@ -112,8 +112,11 @@ class KgeModel(torch.nn.Module):
 
     def __init__(self, num_entities: int, num_relations: int, dim: int, l_norm: float = 1.0,
                  dtype=torch.float32, device=None, entity_args=None, relation_args=None,
-                 score_dtype=None, fused_dist_loss: bool = False):
+                 score_dtype=None, fused_dist_loss: bool = False, fused_f32_loss: bool = False):
         super().__init__()
+        # fused_f32_loss=True (ComplEx / DistMult, float32 parameters on a GPU scored in float32, dim % 8 == 0): loss_sp /
+        # loss_po / loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_f32_fwd / _bwd); off by default
+        self.fused_f32_loss = bool(fused_f32_loss)
         # fused_dist_loss=True (TransE / RotatE, float32 parameters on a GPU, l_norm 1 or 2): loss_sp / loss_po /
         # loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_dist_fwd / _bwd), and kl_loss_sp / kl_loss_po /
         # bce_loss_sp / bce_loss_po without label smoothing (kge_kl_dist_* / kge_bce_dist_*); off by default
@@ -251,6 +254,18 @@ class KgeModel(torch.nn.Module):
         t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach(), self._scorer._norm)
         return t if engine.ce_dist_supported(t) else None
 
+    def _ce_f32_tables(self):
+        """float32 tables for the fused loss of ComplEx / DistMult (`fused_f32_loss=True`), or None (then the loss is
+        composed from score_sp / score_po): float32 parameters scored in float32, pure lookups, on a GPU, a layout
+        kge_ce_f32_workspace_bytes takes."""
+        if not self.fused_f32_loss or not self._fused() or self._scorer.name not in ("complex", "distmult"):
+            return None
+        w = self._entity_embedder.weight
+        if not w.is_cuda or w.dtype != torch.float32 or self._shadow is not None:
+            return None
+        t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach())
+        return t if engine.ce_f32_supported(t) else None
+
     def loss_sp(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
         """Per-row cross entropy of score_sp(s, p) against the true objects o ([n]); its sum is the
         reference's `self.loss(scores_sp, triples[:, 2])` with train.loss=kl (loss.py:192-207)."""
@@ -260,6 +275,9 @@ class KgeModel(torch.nn.Module):
         td = self._ce_dist_tables()
         if td is not None:
             return _FusedCEDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, td)
+        tf = self._ce_f32_tables()
+        if tf is not None:
+            return _FusedCEF32.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, tf)
         return torch.nn.functional.cross_entropy(self.score_sp(s, p), o.long(), reduction="none")
 
     def loss_sp_po(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
@@ -290,6 +308,9 @@ class KgeModel(torch.nn.Module):
         td = self._ce_dist_tables()
         if td is not None:
             return _FusedCEDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p, s, td)
+        tf = self._ce_f32_tables()
+        if tf is not None:
+            return _FusedCEF32.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p, s, tf)
         return torch.nn.functional.cross_entropy(self.score_po(p, o), s.long(), reduction="none")
 
     # -- KvsAll loss: train_KvsAll.py:274-294 with train.loss=kl
@@ -692,6 +713,30 @@ class _FusedCEDist(torch.autograd.Function):
         (lse,) = ctx.saved_tensors
         g_a, g_p, ge = engine.ce_dist_bwd(ctx.t, ctx.direction, a, p, label, lse, g_rows=g_rows.contiguous(),
                                           chunk_cols=ctx.chunk_cols)
+        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
+        _scatter_rows(gr, p, g_p)
+        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
+        return None, ge, gr, None, None, None, None, None
+
+
+class _FusedCEF32(torch.autograd.Function):
+    """_FusedCE for ComplEx / DistMult on FLOAT32 tables (kge_ce_f32_fwd / kge_ce_f32_bwd): `tables` are the parameters
+    themselves; the backward walks the entity columns in chunks of `chunk_cols` (0: the library's default)."""
+
+    @staticmethod
+    def forward(ctx, direction, ent, rel, a, p, label, tables, chunk_cols=0):
+        loss_rows, lse = engine.ce_f32_fwd(tables, direction, a, p, label, chunk_cols)
+        ctx.t, ctx.direction, ctx.idx, ctx.chunk_cols = tables, direction, (a, p, label), chunk_cols
+        ctx.rel_shape = rel.shape
+        ctx.save_for_backward(lse)
+        return loss_rows
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        a, p, label = ctx.idx
+        (lse,) = ctx.saved_tensors
+        g_a, g_p, ge = engine.ce_f32_bwd(ctx.t, ctx.direction, a, p, label, lse, g_rows=g_rows.contiguous(),
+                                         chunk_cols=ctx.chunk_cols)
         gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
         _scatter_rows(gr, p, g_p)
         _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows

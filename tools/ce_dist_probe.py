@@ -1,10 +1,12 @@
 """Fused against composed 1vsAll step for TransE / RotatE (kge_amd.model, fused_dist_loss on / off): time per step and
 torch.cuda.max_memory_allocated, l_norm 1 and 2, at E = 14,541 (FB15k-237) and E = 574,311 (a one-eighth Wikidata5M
 shard), n = 512, d = 128.  --mode kvsall_kl / kvsall_bce: the KvsAll step instead (kl_loss_sp + kl_loss_po or
-bce_loss_sp + bce_loss_po, no label smoothing) with 0..16 (about 8) random labels per row.
+bce_loss_sp + bce_loss_po, no label smoothing) with 0..16 (about 8) random labels per row.  --mode f32_1vsall: the
+1vsAll step of float32 ComplEx / DistMult with fused_f32_loss on / off (kge_ce_f32_*).
 
     python tools/ce_dist_probe.py [--mode 1vsall] [--out profiles/ce_dist_probe.txt] [--steps 10] [--limit 120]
     python tools/ce_dist_probe.py --mode kvsall_kl --out profiles/multilabel_dist_probe_kl.txt
+    python tools/ce_dist_probe.py --mode f32_1vsall --out profiles/ce_f32_probe.txt
 
 The parent never touches the GPU: every (shape, scorer, norm, path) step runs in a child process of its own under its
 own time limit, and after a child that fails in any way other than running out of memory nothing more is started."""
@@ -24,12 +26,13 @@ def one(name, l_norm, E, R, n, d, fused, steps, mode="1vsall"):
     from kge_amd import model as km
     dev = "cuda:0"
     torch.manual_seed(0)
-    m = km.create(name, E, R, d, l_norm=l_norm, device=dev, fused_dist_loss=fused).train()
+    opt = {"fused_f32_loss": fused} if mode == "f32_1vsall" else {"fused_dist_loss": fused}
+    m = km.create(name, E, R, d, l_norm=l_norm, device=dev, **opt).train()
     g = torch.Generator().manual_seed(1)
     s, p, o = (torch.randint(hi, (n,), generator=g).to(dev) for hi in (E, R, E))
 
     csr = []
-    for _ in range(2 if mode != "1vsall" else 0):  # label CSRs of the sp_ and the _po queries: 0..16 labels per row
+    for _ in range(2 if mode.startswith("kvsall") else 0):  # label CSRs of the sp_ and the _po queries: 0..16 labels per row
         k = torch.randint(0, 17, (n,), generator=g)
         rowptr = torch.zeros(n + 1, dtype=torch.int64)
         rowptr[1:] = torch.cumsum(k, 0)
@@ -38,7 +41,7 @@ def one(name, l_norm, E, R, n, d, fused, steps, mode="1vsall"):
 
     def step():
         m.zero_grad(set_to_none=True)
-        if mode == "1vsall":
+        if mode in ("1vsall", "f32_1vsall"):
             (m.loss_sp(s, p, o).sum() / n).backward()
             (m.loss_po(p, o, s).sum() / n).backward()
         elif mode == "kvsall_kl":
@@ -66,7 +69,7 @@ def one(name, l_norm, E, R, n, d, fused, steps, mode="1vsall"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", default="1vsall", choices=("1vsall", "kvsall_kl", "kvsall_bce"))
+    ap.add_argument("--mode", default="1vsall", choices=("1vsall", "kvsall_kl", "kvsall_bce", "f32_1vsall"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--limit", type=int, default=120, help="seconds per child")
@@ -75,11 +78,13 @@ def main():
     if a.one:
         name, l_norm, E, R, n, d, fused = a.one
         return one(name, float(l_norm), int(E), int(R), int(n), int(d), fused == "1", a.steps, a.mode)
-    lines = [f"# fused (fused_dist_loss=True) against composed {a.mode} step, both directions, n and d below; "
-             f"{a.steps} timed steps after one warm-up", "scorer l_norm E n d path ms_per_step peak_MB"]
+    f32 = a.mode == "f32_1vsall"
+    lines = [f"# fused ({'fused_f32_loss' if f32 else 'fused_dist_loss'}=True) against composed {a.mode} step, both "
+             f"directions, n and d below; {a.steps} timed steps after one warm-up",
+             "scorer l_norm E n d path ms_per_step peak_MB"]
     for E, R, n, d in SHAPES:
-        for name in ("transe", "rotate"):
-            for l_norm in (1, 2):
+        for name in (("complex", "distmult") if f32 else ("transe", "rotate")):
+            for l_norm in ((1,) if f32 else (1, 2)):  # (ComplEx / DistMult have no norm)
                 for fused in (1, 0):
                     cmd = [sys.executable, os.path.abspath(__file__), "--mode", a.mode, "--steps", str(a.steps), "--one", name, str(l_norm),
                            str(E), str(R), str(n), str(d), str(fused)]
