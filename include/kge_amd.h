@@ -811,6 +811,68 @@ int kge_bce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int
                      float g_scalar, float* g_a, float* g_p, float* g_tgt, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* ---- the KvsAll losses for ComplEx / DistMult on float32 tables ---------------- */
+/* kge_kl_f32_fwd / _bwd and kge_bce_f32_fwd / _bwd: the losses of kge_kl_fwd / kge_kl_weighted_fwd /
+ * kge_kl_weighted_bwd and kge_bce_fwd / kge_bce_bwd above, for ComplEx and DistMult (complex.py:30-39,
+ * distmult.py:15-21) on float32 tables -- the reference's own precision -- without an [n, num_ent] matrix: the step of
+ * TrainingJobKvsAll for sp_ / _po queries (kge/job/train_KvsAll.py:216-294) with KLDivWithSoftmaxKgeLoss on a label
+ * matrix (kge/util/loss.py:192-213) or BCEWithLogitsKgeLoss with bce_type None (kge/util/loss.py:137-159), built on
+ * the kernels of kge_ce_f32_fwd / kge_ce_f32_bwd and the label machinery of kge_kl_dist_*.
+ *   kl, label_weight == NULL:  loss_rows[i] = lse[i] - (1/k_i) sum_{j in labels_i} score(i, j) - log k_i   (0 if k_i = 0)
+ *   kl, label_weight [n]:      loss_rows[i] = lse[i] - w_i sum_{j in labels_i} score(i, j)      (k_i = 0: lse[i])
+ *   bce:  loss_rows[i] = sum over ALL entities j of max(x, 0) - x y_ij + log1p(exp(-|x|)),  x = score(i, j) + offset
+ *   d / d score(i, j) of sum_i g_i loss_rows[i]:  kl  g_i (softmax_ij - b_i - w_i [j in labels_i])   (w_i = 1/k_i
+ *   without a weight, and then g_i = 0 for a row without labels; b_i = label_bias[i], 0 for label_bias == NULL: the
+ *   uniform term of smoothed labels as for kge_kl_weighted_bwd -- these scores are linear in the target row, so
+ *   KvsAll label smoothing (train_KvsAll.py:34-49, 262-270) stays on this path);
+ *   bce  g_i (sigmoid(score(i, j) + offset) - [j in labels_i])
+ * Labels: lbl_col[lbl_rowptr[i] .. lbl_rowptr[i+1]), an int64 CSR on the device, entity ids unique per row, in ANY
+ * order within a row.  A label outside [0, num_ent) gives loss_rows[i] = NaN and leaves the other rows (and lse)
+ * untouched; the backward ignores it.  The forward is the exact f32 matrix-core scoring kernel with a fold epilogue
+ * (kl: a per-row running (max, sum exp); bce: a sum of softplus): every score of the dense part is bit-identical to
+ * kge_score_sp / kge_score_po, the partial results are merged in a fixed order, and lse is BIT-EQUAL to
+ * kge_ce_f32_fwd's on the same tables and queries.  The label scores are f32 dot products of the query vector (the
+ * Q of kge_score_pairs_bwd) with the label's row: the same operands as the matrix-core kernel in a different f32
+ * summation order; they are summed in CSR order.  No float atomics: the same bits on every run.  The backward walks
+ * the entity columns in chunks as kge_ce_f32_bwd does (g_tgt OVERWRITTEN, bit-equal whatever the chunk width; the
+ * query-side gradient summed in chunk order, then split-K order); a bit mask of n x chunk bits per chunk (set from the
+ * CSR with atomic OR) says which columns are labels.
+ *   g_rows, g_scalar, g_a [n, dim], g_p [n, rel_dim], g_tgt [num_ent, dim]: as for kge_ce_f32_bwd (f32, OVERWRITTEN;
+ *   n = 0: g_tgt is zero-filled).
+ * kge_multilabel_f32_workspace_bytes(t, n, chunk_cols) (train_KvsAll.py:216-294): chunk_cols and the support matrix as
+ * for kge_ce_f32_workspace_bytes (ComplEx / DistMult, KGE_F32, dim % 8 == 0, rel_dim == dim, 16-byte aligned rows;
+ * otherwise 0).  The workspace is kge_ce_f32's layout -- records | [n, dim] | [n, dim] (the query matrix Q) | split-K
+ * partials | the [n, chunk] gradient block -- plus n x chunk / 8 bytes of label bits, each part rounded up to 256
+ * bytes: 256-byte aligned device scratch, no initialisation, stream-ordered use, not shared by concurrent calls.  The
+ * FORWARD needs the records and the two [n, dim] buffers (it writes Q where the backward keeps it):
+ *   align256(12 n G) + 2 align256(4 n dim),  G = the column groups of kge_ce_f32_fwd (at most 256);
+ * the BACKWARD derives its chunk width from `workspace_bytes` and needs at least
+ *   kge_multilabel_f32_workspace_bytes(t, n, 128);
+ * below these, KGE_ERR_WORKSPACE.  The backward leaves the label bits all zero.
+ * kge_kl_f32_fwd (train_KvsAll.py:274-294, loss.py:192-213: the kl loss values of a query type),
+ * kge_bce_f32_fwd (train_KvsAll.py:274-294, loss.py:137-159: the bce loss values of a query type),
+ * kge_kl_f32_bwd (train_KvsAll.py:274-294, loss.py:192-213 under loss_value.backward(): their gradients) and
+ * kge_bce_f32_bwd (train_KvsAll.py:274-294, loss.py:137-159 under loss_value.backward()): other scorers, bf16 tables
+ * or another layout: KGE_ERR_UNSUPPORTED, nothing is launched.  No allocation, no host wait, no library call, no float
+ * atomics: all four are stream-ordered and capturable into a hipGraph. */
+int64_t kge_multilabel_f32_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols);
+int kge_kl_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                   const int64_t* lbl_rowptr, const int64_t* lbl_col,
+                   const float* label_weight /* [n] or NULL */, float* loss_rows, float* lse,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+int kge_kl_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                   const int64_t* lbl_rowptr, const int64_t* lbl_col,
+                   const float* label_weight /* [n] or NULL */, const float* label_bias /* [n] or NULL */,
+                   const float* lse, const float* g_rows, float g_scalar, float* g_a, float* g_p,
+                   float* g_tgt, void* workspace, int64_t workspace_bytes, void* stream);
+int kge_bce_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                    const int64_t* lbl_rowptr, const int64_t* lbl_col, float offset, float* loss_rows,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int kge_bce_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
+                    const int64_t* lbl_rowptr, const int64_t* lbl_col, float offset, const float* g_rows,
+                    float g_scalar, float* g_a, float* g_p, float* g_tgt, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* Both query types of a KvsAll batch, backward, with COMPLETE table gradients.  TrainingJobKvsAll scores the sp_ and
  * the _po queries of a batch one after the other and back-propagates each loss on its own
  * (kge/job/train_KvsAll.py:274-294): two d loss / d score passes, four gradient products, and autograd's index_add and

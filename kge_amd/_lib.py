@@ -203,6 +203,15 @@ PROTOTYPES = {
                                         c_vp, c_i64, c_vp]),
     "kge_bce_dist_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, ctypes.c_float, c_vp,
                                         ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "kge_multilabel_f32_workspace_bytes": (c_i64, [_PT, c_i64, c_i64]),
+    "kge_kl_f32_fwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_i64, c_vp]),
+    "kge_kl_f32_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "kge_bce_f32_fwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, ctypes.c_float, c_vp,
+                                       c_vp, c_i64, c_vp]),
+    "kge_bce_f32_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, ctypes.c_float, c_vp,
+                                       ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "kge_ce_sp_po_workspace_bytes": (c_i64, [_PT, c_i64]),
     "kge_ce_sp_po_fwd": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "kge_ce_sp_po_bwd": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, ctypes.c_float, c_vp,

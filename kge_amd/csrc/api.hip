@@ -33,6 +33,14 @@ int run_ce_f32_fwd(int scorer, const Operand& A, const Operand& R, const Operand
 int run_ce_f32_bwd(int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n,
                    long long m, const Index& label, const float* lse, const float* g_rows, float g_scalar, float* g_a,
                    float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st);
+long long ml_f32_workspace_bytes(long long n, long long m, int d, long long chunk_cols);
+int run_ml_f32_fwd(bool bce, int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                   long long n, long long m, const long long* rowptr, const long long* col, const float* label_weight,
+                   float offset, float* loss_rows, float* lse, void* ws, long long ws_bytes, hipStream_t st);
+int run_ml_f32_bwd(bool bce, int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+                   long long n, long long m, const long long* rowptr, const long long* col, const float* label_weight,
+                   const float* label_bias, float offset, const float* lse, const float* g_rows, float g_scalar,
+                   float* g_a, float* g_p, float* g_tgt, void* ws, long long ws_bytes, hipStream_t st);
 long long ce_dist_workspace_bytes(long long n, long long m, int d, long long chunk_cols);
 int run_ce_dist_fwd(int scorer, float lp, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr,
                     long long n, long long m, const Index& label, float* loss_rows, float* lse, void* ws,
@@ -1758,6 +1766,83 @@ int kge_bce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int
                          (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr,
                          offset, nullptr, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
                          (hipStream_t)stream);
+}
+
+// ---- the KvsAll losses of ComplEx / DistMult on FLOAT32 tables (ce_f32.hip, the folds F3_KL / F3_BCE and the gradient
+// epilogues F3_GRAD_KL / F3_GRAD_BCE): train_KvsAll.py:216-294, loss.py:137-159 and :192-213 ---------------------------
+namespace {
+int ml_f32_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, int64_t n,
+                 const int64_t* lbl_rowptr, const int64_t* lbl_col) {
+  int rc = check_tables(t, true);
+  if (rc) return rc;
+  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
+  if (n < 0) return KGE_ERR_INVALID_ARG;
+  if (!ce_f32_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
+  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n))) return rc;
+  if (n > 0 && (!lbl_rowptr || !lbl_col)) return KGE_ERR_INVALID_ARG;
+  return KGE_OK;
+}
+}  // namespace
+
+int64_t kge_multilabel_f32_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
+  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_f32_tables_ok(t)) return 0;
+  if (chunk_cols < 0 || chunk_cols % 128) return 0;
+  return ml_f32_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+}
+
+int kge_kl_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                   const int64_t* lbl_col, const float* label_weight, float* loss_rows, float* lse, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ml_f32_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (n == 0) return KGE_OK;
+  if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_f32_fwd(false, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+                        (const long long*)lbl_rowptr, (const long long*)lbl_col, label_weight, 0.0f, loss_rows, lse,
+                        workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int kge_kl_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                   const int64_t* lbl_col, const float* label_weight, const float* label_bias, const float* lse,
+                   const float* g_rows, float g_scalar, float* g_a, float* g_p, float* g_tgt, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ml_f32_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_f32_bwd(false, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+                        (const long long*)lbl_rowptr, (const long long*)lbl_col, label_weight, label_bias, 0.0f, lse,
+                        g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int kge_bce_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                    const int64_t* lbl_col, float offset, float* loss_rows, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+  KGE_RANGE();
+  const int rc = ml_f32_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (n == 0) return KGE_OK;
+  if (!loss_rows) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_f32_fwd(true, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+                        (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr, offset, loss_rows, nullptr,
+                        workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int kge_bce_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
+                    const int64_t* lbl_col, float offset, const float* g_rows, float g_scalar, float* g_a, float* g_p,
+                    float* g_tgt, void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int rc = ml_f32_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
+  if (rc) return rc;
+  if (!g_tgt || (n > 0 && (!g_a || !g_p))) return KGE_ERR_INVALID_ARG;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return run_ml_f32_bwd(true, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+                        (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr, nullptr, offset, nullptr,
+                        g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- the same with DENSE query rows (entity-sharded training: the query rows of a batch come out of

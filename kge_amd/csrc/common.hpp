@@ -478,6 +478,9 @@ struct RankArgs {
 };
 
 // ---- loss epilogues of pairs_f32_kernel (score_pairs_f32.hip, driven by ce_f32.hip): kge_ce_f32_fwd / kge_ce_f32_bwd
+// and the KvsAll losses kge_kl_f32_* / kge_bce_f32_* (the F3_KL / F3_BCE folds, the F3_GRAD_KL / F3_GRAD_BCE gradients)
+enum { F3_STORE = 0, F3_RANK = 1, F3_CE = 2, F3_GRAD = 3, F3_KL = 4, F3_BCE = 5, F3_GRAD_KL = 6, F3_GRAD_BCE = 7 };
+
 struct F32LossArgs {
   Index label;          // [n] entity id of row i's true target
   float* rec;           // fold: records [n][groups][3] = max, sum exp(score - max), label score (ce_dist.hip's layout)
@@ -487,6 +490,15 @@ struct F32LossArgs {
   const float* g_rows;  // gradient: upstream gradient per row, or NULL: g_scalar
   float g_scalar;
   long long col_lo;     // gradient: entity id of the chunk's column 0
+  // KvsAll (ce_dist.hip's MlArgs): the chunk's label bits (bit y & 31 of word [i * maskw + (y >> 5)]: chunk column y is
+  // a label of row i), the rows' upstream gradient g_i and label weight w_i (ml_rows_kernel), the label-smoothing bias
+  // b_i (or NULL: 0), the bce offset (fold and gradient)
+  const unsigned int* mask;
+  long long maskw;
+  const float* grow;
+  const float* wrow;
+  const float* bias;
+  float offset;
 };
 
 // A finished ROWS x COLS score tile sits in LDS (`tile`, row pitch LDT floats).  256 threads: thread t takes the W =

@@ -32,7 +32,16 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // the workgroup (ce_dist.hip's record layout, merged by ce_dist_merge_kernel).  Padding columns (>= m) take no part.
 // F3_GRAD (kge_ce_f32_bwd): one tile per workgroup; out[i, j] = g_i (exp(S_ij - lse_i) - [col_lo + j == label_i]) in
 // whole 16-byte pieces, 0 in the padding columns of the tile (`out` has them: its pitch is a multiple of 128).
-enum { F3_STORE = 0, F3_RANK = 1, F3_CE = 2, F3_GRAD = 3 };
+// The KvsAll losses (kge_kl_f32_* / kge_bce_f32_*, ce_f32.hip) ride on the same two epilogues:
+// F3_KL: the walk, the (max, sum exp) arithmetic and the record of F3_CE without a label (rec[.. + 2] is not written:
+// the lse merged from these records has the bits of kge_ce_f32_fwd's).  F3_BCE: rec[.. + 0] = sum of
+// softplus(score + offset) over the group's valid columns.  F3_GRAD_KL: out[i, j] = g_i (exp(S_ij - lse_i) - b_i -
+// w_i [j in labels_i]), F3_GRAD_BCE: g_i (sigmoid(S_ij + offset) - [j in labels_i]); [j in labels_i] is a bit of the
+// chunk's mask (a thread's 4 columns lie in one word), padding columns stay exactly 0.
+// (F3_* modes: common.hpp)
+__device__ __forceinline__ float f3_softplus(float x) {  // max(x, 0) + log1p(exp(-|x|)) (loss.py:137-159)
+  return __builtin_fmaxf(x, 0.0f) + log1pf(expf(-__builtin_fabsf(x)));
+}
 
 template <int SCORER, typename T, int MODE>
 __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Operand TG, int dir, int d,
@@ -40,12 +49,14 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
                                                         float* __restrict__ out, long long ldo, RankArgs rk,
                                                         F32LossArgs ce) {
   constexpr bool RANK = MODE == F3_RANK;
+  constexpr bool FOLD = MODE == F3_CE || MODE == F3_KL || MODE == F3_BCE;
+  constexpr bool GRAD = MODE == F3_GRAD || MODE == F3_GRAD_KL || MODE == F3_GRAD_BCE;
   // [buffer][q|t][half][pair][row]
   __shared__ __attribute__((aligned(16))) float lds[2][2][2][F3_KC][F3_LD];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // RANK: this workgroup walks CT consecutive column tiles of its 128 rows and keeps the counts in registers
-  const int CT = RANK ? rk.col_tiles : MODE == F3_CE ? ce.col_tiles : 1;
+  const int CT = RANK ? rk.col_tiles : FOLD ? ce.col_tiles : 1;
   const long long row0 = (long long)blockIdx.y * F3_BM;
   const int hh = d / 2;
   const int nchunk = (hh + F3_KC - 1) / F3_KC;
@@ -193,7 +204,7 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
       }
     __syncthreads();
     if constexpr (RANK) rank_acc_add<F3_BM, F3_BN, F3_LD>(racc, tile, row0, col0, n, m, rk, tid);
-    if constexpr (MODE == F3_CE) {
+    if constexpr (FOLD) {
       // 16 columns at a time; a thread that has seen only padding keeps (-inf, 0), which the merges skip
 #pragma unroll 1
       for (int q16 = 0; q16 < 4; ++q16) {
@@ -207,6 +218,13 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
           const f32x4 x = *reinterpret_cast<const f32x4*>(&tile[fr * F3_LD + fseg * 64 + q16 * 16 + q * 4]);
           v[q * 4 + 0] = x[0]; v[q * 4 + 1] = x[1]; v[q * 4 + 2] = x[2]; v[q * 4 + 3] = x[3];
         }
+        if constexpr (MODE == F3_BCE) {
+          float s = run_s;
+#pragma unroll
+          for (int k = 0; k < 16; ++k)
+            if (k < valid) s += f3_softplus(v[k] + ce.offset);
+          run_s = s;
+        } else {
         float tm = v[0];
 #pragma unroll
         for (int k = 1; k < 16; ++k)
@@ -218,15 +236,18 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
           if (k < valid) s += expf(v[k] - nm);
         run_m = nm;
         run_s = s;
+        }
+        if constexpr (MODE == F3_CE) {
         const long long off = lbl - cbase;
         if (off >= 0 && off < valid) {
 #pragma unroll
           for (int k = 0; k < 16; ++k)
             if (k == (int)off) lbl_score = v[k];
         }
+        }
       }
     }
-    if constexpr (MODE == F3_GRAD) {
+    if constexpr (GRAD) {
       // thread t: tile rows (t >> 5) + 8 k, columns 4 (t & 31) .. + 3: a wave stores two whole 512-byte row pieces
       const int gc = (tid & 31) * 4;
 #pragma unroll 4
@@ -234,6 +255,7 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
         const int lr = (tid >> 5) + 8 * k;
         const long long orow = row0 + lr;
         if (orow >= n) break;  // (rows ascend with k)
+        if constexpr (MODE == F3_GRAD) {
         const float gi = ce.g_rows != nullptr ? ce.g_rows[orow] : ce.g_scalar;
         const float l = ce.lse[orow];
         const long long lb = index_at(ce.label, orow) - ce.col_lo - col0 - gc;
@@ -246,6 +268,24 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
           g[e] = col0 + gc + e < m ? gi * w : 0.0f;
         }
         *reinterpret_cast<f32x4*>(out + orow * ldo + col0 + gc) = g;
+        } else {
+          // the chunk's column y = col0 + gc + e; gc % 4 == 0: the four bits lie in one word
+          const long long y = col0 + gc;
+          const unsigned int bits = ce.mask[orow * ce.maskw + (y >> 5)] >> (unsigned)(y & 31);
+          const float gi = ce.grow[orow];
+          const float l = MODE == F3_GRAD_KL ? ce.lse[orow] : 0.0f;
+          const float wi = MODE == F3_GRAD_KL ? ce.wrow[orow] : 1.0f;
+          const float bi = MODE == F3_GRAD_KL && ce.bias != nullptr ? ce.bias[orow] : 0.0f;
+          const f32x4 x = *reinterpret_cast<const f32x4*>(&tile[lr * F3_LD + gc]);
+          f32x4 g;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float w = MODE == F3_GRAD_KL ? expf(x[e] - l) - bi : 1.0f / (1.0f + expf(-(x[e] + ce.offset)));
+            if ((bits >> e) & 1u) w -= wi;
+            g[e] = y + e < m ? gi * w : 0.0f;
+          }
+          *reinterpret_cast<f32x4*>(out + orow * ldo + col0 + gc) = g;
+        }
       }
     }
     continue;
@@ -263,7 +303,7 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
     }
   }  // column tiles
   if constexpr (RANK) rank_acc_flush<F3_BM>(racc, row0, n, rk, tid);
-  if constexpr (MODE == F3_CE) {
+  if constexpr (FOLD) {
     // merge the row's two threads (neighbouring lanes) in lane order
     float pm[2], ps[2], pl[2];
 #pragma unroll
@@ -273,7 +313,9 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
       ps[k] = __shfl(run_s, src, 64);
       pl[k] = __shfl(lbl_score, src, 64);
     }
-    if (fseg == 0 && row0 + fr < n) {
+    if constexpr (MODE == F3_BCE) {
+      if (fseg == 0 && row0 + fr < n) ce.rec[((row0 + fr) * ce.groups + blockIdx.x) * 3] = ps[0] + ps[1];
+    } else if (fseg == 0 && row0 + fr < n) {
       const float mm = __builtin_fmaxf(pm[0], pm[1]);
       float ss = 0.0f;
 #pragma unroll
@@ -282,7 +324,7 @@ __global__ __launch_bounds__(256) void pairs_f32_kernel(Operand A, Operand R, Op
       float* o = ce.rec + ((row0 + fr) * ce.groups + blockIdx.x) * 3;
       o[0] = mm;
       o[1] = ss;
-      o[2] = pl[0] + pl[1];  // (at most one of the two is not zero)
+      if constexpr (MODE == F3_CE) o[2] = pl[0] + pl[1];  // (at most one of the two is not zero)
     }
   }
 }
@@ -325,23 +367,36 @@ int run_pairs_f32(int scorer, int dtype, const Operand& A, const Operand& R, con
 }
 
 // The loss epilogues on float32 tables (ce_f32.hip; the caller checked the layout run_pairs_f32 takes).
-// fold: records of the n rows over all m columns, grid = ce.groups x row tiles, ce.col_tiles tiles per workgroup.
-// !fold: out [n, ldo] = d loss / d score of the m columns from ce.col_lo on; ldo % 128 == 0, ldo >= m rounded up to 128.
-int run_pairs_f32_loss(int scorer, bool fold, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+// mode F3_CE / F3_KL / F3_BCE (fold): records of the n rows over all m columns, grid = ce.groups x row tiles,
+// ce.col_tiles tiles per workgroup.
+// mode F3_GRAD / F3_GRAD_KL / F3_GRAD_BCE: out [n, ldo] = d loss / d score of the m columns from ce.col_lo on; ldo % 128 == 0, ldo >= m rounded up to 128.
+int run_pairs_f32_loss(int scorer, int mode, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
                        long long n, long long m, float* out, long long ldo, const F32LossArgs& ce, hipStream_t st) {
   if (n > 65535LL * F3_BM) return KGE_ERR_UNSUPPORTED;
   if (scorer != KGE_COMPLEX && scorer != KGE_DISTMULT) return KGE_ERR_UNSUPPORTED;
+  const bool fold = mode == F3_CE || mode == F3_KL || mode == F3_BCE;
+  if (!fold && mode != F3_GRAD && mode != F3_GRAD_KL && mode != F3_GRAD_BCE) return KGE_ERR_INVALID_ARG;
   const long long tiles = (m + F3_BN - 1) / F3_BN;
   if (!fold && (ldo % F3_BN || ldo < tiles * F3_BN)) return KGE_ERR_INVALID_ARG;
   const dim3 grid((unsigned)(fold ? ce.groups : tiles), (unsigned)((n + F3_BM - 1) / F3_BM));
 #define KGE_F3L(SC, MD) \
   hipLaunchKernelGGL((pairs_f32_kernel<SC, float, MD>), grid, dim3(256), 0, st, A, R, TG, dir, d, n, m, 0, out, ldo, \
                      RankArgs{}, ce)
-  if (scorer == KGE_COMPLEX) {
-    if (fold) KGE_F3L(KGE_COMPLEX, F3_CE); else KGE_F3L(KGE_COMPLEX, F3_GRAD);
-  } else {
-    if (fold) KGE_F3L(KGE_DISTMULT, F3_CE); else KGE_F3L(KGE_DISTMULT, F3_GRAD);
+#define KGE_F3M(SC)                                       \
+  switch (mode) {                                         \
+    case F3_CE: KGE_F3L(SC, F3_CE); break;                \
+    case F3_KL: KGE_F3L(SC, F3_KL); break;                \
+    case F3_BCE: KGE_F3L(SC, F3_BCE); break;              \
+    case F3_GRAD: KGE_F3L(SC, F3_GRAD); break;            \
+    case F3_GRAD_KL: KGE_F3L(SC, F3_GRAD_KL); break;      \
+    default: KGE_F3L(SC, F3_GRAD_BCE); break;             \
   }
+  if (scorer == KGE_COMPLEX) {
+    KGE_F3M(KGE_COMPLEX)
+  } else {
+    KGE_F3M(KGE_DISTMULT)
+  }
+#undef KGE_F3M
 #undef KGE_F3L
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }

@@ -405,6 +405,91 @@ std::vector<at::Tensor> bce_dist_bwd(const at::Tensor& ent, const at::Tensor& re
   return {g_a, g_p, g_t};
 }
 
+// ---- the KvsAll losses of ComplEx / DistMult on FLOAT32 tables (kge_kl_f32_* / kge_bce_f32_*): the signatures of the
+// distance twins above, plus label_bias in the kl backward; workspace: kge_multilabel_f32_workspace_bytes.
+int64_t multilabel_f32_workspace_bytes(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                       int64_t n, int64_t chunk_cols) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  return kge_multilabel_f32_workspace_bytes(&t, n, chunk_cols);
+}
+
+std::vector<at::Tensor> kl_f32_fwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                   int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr,
+                                   const at::Tensor& col, const c10::optional<at::Tensor>& label_weight,
+                                   const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, label_weight, c10::nullopt);
+  at::Tensor loss_rows = empty_f32({n}, ent), lse = empty_f32({n}, ent);
+  check(kge_kl_f32_fwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(), l.w,
+                       loss_rows.data_ptr<float>(), lse.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes),
+                       workspace_bytes, stream_of(ent)),
+        "kge_kl_f32_fwd");
+  return {loss_rows, lse};
+}
+
+std::vector<at::Tensor> kl_f32_bwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                   int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr,
+                                   const at::Tensor& col, const c10::optional<at::Tensor>& label_weight,
+                                   const c10::optional<at::Tensor>& label_bias, const at::Tensor& lse,
+                                   const c10::optional<at::Tensor>& g_rows, double g_scalar, const at::Tensor& workspace,
+                                   int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, label_weight, g_rows);
+  const at::Tensor lse_c = lse.to(at::kFloat).contiguous();
+  TORCH_CHECK_VALUE(lse_c.numel() == n, "kge_amd: lse must have one entry per row");
+  at::Tensor lb;
+  if (label_bias.has_value() && label_bias->defined()) {
+    lb = label_bias->to(at::kFloat).contiguous();
+    TORCH_CHECK_VALUE(lb.numel() == n, "kge_amd: label_bias must have one entry per row");
+  }
+  at::Tensor g_a = empty_f32({n, t.dim}, ent), g_p = empty_f32({n, t.rel_dim}, ent), g_t = empty_f32({t.num_ent, t.dim}, ent);
+  check(kge_kl_f32_bwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(), l.w,
+                       lb.defined() ? lb.data_ptr<float>() : nullptr, lse_c.data_ptr<float>(), l.g, (float)g_scalar,
+                       g_a.data_ptr<float>(), g_p.data_ptr<float>(), g_t.data_ptr<float>(),
+                       ce_dist_ws(workspace, workspace_bytes), workspace_bytes, stream_of(ent)),
+        "kge_kl_f32_bwd");
+  return {g_a, g_p, g_t};
+}
+
+at::Tensor bce_f32_fwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t direction,
+                       const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr, const at::Tensor& col,
+                       double offset, const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, c10::nullopt, c10::nullopt);
+  at::Tensor loss_rows = empty_f32({n}, ent);
+  check(kge_bce_f32_fwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(),
+                        (float)offset, loss_rows.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes),
+                        workspace_bytes, stream_of(ent)),
+        "kge_bce_f32_fwd");
+  return loss_rows;
+}
+
+std::vector<at::Tensor> bce_f32_bwd(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm,
+                                    int64_t direction, const at::Tensor& a, const at::Tensor& p, const at::Tensor& rowptr,
+                                    const at::Tensor& col, double offset, const c10::optional<at::Tensor>& g_rows,
+                                    double g_scalar, const at::Tensor& workspace, int64_t workspace_bytes) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep, &n), pi = index_of(p, ent, keep, &n);
+  const DistLabels l = dist_labels(ent, n, rowptr, col, c10::nullopt, g_rows);
+  at::Tensor g_a = empty_f32({n, t.dim}, ent), g_p = empty_f32({n, t.rel_dim}, ent), g_t = empty_f32({t.num_ent, t.dim}, ent);
+  check(kge_bce_f32_bwd(&t, (int)direction, ai, pi, n, l.rowptr.data_ptr<int64_t>(), l.col.data_ptr<int64_t>(),
+                        (float)offset, l.g, (float)g_scalar, g_a.data_ptr<float>(), g_p.data_ptr<float>(),
+                        g_t.data_ptr<float>(), ce_dist_ws(workspace, workspace_bytes), workspace_bytes, stream_of(ent)),
+        "kge_bce_f32_bwd");
+  return {g_a, g_p, g_t};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -426,4 +511,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("kl_dist_bwd", &kl_dist_bwd, "its backward: (g_a, g_p, g_entities)");
   mod.def("bce_dist_fwd", &bce_dist_fwd, "KvsAll bce loss of TransE / RotatE without a score matrix: loss_rows");
   mod.def("bce_dist_bwd", &bce_dist_bwd, "its backward: (g_a, g_p, g_entities)");
+  mod.def("multilabel_f32_workspace_bytes", &multilabel_f32_workspace_bytes);
+  mod.def("kl_f32_fwd", &kl_f32_fwd, "KvsAll kl loss of float32 ComplEx / DistMult without a score matrix: (loss_rows, lse)");
+  mod.def("kl_f32_bwd", &kl_f32_bwd, "its backward (label_bias: the uniform term of smoothed labels): (g_a, g_p, g_entities)");
+  mod.def("bce_f32_fwd", &bce_f32_fwd, "KvsAll bce loss of float32 ComplEx / DistMult without a score matrix: loss_rows");
+  mod.def("bce_f32_bwd", &bce_f32_bwd, "its backward: (g_a, g_p, g_entities)");
 }

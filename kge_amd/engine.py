@@ -1770,6 +1770,148 @@ def bce_dist_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: f
     return g_a, g_p, g_t
 
 
+# ---- KvsAll losses of ComplEx / DistMult on float32 tables (kge_kl_f32_* / kge_bce_f32_*): the CSR of the distance
+# twins above, the tables and chunk widths of ce_f32_fwd / ce_f32_bwd -----------------------------------------------------
+def multilabel_f32_supported(t: Tables) -> bool:
+    """Can the fused KvsAll losses of float32 ComplEx / DistMult tables run (kge_multilabel_f32_workspace_bytes > 0):
+    float32, dim % 8 == 0, 16-byte aligned rows, on a GPU?"""
+    if not t.ent.is_cuda:
+        return False
+    return _lib.lib().kge_multilabel_f32_workspace_bytes(ctypes.byref(t.c()), 1, 0) > 0
+
+
+def _ml_f32_args(t: Tables, a, p, lbl_rowptr, lbl_col, chunk_cols, what, per_row=()):
+    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths, the CSR,
+    the lengths of the `per_row` vectors ((tensor or None, name) pairs)."""
+    chunk_cols = int(chunk_cols)
+    if chunk_cols < 0 or chunk_cols % 128:
+        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 128, got {chunk_cols}")
+    if t.scorer not in (_lib.COMPLEX, _lib.DISTMULT) or t.ent.dtype != torch.float32 or t.rel.dtype != torch.float32:
+        raise RuntimeError(f"kge_amd: {what}: ComplEx / DistMult on float32 tables only "
+                           "(bf16 tables: kl_fwd / bce_fwd; TransE / RotatE: kl_dist_fwd / bce_dist_fwd)")
+    if t.ent.shape[1] % 8:
+        raise RuntimeError(f"kge_amd: {what}: the dimension must be a multiple of 8, got {t.ent.shape[1]}")
+    keep = []
+    ixs = tuple(_index(x, t.device, keep) for x in (a, p))
+    n = _same_len(keep[:2], what)
+    if not torch.is_tensor(lbl_rowptr) or not torch.is_tensor(lbl_col) or lbl_rowptr.dim() != 1 or lbl_col.dim() != 1:
+        raise ValueError(f"kge_amd: {what}: the labels are a CSR of two 1-d tensors (rowptr [n + 1], col [nnz])")
+    if lbl_rowptr.is_floating_point() or lbl_col.is_floating_point():
+        raise TypeError(f"kge_amd: {what}: the label CSR holds integers")
+    if lbl_rowptr.numel() != n + 1:
+        raise ValueError(f"kge_amd: {what}: label rowptr has {lbl_rowptr.numel()} entries for {n} rows")
+    for x, name in per_row:
+        if x is not None and x.numel() != n:
+            raise ValueError(f"kge_amd: {what}: {name} has {x.numel()} entries for {n} rows")
+    _require_gpu(t.ent, "entity table")
+    rp, cl = _csr64(lbl_rowptr, lbl_col, t.device)
+    return ixs, n, chunk_cols, rp, cl, keep
+
+
+def _ml_f32_workspace(tc, n, chunk_cols, device, st):
+    """(ptr, bytes): the per-(device, stream) scratch of kge_kl_f32_* / kge_bce_f32_*; `bytes` is exactly what the
+    chunk width asks for (the backward derives its chunk width from it), the buffer may be larger.  The backward leaves
+    the label bits zero and nothing else needs a value: no initialisation."""
+    need = _lib.lib().kge_multilabel_f32_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
+    if need <= 0:
+        raise RuntimeError("kge_kl_f32_* / kge_bce_f32_*: float32 ComplEx / DistMult tables, dim % 8 == 0, "
+                           "16-byte aligned rows only")
+    key = (device.index, st, "ml_f32")
+    buf = _WORKSPACES.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
+    return buf.data_ptr(), need
+
+
+def kl_f32_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, label_weight=None, chunk_cols: int = 0):
+    """kl_fwd for ComplEx / DistMult on float32 tables (kge_kl_f32_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
+    a = s) / score_po ('po': a = o) against all entities with the rows' labels as an int64 CSR (ids in any order), no
+    [n, E] matrix.  label_weight [n]: loss_rows[i] = lse[i] - label_weight[i] * (sum of row i's label scores)."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_f32_fwd",
+                                                         ((label_weight, "label_weight"),))
+    lw = _ml_dist_rows(label_weight, n, t.device, "kl_f32_fwd", "label_weight")
+    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
+    if n == 0:
+        return loss_rows, lse
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_kl_f32_fwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
+            None if lw is None else lw.data_ptr(), loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_kl_f32_fwd")
+    return loss_rows, lse
+
+
+def kl_f32_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, lse, g_rows=None, g_scalar: float = 1.0,
+               label_weight=None, label_bias=None, chunk_cols: int = 0):
+    """Backward of kl_f32_fwd (kge_kl_f32_bwd): (g_a [n, d], g_p [n, d], g_entities [E, d]).  label_bias [n]: b_i is
+    subtracted at every column (the uniform term of smoothed labels: the gradient of loss_rows[i] - b_i sum_j score_ij).
+    chunk_cols: entity columns per chunk (a multiple of 128; 0 = the library's default, a gradient chunk of at most
+    32 MB)."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(
+        t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_f32_bwd",
+        ((lse, "lse"), (g_rows, "g_rows"), (label_weight, "label_weight"), (label_bias, "label_bias")))
+    d, dr = t.ent.shape[1], t.rel.shape[1]
+    lse = _ml_dist_rows(lse, n, t.device, "kl_f32_bwd", "lse")
+    gr = _ml_dist_rows(g_rows, n, t.device, "kl_f32_bwd", "g_rows")
+    lw = _ml_dist_rows(label_weight, n, t.device, "kl_f32_bwd", "label_weight")
+    lb = _ml_dist_rows(label_bias, n, t.device, "kl_f32_bwd", "label_bias")
+    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
+    if n == 0:
+        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
+    g_t = _empty((t.num_ent, d), t.device)
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_kl_f32_bwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
+            None if lw is None else lw.data_ptr(), None if lb is None else lb.data_ptr(), lse.data_ptr(),
+            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(),
+            ws, wsb, st), "kge_kl_f32_bwd")
+    return g_a, g_p, g_t
+
+
+def bce_f32_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, chunk_cols: int = 0):
+    """bce_fwd for ComplEx / DistMult on float32 tables (kge_bce_f32_fwd): loss_rows [n], the sum over ALL entities of
+    BCEWithLogits(score + offset, multi-hot labels), no [n, E] matrix."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_f32_fwd")
+    loss_rows = _empty((n,), t.device)
+    if n == 0:
+        return loss_rows
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_bce_f32_fwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
+            loss_rows.data_ptr(), ws, wsb, st), "kge_bce_f32_fwd")
+    return loss_rows
+
+
+def bce_f32_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, g_rows=None,
+                g_scalar: float = 1.0, chunk_cols: int = 0):
+    """Backward of bce_f32_fwd (kge_bce_f32_bwd): (g_a [n, d], g_p [n, d], g_entities [E, d])."""
+    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_f32_bwd",
+                                                         ((g_rows, "g_rows"),))
+    d, dr = t.ent.shape[1], t.rel.shape[1]
+    gr = _ml_dist_rows(g_rows, n, t.device, "bce_f32_bwd", "g_rows")
+    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
+    if n == 0:
+        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
+    g_t = _empty((t.num_ent, d), t.device)
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
+        _lib.check(_lib.lib().kge_bce_f32_bwd(
+            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
+            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(),
+            ws, wsb, st), "kge_bce_f32_bwd")
+    return g_a, g_p, g_t
+
+
 def ce_emb_fwd(t: Tables, direction: str, a_rows, p_rows, label):
     """ce_fwd with dense bf16 query rows against ALL rows of t.ent (the per-shard step of entity-sharded
     1vsAll training): (loss_rows [n] -- NaN where `label` (local row ids) is outside [0, num_ent) --, lse [n])."""

@@ -8,8 +8,8 @@ from kge.model.rotate import RotatE as _RefRotatE
 from kge.model.transe import TransE as _RefTransE
 
 from .. import engine
-from ..model import (BF16Shadow, _FusedBCEDist, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32, _FusedKLDist,
-                     _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
+from ..model import (BF16Shadow, _FusedBCEDist, _FusedBCEF32, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32,
+                     _FusedKLDist, _FusedKLF32, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
                      bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable)
 
 
@@ -278,6 +278,8 @@ class _FusedScoring:
 
     # `hip_1vsAll.fused_f32_loss: true` (set by HipTrainingJob1vsAll; false by default): the 1vsAll kl loss of hip_complex /
     # hip_distmult scoring in float32 without an [n, E] matrix (kge_ce_f32_fwd / kge_ce_f32_bwd).
+    # `hip_KvsAll.fused_f32_loss: true` (set by HipTrainingJobKvsAll): the same for the KvsAll kl and bce losses, WITH
+    # label smoothing -- these scores are linear in the target row (kge_kl_f32_* / kge_bce_f32_*).
     _fused_f32_loss = False
 
     def _ce_f32_tables(self):
@@ -299,6 +301,25 @@ class _FusedScoring:
             return _FusedCEDist.apply(direction, *self._w(), a, p, label, td)
         tf = self._ce_f32_tables()
         return None if tf is None else _FusedCEF32.apply(direction, *self._w(), a, p, label, tf)
+
+    def _kl_f32(self, direction, a, p, lbl_rowptr, lbl_col, label_smoothing):
+        """kl_loss_sp / kl_loss_po where neither _ce_tables() nor _ml_dist_tables() applies: the float32 ComplEx /
+        DistMult loss (kl_fused around _FusedKLF32: label smoothing included), or None."""
+        tf = self._ce_f32_tables()
+        if tf is None:
+            return None
+        ent, rel = self._w()
+        return kl_fused(self._scorer.name, self._scorer._norm, direction, ent, rel, a, p, lbl_rowptr, lbl_col,
+                        float(label_smoothing), tf, _FusedKLF32)
+
+    def _bce_f32(self, direction, a, p, lbl_rowptr, lbl_col, offset, label_smoothing):
+        """The same for bce_loss_sp / bce_loss_po (bce_fused around _FusedBCEF32), or None."""
+        tf = self._ce_f32_tables()
+        if tf is None:
+            return None
+        ent, rel = self._w()
+        return bce_fused(self._scorer.name, self._scorer._norm, direction, ent, rel, a, p, lbl_rowptr, lbl_col,
+                         float(offset), float(label_smoothing), tf, _FusedBCEF32)
 
     def _rank_tables(self):
         """The tables HipEntityRankingJob counts on (kge_score_rank_sp_po: scoring + _filter_and_rank counts in one
@@ -364,7 +385,9 @@ class _FusedScoring:
         t = self._ce_tables()
         if t is None:
             td = self._ml_dist_tables(label_smoothing)
-            return None if td is None else _FusedKLDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, None, td)
+            if td is not None:
+                return _FusedKLDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, None, td)
+            return self._kl_f32("sp", s, p, lbl_rowptr, lbl_col, label_smoothing)
         ent, rel = self._w()
         return kl_fused(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, lbl_rowptr, lbl_col,
                         float(label_smoothing), t)
@@ -374,7 +397,9 @@ class _FusedScoring:
         t = self._ce_tables()
         if t is None:
             td = self._ml_dist_tables(label_smoothing)
-            return None if td is None else _FusedKLDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, None, td)
+            if td is not None:
+                return _FusedKLDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, None, td)
+            return self._kl_f32("po", o, p, lbl_rowptr, lbl_col, label_smoothing)
         ent, rel = self._w()
         return kl_fused(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, lbl_rowptr, lbl_col,
                         float(label_smoothing), t)
@@ -386,7 +411,9 @@ class _FusedScoring:
         t = self._ce_tables()
         if t is None:
             td = self._ml_dist_tables(label_smoothing)
-            return None if td is None else _FusedBCEDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, float(offset), td)
+            if td is not None:
+                return _FusedBCEDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, float(offset), td)
+            return self._bce_f32("sp", s, p, lbl_rowptr, lbl_col, offset, label_smoothing)
         ent, rel = self._w()
         return bce_fused(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, lbl_rowptr, lbl_col,
                          float(offset), float(label_smoothing), t)
@@ -396,7 +423,9 @@ class _FusedScoring:
         t = self._ce_tables()
         if t is None:
             td = self._ml_dist_tables(label_smoothing)
-            return None if td is None else _FusedBCEDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, float(offset), td)
+            if td is not None:
+                return _FusedBCEDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, float(offset), td)
+            return self._bce_f32("po", o, p, lbl_rowptr, lbl_col, offset, label_smoothing)
         ent, rel = self._w()
         return bce_fused(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, lbl_rowptr, lbl_col,
                          float(offset), float(label_smoothing), t)

@@ -42,7 +42,8 @@ def _model_takes_dist_loss(model) -> bool:
 
 def _model_takes_f32_loss(model) -> bool:
     """The fused 1vsAll kl loss of hip_complex / hip_distmult scoring in float32 (`hip_1vsAll.fused_f32_loss: true`):
-    decided once per subbatch; the two one-sided calls loss_sp / loss_po, no captured step, no two-sided launch."""
+    decided once per subbatch; the two one-sided calls loss_sp / loss_po, no captured step, no two-sided launch.  The
+    same question for `hip_KvsAll.fused_f32_loss` (kl_loss_* / bce_loss_* per query type, label smoothing included)."""
     f = getattr(model, "_ce_f32_tables", None)
     return f is not None and f() is not None
 
@@ -73,8 +74,9 @@ def _set_fused_dist_loss(job, key):
 def _has_repeated_labels(coords) -> bool:
     """Does a batch's `label_coords` ([nnz, 2]: batch row, label) hold the same (row, label) twice?  A training split
     that repeats a triple does that: the reference's dense label row then carries a 2, while kge_kl_dist_* /
-    kge_bce_dist_* take ids that are unique per row (the forward would count the id twice, the backward's bit mask
-    once).  One sort of nnz keys and one host read per subbatch, on the fused_dist_loss path only."""
+    kge_bce_dist_* (and kge_kl_f32_* / kge_bce_f32_*) take ids that are unique per row (the forward would count the id
+    twice, the backward's bit mask once).  One sort of nnz keys and one host read per subbatch, on the fused_dist_loss
+    and fused_f32_loss paths only."""
     if coords.shape[0] < 2:
         return False
     c = coords.long()
@@ -364,7 +366,8 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
     kge_bce_fwd: scores never written; labels as a CSR cut out of the batch's `label_coords`); s_o
     queries and every other configuration run the reference's code.  `hip_KvsAll.fused_dist_loss: true`: hip_transe /
     hip_rotate on float32 tables take the same hooks without label smoothing (kge_kl_dist_* / kge_bce_dist_*), one call
-    per query type, no captured step."""
+    per query type, no captured step.  `hip_KvsAll.fused_f32_loss: true`: hip_complex / hip_distmult scoring in float32
+    take them too, with or without label smoothing (kge_kl_f32_* / kge_bce_f32_*), again one call per query type."""
 
     def __init__(self, config, dataset, parent_job=None, model=None, forward_only=False):
         super().__init__(config, dataset, parent_job, model=model, forward_only=forward_only)
@@ -375,6 +378,7 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         self.graph_batches = 0        # batches that went through the GraphedStep (replayed or eager)
         self._skip_optimizer_step = False
         _set_fused_dist_loss(self, "hip_KvsAll")
+        _set_fused_f32_loss(self, "hip_KvsAll")
         if self.__class__ == HipTrainingJobKvsAll:
             for f in Job.job_created_hooks:
                 f(self)
@@ -469,6 +473,8 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         # only -- no captured step, no multilabel_loss_sp_po
         dist = not takes and float(self.label_smoothing) == 0.0 and _model_takes_dist_loss(self.model)
         # (a batch with a repeated (query, label) pair -- a split that repeats a triple -- takes the composed path)
+        # hip_KvsAll.fused_f32_loss (hip_complex / hip_distmult in float32, label smoothing included): the same per-type loop
+        dist = dist or (not takes and _model_takes_f32_loss(self.model))
         dist = dist and self._fused_ok() and not _has_repeated_labels(batch["label_coords"])
         if not self._fused_ok() or not (takes or dist):
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)

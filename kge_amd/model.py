@@ -115,7 +115,9 @@ class KgeModel(torch.nn.Module):
                  score_dtype=None, fused_dist_loss: bool = False, fused_f32_loss: bool = False):
         super().__init__()
         # fused_f32_loss=True (ComplEx / DistMult, float32 parameters on a GPU scored in float32, dim % 8 == 0): loss_sp /
-        # loss_po / loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_f32_fwd / _bwd); off by default
+        # loss_po / loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_f32_fwd / _bwd), and kl_loss_sp /
+        # kl_loss_po / bce_loss_sp / bce_loss_po with or without label smoothing (kge_kl_f32_* / kge_bce_f32_*); off by
+        # default
         self.fused_f32_loss = bool(fused_f32_loss)
         # fused_dist_loss=True (TransE / RotatE, float32 parameters on a GPU, l_norm 1 or 2): loss_sp / loss_po /
         # loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_dist_fwd / _bwd), and kl_loss_sp / kl_loss_po /
@@ -328,9 +330,10 @@ class KgeModel(torch.nn.Module):
         y = torch.nn.functional.normalize(labels, p=1, dim=1)
         return torch.nn.functional.kl_div(torch.log_softmax(scores, dim=1), y, reduction="none").sum(dim=1)
 
-    def _kl_fused(self, direction: str, a: Tensor, p: Tensor, rowptr: Tensor, col: Tensor, eps: float, t) -> Tensor:
+    def _kl_fused(self, direction: str, a: Tensor, p: Tensor, rowptr: Tensor, col: Tensor, eps: float, t,
+                  fused_fn=None) -> Tensor:
         return kl_fused(self._scorer.name, self._scorer._norm, direction, self._entity_embedder.weight,
-                        self._relation_embedder.weight, a, p, rowptr, col, eps, t)
+                        self._relation_embedder.weight, a, p, rowptr, col, eps, t, fused_fn)
 
     def kl_loss_sp(self, s: Tensor, p: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
                    label_smoothing: float = 0.0) -> Tensor:
@@ -343,6 +346,9 @@ class KgeModel(torch.nn.Module):
         if td is not None:
             return _FusedKLDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p,
                                       lbl_rowptr, lbl_col, None, td)
+        tf = self._ce_f32_tables()
+        if tf is not None:
+            return self._kl_fused("sp", s, p, lbl_rowptr, lbl_col, float(label_smoothing), tf, _FusedKLF32)
         return self._kl_composed(self.score_sp(s, p), lbl_rowptr, lbl_col, label_smoothing)
 
     def kl_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
@@ -354,6 +360,9 @@ class KgeModel(torch.nn.Module):
         if td is not None:
             return _FusedKLDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p,
                                       lbl_rowptr, lbl_col, None, td)
+        tf = self._ce_f32_tables()
+        if tf is not None:
+            return self._kl_fused("po", o, p, lbl_rowptr, lbl_col, float(label_smoothing), tf, _FusedKLF32)
         return self._kl_composed(self.score_po(p, o), lbl_rowptr, lbl_col, label_smoothing)
 
     def multilabel_loss_sp_po(self, kind: str, s: Tensor, p_sp: Tensor, rowptr_sp: Tensor, col_sp: Tensor, o: Tensor,
@@ -401,6 +410,11 @@ class KgeModel(torch.nn.Module):
         if td is not None:
             return _FusedBCEDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p,
                                        lbl_rowptr, lbl_col, float(offset), td)
+        tf = self._ce_f32_tables()
+        if tf is not None:
+            return bce_fused(self._scorer.name, self._scorer._norm, "sp", self._entity_embedder.weight,
+                             self._relation_embedder.weight, s, p, lbl_rowptr, lbl_col, float(offset),
+                             float(label_smoothing), tf, _FusedBCEF32)
         return self._bce_composed(self.score_sp(s, p), lbl_rowptr, lbl_col, offset, label_smoothing)
 
     def bce_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor, offset: float = 0.0,
@@ -414,6 +428,11 @@ class KgeModel(torch.nn.Module):
         if td is not None:
             return _FusedBCEDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p,
                                        lbl_rowptr, lbl_col, float(offset), td)
+        tf = self._ce_f32_tables()
+        if tf is not None:
+            return bce_fused(self._scorer.name, self._scorer._norm, "po", self._entity_embedder.weight,
+                             self._relation_embedder.weight, o, p, lbl_rowptr, lbl_col, float(offset),
+                             float(label_smoothing), tf, _FusedBCEF32)
         return self._bce_composed(self.score_po(p, o), lbl_rowptr, lbl_col, offset, label_smoothing)
 
     def score_so(self, s: Tensor, o: Tensor, p: Tensor = None) -> Tensor:
@@ -789,6 +808,56 @@ class _FusedBCEDist(torch.autograd.Function):
         return None, ge, gr, None, None, None, None, None, None, None
 
 
+class _FusedKLF32(torch.autograd.Function):
+    """_FusedKL for ComplEx / DistMult on FLOAT32 tables (kge_kl_f32_fwd / kge_kl_f32_bwd): `tables` are the parameters
+    themselves, labels an int64 CSR (rowptr [n + 1], col [nnz]; ids in any order).  _FusedKL's signature -- these scores
+    are linear in the target row, so label_bias (the uniform term of smoothed labels) is taken inside the gradient
+    kernel as there: kl_fused composes label smoothing around either.  The backward walks the entity columns in chunks
+    of `chunk_cols` (0: the library's default)."""
+
+    @staticmethod
+    def forward(ctx, direction, ent, rel, a, p, rowptr, col, label_weight, label_bias, tables, chunk_cols=0):
+        loss_rows, lse = engine.kl_f32_fwd(tables, direction, a, p, rowptr, col, label_weight, chunk_cols)
+        ctx.t, ctx.direction, ctx.chunk_cols = tables, direction, chunk_cols
+        ctx.idx = (a, p, rowptr, col, label_weight, label_bias)
+        ctx.rel_shape = rel.shape
+        ctx.save_for_backward(lse)
+        return loss_rows
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        a, p, rowptr, col, label_weight, label_bias = ctx.idx
+        (lse,) = ctx.saved_tensors
+        g_a, g_p, ge = engine.kl_f32_bwd(ctx.t, ctx.direction, a, p, rowptr, col, lse, g_rows=g_rows.contiguous(),
+                                         label_weight=label_weight, label_bias=label_bias, chunk_cols=ctx.chunk_cols)
+        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
+        _scatter_rows(gr, p, g_p)
+        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
+        return None, ge, gr, None, None, None, None, None, None, None, None
+
+
+class _FusedBCEF32(torch.autograd.Function):
+    """_FusedBCE for ComplEx / DistMult on FLOAT32 tables (kge_bce_f32_fwd / kge_bce_f32_bwd); _FusedBCE's signature
+    (bce_fused composes label smoothing around either)."""
+
+    @staticmethod
+    def forward(ctx, direction, ent, rel, a, p, rowptr, col, offset, tables, chunk_cols=0):
+        loss_rows = engine.bce_f32_fwd(tables, direction, a, p, rowptr, col, offset, chunk_cols)
+        ctx.t, ctx.direction, ctx.idx, ctx.offset, ctx.chunk_cols = tables, direction, (a, p, rowptr, col), offset, chunk_cols
+        ctx.rel_shape = rel.shape
+        return loss_rows
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        a, p, rowptr, col = ctx.idx
+        g_a, g_p, ge = engine.bce_f32_bwd(ctx.t, ctx.direction, a, p, rowptr, col, ctx.offset,
+                                          g_rows=g_rows.contiguous(), chunk_cols=ctx.chunk_cols)
+        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
+        _scatter_rows(gr, p, g_p)
+        _scatter_rows(ge, a, g_a)
+        return None, ge, gr, None, None, None, None, None, None, None
+
+
 class _FusedCE2(torch.autograd.Function):
     """Both directions of a 1vsAll batch (kge_ce_sp_po_fwd / _bwd): [2n] loss rows, sp_ queries
     first; one scoring launch and one pair of gradient products for the whole batch."""
@@ -956,7 +1025,7 @@ class _FusedMultiLabel2(torch.autograd.Function):
 
 
 def kl_fused(name: str, l_norm, direction: str, ent: Tensor, rel: Tensor, a: Tensor, p: Tensor, rowptr: Tensor,
-             col: Tensor, eps: float, t) -> Tensor:
+             col: Tensor, eps: float, t, fused_fn=None) -> Tensor:
     """The fused KvsAll KL loss with label smoothing `eps` (train_KvsAll.py:260-266: labels =
     (1 - eps) * multi_hot + 1/E before loss.py:208-213 normalises them).  The smoothed label row is a_i on
     row i's k_i labels and b_i elsewhere (Z_i = (1 - eps) k_i + 1, a_i = (1 - eps + 1/E) / Z_i,
@@ -965,16 +1034,19 @@ def kl_fused(name: str, l_norm, direction: str, ent: Tensor, rel: Tensor, a: Ten
                - b_i * sum_j score_ij                            <- linear in the entity table (ComplEx and
                                                                     DistMult, the fused path's scorers): ONE
                                                                     [n, 1] score against the table's column sum
-               + k_i a_i log a_i + (E - k_i) b_i log b_i         <- constant."""
+               + k_i a_i log a_i + (E - k_i) b_i log b_i         <- constant.
+    fused_fn: the autograd function of the fused part, _FusedKL (bf16 tables; the default) or _FusedKLF32 (float32
+    tables: `t` are then the parameters themselves)."""
+    fused_fn = fused_fn or _FusedKL
     if eps == 0.0:
-        return _FusedKL.apply(direction, ent, rel, a, p, rowptr, col, None, None, t)
+        return fused_fn.apply(direction, ent, rel, a, p, rowptr, col, None, None, t)
     E = ent.shape[0]
     k = (rowptr[1:] - rowptr[:-1]).to(device=ent.device, dtype=torch.float32)
     Z = (1.0 - eps) * k + 1.0
     a_w, b_w = (1.0 - eps + 1.0 / E) / Z, (1.0 / E) / Z
     # the GRADIENT of the uniform term is taken inside the gradient kernel (label_bias = b_i: b_i is subtracted at
     # every column next to the softmax), so only its VALUE is computed here
-    fused = _FusedKL.apply(direction, ent, rel, a, p, rowptr, col, (a_w - b_w).contiguous(), b_w.contiguous(), t)
+    fused = fused_fn.apply(direction, ent, rel, a, p, rowptr, col, (a_w - b_w).contiguous(), b_w.contiguous(), t)
     with torch.no_grad():
         s_all = _sum_of_scores_value(name, direction, ent, rel, a, p)
     const = k * a_w * torch.log(a_w) + (E - k) * b_w * torch.log(b_w)
@@ -1030,14 +1102,15 @@ def _sum_of_scores_value(name: str, direction: str, ent: Tensor, rel: Tensor, a:
 
 
 def bce_fused(name: str, l_norm, direction: str, ent: Tensor, rel: Tensor, a: Tensor, p: Tensor, rowptr: Tensor,
-              col: Tensor, offset: float, eps: float, t) -> Tensor:
+              col: Tensor, offset: float, eps: float, t, fused_fn=None) -> Tensor:
     """The fused KvsAll BCE loss with label smoothing `eps` (train_KvsAll.py:260-266; loss.py:137-159 with
     bce_type None).  With x_ij = score_ij + offset and y_ij = (1 - eps) [j in labels_i] + 1/E,
         sum_j softplus(x_ij) - y_ij x_ij
           = [sum_j softplus(x_ij) - sum_{labels} x_ij]      <- kge_bce_fwd, fused, scores never written
             + eps * sum_{labels} x_ij                       <- nnz(labels) spo scores (kge_score_spo)
-            - (1/E) * sum_j x_ij                            <- one [n, 1] score against the column sum."""
-    fused = _FusedBCE.apply(direction, ent, rel, a, p, rowptr, col, offset, t)
+            - (1/E) * sum_j x_ij                            <- one [n, 1] score against the column sum.
+    fused_fn: _FusedBCE (bf16 tables; the default) or _FusedBCEF32 (float32 tables)."""
+    fused = (fused_fn or _FusedBCE).apply(direction, ent, rel, a, p, rowptr, col, offset, t)
     if eps == 0.0:
         return fused
     n, E = a.shape[0], ent.shape[0]

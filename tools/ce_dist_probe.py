@@ -2,11 +2,13 @@
 torch.cuda.max_memory_allocated, l_norm 1 and 2, at E = 14,541 (FB15k-237) and E = 574,311 (a one-eighth Wikidata5M
 shard), n = 512, d = 128.  --mode kvsall_kl / kvsall_bce: the KvsAll step instead (kl_loss_sp + kl_loss_po or
 bce_loss_sp + bce_loss_po, no label smoothing) with 0..16 (about 8) random labels per row.  --mode f32_1vsall: the
-1vsAll step of float32 ComplEx / DistMult with fused_f32_loss on / off (kge_ce_f32_*).
+1vsAll step of float32 ComplEx / DistMult with fused_f32_loss on / off (kge_ce_f32_*).  --mode f32_kvsall_kl /
+f32_kvsall_bce: their KvsAll step (kge_kl_f32_* / kge_bce_f32_*) with the same label sets.
 
     python tools/ce_dist_probe.py [--mode 1vsall] [--out profiles/ce_dist_probe.txt] [--steps 10] [--limit 120]
     python tools/ce_dist_probe.py --mode kvsall_kl --out profiles/multilabel_dist_probe_kl.txt
     python tools/ce_dist_probe.py --mode f32_1vsall --out profiles/ce_f32_probe.txt
+    python tools/ce_dist_probe.py --mode f32_kvsall_kl --out profiles/ml_f32_probe.txt
 
 The parent never touches the GPU: every (shape, scorer, norm, path) step runs in a child process of its own under its
 own time limit, and after a child that fails in any way other than running out of memory nothing more is started."""
@@ -26,13 +28,13 @@ def one(name, l_norm, E, R, n, d, fused, steps, mode="1vsall"):
     from kge_amd import model as km
     dev = "cuda:0"
     torch.manual_seed(0)
-    opt = {"fused_f32_loss": fused} if mode == "f32_1vsall" else {"fused_dist_loss": fused}
+    opt = {"fused_f32_loss": fused} if mode.startswith("f32_") else {"fused_dist_loss": fused}
     m = km.create(name, E, R, d, l_norm=l_norm, device=dev, **opt).train()
     g = torch.Generator().manual_seed(1)
     s, p, o = (torch.randint(hi, (n,), generator=g).to(dev) for hi in (E, R, E))
 
     csr = []
-    for _ in range(2 if mode.startswith("kvsall") else 0):  # label CSRs of the sp_ and the _po queries: 0..16 labels per row
+    for _ in range(2 if "kvsall" in mode else 0):  # label CSRs of the sp_ and the _po queries: 0..16 labels per row
         k = torch.randint(0, 17, (n,), generator=g)
         rowptr = torch.zeros(n + 1, dtype=torch.int64)
         rowptr[1:] = torch.cumsum(k, 0)
@@ -44,7 +46,7 @@ def one(name, l_norm, E, R, n, d, fused, steps, mode="1vsall"):
         if mode in ("1vsall", "f32_1vsall"):
             (m.loss_sp(s, p, o).sum() / n).backward()
             (m.loss_po(p, o, s).sum() / n).backward()
-        elif mode == "kvsall_kl":
+        elif mode in ("kvsall_kl", "f32_kvsall_kl"):
             (m.kl_loss_sp(s, p, *csr[0]).sum() / n).backward()
             (m.kl_loss_po(p, o, *csr[1]).sum() / n).backward()
         else:
@@ -69,7 +71,7 @@ def one(name, l_norm, E, R, n, d, fused, steps, mode="1vsall"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", default="1vsall", choices=("1vsall", "kvsall_kl", "kvsall_bce", "f32_1vsall"))
+    ap.add_argument("--mode", default="1vsall", choices=("1vsall", "kvsall_kl", "kvsall_bce", "f32_1vsall", "f32_kvsall_kl", "f32_kvsall_bce"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--limit", type=int, default=120, help="seconds per child")
@@ -78,7 +80,7 @@ def main():
     if a.one:
         name, l_norm, E, R, n, d, fused = a.one
         return one(name, float(l_norm), int(E), int(R), int(n), int(d), fused == "1", a.steps, a.mode)
-    f32 = a.mode == "f32_1vsall"
+    f32 = a.mode.startswith("f32_")
     lines = [f"# fused ({'fused_f32_loss' if f32 else 'fused_dist_loss'}=True) against composed {a.mode} step, both "
              f"directions, n and d below; {a.steps} timed steps after one warm-up",
              "scorer l_norm E n d path ms_per_step peak_MB"]
