@@ -507,6 +507,29 @@ int kge_embed(const kge_tables* t, kge_index ent_idx, int64_t n_ent, void* ent_o
 int kge_ns_bce_loss(const float* scores, int64_t ld, int64_t n, int64_t c, int kind, float offset, float temperature,
                     float* loss_rows, float* grad, int64_t ldg, void* stream);
 
+/* Every negative-sampling loss of LibKGE over one slot's scores, the positive and its negatives as TWO pieces: row i
+ * has x_0 = pos[i * pos_stride] and x_j = neg[i * neg_ld + j - 1], j = 1..K (a contiguous [n, 1 + K] block is the
+ * special case pos = scores, pos_stride = ld, neg = scores + 1, neg_ld = ld).  Forward and gradient in one launch, one
+ * wave per row, no atomics (two runs give the same bits):
+ *   kinds 0-2  the arithmetic of kge_ns_bce_loss, arg = offset                         kge/util/loss.py:153-186
+ *   kind 3 "kl"              lse_j(x_j) - x_0: KLDivWithSoftmaxKgeLoss on the label matrix "column 0 is 1"
+ *                            (0 log 0 = 0); d / d x_j = softmax(x)_j - [j = 0]         kge/util/loss.py:198-213
+ *   kind 4 "margin_ranking"  sum_{j>=1} clamp_min(-(x_0 - x_j) + arg, 0), arg = the margin (train.loss_arg), in
+ *                            float32 in torch's order; the subgradient is torch's: a negative with v_j >= 0 (the exact
+ *                            tie v_j = 0 INCLUDED) gets 1, the positive minus their count   kge/util/loss.py:236-252
+ *   kind 5 "soft_margin"     sum_j log(1 + exp(-t_j x_j)), t_0 = 1, t_j = -1, as max(z, 0) + log1p(exp(-|z|)): finite
+ *                            where the reference's float32 log(1 + exp(z)) overflows (z >~ 89);
+ *                            d / d x_j = -t_j sigmoid(-t_j x_j)                        kge/util/loss.py:221-224
+ *   kind 6 "se"              sum_j (x_j - y_j)^2, y_0 = 1, y_j = 0; d / d x_j = 2 (x_j - y_j)   kge/util/loss.py:272-274
+ * arg is ignored by kinds 3, 5 and 6, temperature by all but kind 2.
+ * loss_rows[i] = row i's term (the job's loss is their sum).  g_pos / g_neg: both NULL (no gradient) or both set:
+ * g_pos[i * g_pos_stride] = d (sum loss_rows) / d x_0 of row i, g_neg[i * g_neg_ld + j - 1] = ... / d x_j.
+ * KGE_ERR_INVALID_ARG: K < 1, an unknown kind, a NULL piece, one gradient pointer without the other, a leading
+ * dimension below K; n == 0 is KGE_OK. */
+int kge_ns_loss(const float* pos, int64_t pos_stride, const float* neg, int64_t neg_ld, int64_t n, int64_t K, int kind,
+                float arg, float temperature, float* loss_rows, float* g_pos, int64_t g_pos_stride, float* g_neg,
+                int64_t g_neg_ld, void* stream);
+
 /* The two row moves of the entity-sharded exchange (kge_amd/sharded.py: ShardedEntityTable.exchange_rows),
  * the id arithmetic evaluated inside the kernel, one launch each:
  *   kge_shard_gather   t->ent = THIS RANK's rows [lo, lo + t->num_ent) of the entity table.  For j < num_ids (1 or 2

@@ -104,6 +104,9 @@ int v8_launch_count(int which);
 int run_embed2(const EmbedJob& a, const EmbedJob& b, int rowbytes, int esize, hipStream_t st);
 int run_ns_bce(int kind, const float* scores, long long ld, long long n, long long c, float offset, float temp,
                float* loss_rows, float* grad, long long ldg, hipStream_t st);
+int run_ns_loss(int kind, const float* pos, long long pos_stride, const float* neg, long long neg_ld, long long n,
+                long long K, float arg, float temp, float* loss_rows, float* g_pos, long long g_pos_stride, float* g_neg,
+                long long g_neg_ld, hipStream_t st);
 int run_shard_rows(const ShardJob& a, const ShardJob& b, const ShardJob& c, int rowbytes01, int rowbytes2, int esize,
                    hipStream_t st);
 int run_rank(const float* scores, long long lds, long long n, long long c,
@@ -856,6 +859,20 @@ int kge_ns_bce_loss(const float* scores, int64_t ld, int64_t n, int64_t c, int k
   if (n > 0 && (!scores || !loss_rows)) return KGE_ERR_INVALID_ARG;
   if (kind != 0 && c < 2) return KGE_ERR_INVALID_ARG;  // the mean / adversarial forms need a negative
   return run_ns_bce(kind, scores, ld, n, c, offset, temperature, loss_rows, grad, ldg, (hipStream_t)stream);
+}
+
+int kge_ns_loss(const float* pos, int64_t pos_stride, const float* neg, int64_t neg_ld, int64_t n, int64_t K, int kind,
+                float arg, float temperature, float* loss_rows, float* g_pos, int64_t g_pos_stride, float* g_neg,
+                int64_t g_neg_ld, void* stream) {
+  KGE_RANGE();
+  if (n < 0 || K < 1 || kind < 0 || kind > 6 || neg_ld < K) return KGE_ERR_INVALID_ARG;
+  if ((g_pos == nullptr) != (g_neg == nullptr)) return KGE_ERR_INVALID_ARG;  // the gradient comes whole or not at all
+  if (g_neg && (g_neg_ld < K || (n > 1 && g_pos_stride < 1))) return KGE_ERR_INVALID_ARG;  // (rows must not overlap)
+  if (pos_stride < 0) return KGE_ERR_INVALID_ARG;
+  if (n == 0) return KGE_OK;
+  if (!pos || !neg || !loss_rows) return KGE_ERR_INVALID_ARG;
+  return run_ns_loss(kind, pos, pos_stride, neg, neg_ld, n, K, arg, temperature, loss_rows, g_pos, g_pos_stride, g_neg,
+                     g_neg_ld, (hipStream_t)stream);
 }
 
 int kge_shard_gather(const kge_tables* t, int64_t lo, const kge_index* ids, int num_ids, int64_t n, void* send,

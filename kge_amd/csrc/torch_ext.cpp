@@ -490,6 +490,31 @@ std::vector<at::Tensor> bce_f32_bwd(const at::Tensor& ent, const at::Tensor& rel
   return {g_a, g_p, g_t};
 }
 
+// ---- every negative-sampling loss over one slot's scores (kge_ns_loss): pos [n] of any stride, neg [n, K] with unit
+// inner stride (a slice of a wider matrix is fine).  -> (loss_rows [n], g_pos [n], g_neg [n, K]); the gradients are
+// undefined tensors (None in Python) without want_grad.
+std::vector<at::Tensor> ns_loss_parts(const at::Tensor& pos, const at::Tensor& neg, int64_t kind, double arg,
+                                      double temperature, bool want_grad) {
+  TORCH_CHECK(pos.is_cuda() && neg.is_cuda() && pos.get_device() == neg.get_device(),
+              "kge_amd: ns_loss takes GPU tensors on one device (no CPU path)");
+  TORCH_CHECK_VALUE(pos.scalar_type() == at::kFloat && neg.scalar_type() == at::kFloat && pos.dim() == 1 && neg.dim() == 2 &&
+                        neg.size(0) == pos.size(0) && neg.size(1) >= 1 && (neg.size(1) == 1 || neg.stride(1) == 1),
+                    "kge_amd: ns_loss takes float32 pos [n] and neg [n, K >= 1] with unit inner stride");
+  const int64_t n = neg.size(0), K = neg.size(1);
+  TORCH_CHECK_VALUE(n <= 1 || (pos.stride(0) >= 0 && neg.stride(0) >= K), "kge_amd: ns_loss: overlapping or reversed rows");
+  at::Tensor rows = empty_f32({n}, neg), g_pos, g_neg;
+  if (want_grad) {
+    g_pos = empty_f32({n}, neg);
+    g_neg = empty_f32({n, K}, neg);
+  }
+  check(kge_ns_loss(pos.data_ptr<float>(), n > 1 ? pos.stride(0) : 1, neg.data_ptr<float>(), n > 1 ? neg.stride(0) : K, n, K,
+                    (int)kind, (float)arg, (float)temperature, rows.data_ptr<float>(),
+                    want_grad ? g_pos.data_ptr<float>() : nullptr, 1, want_grad ? g_neg.data_ptr<float>() : nullptr, K,
+                    stream_of(neg)),
+        "kge_ns_loss");
+  return {rows, g_pos, g_neg};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -516,4 +541,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("kl_f32_bwd", &kl_f32_bwd, "its backward (label_bias: the uniform term of smoothed labels): (g_a, g_p, g_entities)");
   mod.def("bce_f32_fwd", &bce_f32_fwd, "KvsAll bce loss of float32 ComplEx / DistMult without a score matrix: loss_rows");
   mod.def("bce_f32_bwd", &bce_f32_bwd, "its backward: (g_a, g_p, g_entities)");
+  mod.def("ns_loss_parts", &ns_loss_parts,
+          "negative-sampling loss of one slot from (pos [n], neg [n, K]): (loss_rows, g_pos, g_neg)");
 }

@@ -21,7 +21,7 @@ from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT
                    SCORERS, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
 
 __all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "shared_samples",
-           "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
+           "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
            "FLAG_SPLIT_QUERY", "reserve_cus", "Queries", "build_queries", "score_queries", "ScorePipeline"]
 
 
@@ -1008,6 +1008,69 @@ def ns_bce_loss(scores: torch.Tensor, kind: str, offset: float = 0.0, temperatur
             scores.data_ptr(), scores.stride(0) if n > 1 else c, n, c, NS_BCE_KINDS[kind], float(offset),
             float(temperature), rows.data_ptr(), None if grad is None else grad.data_ptr(), c,
             _stream_handle(scores.device)), "kge_ns_bce_loss")
+    return rows, grad
+
+
+# kge_ns_loss's kinds: the bce family (NS_BCE_KINDS, the same arithmetic) and LibKGE's other negative-sampling losses
+NS_LOSS_KINDS = dict(NS_BCE_KINDS, kl=3, margin_ranking=4, soft_margin=5, se=6)
+
+
+def ns_loss_parts(pos: torch.Tensor, neg: torch.Tensor, kind: str, arg: float = 0.0, temperature: float = 1.0,
+                  want_grad: bool = True, g_pos: torch.Tensor = None, g_neg: torch.Tensor = None):
+    """(loss_rows [n], g_pos [n] or None, g_neg [n, K] or None) of a negative-sampling loss over one slot's scores given
+    as two pieces -- the positives `pos` [n] (any stride) and their negatives `neg` [n, K] (unit inner stride, any row
+    pitch) -- from ONE kernel (kge_ns_loss): the loss value is loss_rows.sum().  `arg`: the score offset of the bce
+    kinds, the margin of margin_ranking.  g_pos / g_neg: preallocated float32 outputs (a column and a slice of a wider
+    matrix, say); given, they are filled and returned."""
+    _require_gpu(pos, "pos")
+    _require_gpu(neg, "neg")
+    if (pos.dtype != torch.float32 or neg.dtype != torch.float32 or neg.dim() != 2 or neg.shape[1] < 1
+            or pos.numel() != neg.shape[0] or pos.device != neg.device):
+        raise ValueError("kge_amd: ns_loss_parts takes float32 pos [n] and neg [n, K >= 1] on one device")
+    code = NS_LOSS_KINDS[kind]
+    pos = pos.reshape(-1)
+    n, K = neg.shape
+    if K > 1 and neg.stride(1) != 1 or n > 1 and (neg.stride(0) < K or pos.stride(0) < 0):
+        neg = neg.contiguous()
+    if (g_pos is None) != (g_neg is None):
+        raise ValueError("kge_amd: ns_loss_parts: g_pos and g_neg come together")
+    ex = _ext()
+    if ex and g_pos is None:
+        with _on_device(neg.device):
+            rows, g_pos, g_neg = ex.ns_loss_parts(pos, neg, code, float(arg), float(temperature), bool(want_grad))
+        return rows, g_pos, g_neg
+    rows = _empty((n,), neg.device)
+    if g_pos is not None:
+        _require_gpu(g_pos, "g_pos")
+        _require_gpu(g_neg, "g_neg")
+        if (g_pos.dtype != torch.float32 or g_neg.dtype != torch.float32 or g_pos.dim() != 1 or g_pos.numel() != n
+                or tuple(g_neg.shape) != (n, K) or (K > 1 and g_neg.stride(1) != 1)
+                or (n > 1 and (g_neg.stride(0) < K or g_pos.stride(0) < 1))):
+            raise ValueError("kge_amd: ns_loss_parts: g_pos is float32 [n], g_neg float32 [n, K] with unit inner stride")
+    elif want_grad:
+        g_pos, g_neg = _empty((n,), neg.device), _empty((n, K), neg.device)
+    with _on_device(neg.device):
+        _lib.check(_lib.lib().kge_ns_loss(
+            pos.data_ptr(), pos.stride(0) if n > 1 else 1, neg.data_ptr(), neg.stride(0) if n > 1 else K, n, K, code,
+            float(arg), float(temperature), rows.data_ptr(), None if g_pos is None else g_pos.data_ptr(),
+            1 if g_pos is None or n <= 1 else g_pos.stride(0), None if g_neg is None else g_neg.data_ptr(),
+            K if g_neg is None or n <= 1 else g_neg.stride(0), _stream_handle(neg.device)), "kge_ns_loss")
+    return rows, g_pos, g_neg
+
+
+def ns_loss(scores: torch.Tensor, kind: str, arg: float = 0.0, temperature: float = 1.0, want_grad: bool = True):
+    """(loss_rows [n], grad [n, 1 + K] or None) of any negative-sampling loss (NS_LOSS_KINDS) over a score block
+    [n, 1 + K] with the positives in column 0 -- ns_loss_parts on its two column pieces, the gradient written straight
+    into one block.  A strided slice of a wider matrix is taken as it is."""
+    _require_gpu(scores, "scores")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or scores.shape[1] < 2:
+        raise ValueError("kge_amd: ns_loss takes a float32 [n, 1 + K] score block, K >= 1")
+    if scores.stride(1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
+        scores = scores.contiguous()
+    n, c = scores.shape
+    grad = _empty((n, c), scores.device) if want_grad else None
+    rows, _, _ = ns_loss_parts(scores[:, 0], scores[:, 1:], kind, arg, temperature, want_grad,
+                               None if grad is None else grad[:, 0], None if grad is None else grad[:, 1:])
     return rows, grad
 
 

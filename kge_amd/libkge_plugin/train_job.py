@@ -93,7 +93,8 @@ from kge.job import Job
 from kge.job.train_1vsAll import TrainingJob1vsAll
 from kge.job.train_KvsAll import TrainingJobKvsAll
 from kge.job.train_negative_sampling import TrainingJobNegativeSampling, S, P, O
-from kge.util.loss import BCEWithLogitsKgeLoss, KLDivWithSoftmaxKgeLoss
+from kge.util.loss import (BCEWithLogitsKgeLoss, KLDivWithSoftmaxKgeLoss, MarginRankingKgeLoss, SEKgeLoss,
+                           SoftMarginKgeLoss)
 
 
 def _optimizer_is_capturable(opt) -> bool:
@@ -683,6 +684,102 @@ def _fusable_ns_loss(loss) -> bool:
     return getattr(inner, "weight", None) is None and getattr(inner, "pos_weight", None) is None
 
 
+class _FusedNsLoss(torch.autograd.Function):
+    """loss = sum of kge_ns_loss's per-row terms over a [n, 1 + K] block; the kernel writes d loss / d scores in the
+    same pass."""
+
+    @staticmethod
+    def forward(ctx, scores, kind, arg):
+        from .. import engine
+        rows, grad = engine.ns_loss(scores, kind, arg, want_grad=True)
+        ctx.save_for_backward(grad)
+        return rows.sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+class _FusedNsLossParts(torch.autograd.Function):
+    """The same on two pieces -- the positives [n] and a slot's negatives [n, K] as the scoring node returns them: no
+    torch.cat in front of the loss, no split of its gradient behind it (the captured step's form)."""
+
+    @staticmethod
+    def forward(ctx, pos, neg, kind, arg, temperature):
+        from .. import engine
+        rows, g_pos, g_neg = engine.ns_loss_parts(pos, neg, kind, arg, temperature, want_grad=True)
+        ctx.save_for_backward(g_pos, g_neg)
+        ctx.pos_shape = pos.shape
+        return rows.sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        g_pos, g_neg = ctx.saved_tensors
+        return (g_pos * g).view(ctx.pos_shape), g_neg * g, None, None, None
+
+
+def _other_ns_loss_kind(loss):
+    """(kind, arg) of kge_ns_loss for the job's loss object if it is one of LibKGE's four negative-sampling losses
+    outside the bce family with its inner torch loss(es) as the reference builds them -- reduction "sum", no weight --,
+    else None (the stand-in is not installed)."""
+    def plain(inner, **more):
+        return (getattr(inner, "reduction", None) == "sum" and getattr(inner, "weight", None) is None
+                and all(getattr(inner, k, v) == v for k, v in more.items()))
+    if type(loss) is KLDivWithSoftmaxKgeLoss:
+        return ("kl", 0.0) if plain(loss._klloss, log_target=False) and plain(loss._celoss) else None
+    if type(loss) is MarginRankingKgeLoss:
+        if not plain(loss._loss) or "negative_sampling" not in str(loss._train_type):
+            return None
+        return "margin_ranking", float(loss._loss.margin)
+    if type(loss) is SoftMarginKgeLoss:
+        return ("soft_margin", 0.0) if plain(loss._loss) else None
+    if type(loss) is SEKgeLoss:
+        return ("se", 0.0) if plain(loss._loss) else None
+    return None
+
+
+class _HipNsLoss:
+    """Stands in for the job's KLDivWithSoftmaxKgeLoss / MarginRankingKgeLoss / SoftMarginKgeLoss / SEKgeLoss
+    (`train.loss: kl | margin_ranking | soft_margin | se`, kge/util/loss.py:192-274) on the [n, 1 + K] score block of a
+    negative-sampling slot, in the mould of _HipNsBceLoss: one kernel (kge_ns_loss) for the loss and its gradient
+    instead of the reference's op sequence -- for margin ranking instead of two nonzero() calls (two device -> host
+    waits per slot and step) and the positives repeated to [n K].  The margin is read from the wrapped
+    torch.nn.MarginRankingLoss.  Everything it does not recognise -- CPU tensors, index labels, a label matrix that is
+    not "column 0 positive, the rest negative" (checked once per label tensor) -- goes to the reference loss it wraps.
+    Installed by `hip_negative_sampling.fused_other_losses: true` (false by default)."""
+
+    def __init__(self, ref_loss):
+        self.ref = ref_loss
+        self.kind, self.arg = _other_ns_loss_kind(ref_loss)
+        self._pattern_ok = {}
+        self.fused_calls = 0
+
+    def __getattr__(self, name):  # everything else (config, _loss, ...) is the wrapped loss's
+        if name == "ref":  # not set yet (copy / pickle protocols probe attributes on a blank instance): no recursion
+            raise AttributeError(name)
+        return getattr(self.ref, name)
+
+    def __call__(self, scores, labels, **kwargs):
+        if not (torch.is_tensor(labels) and scores.is_cuda and scores.dim() == 2 and scores.dtype == torch.float32
+                and labels.dim() == 2 and labels.shape == scores.shape and scores.shape[1] >= 2):
+            return self.ref(scores, labels, **kwargs)
+        key = (labels.data_ptr(), tuple(labels.shape))
+        ok = self._pattern_ok.get(key)
+        if ok is None:
+            ok = self._pattern_ok[key] = bool((labels[:, 0] == 1).all()) and bool((labels[:, 1:] == 0).all())
+        if not ok:
+            return self.ref(scores, labels, **kwargs)
+        self.fused_calls += 1
+        return _FusedNsLoss.apply(scores, self.kind, self.arg)
+
+    def parts(self, pos, neg):
+        """The loss of a slot from the positives [n] and the slot's negatives [n, K] (float32, on the GPU) -- the label
+        pattern is the caller's statement: column 0 positive, the rest negative."""
+        self.fused_calls += 1
+        return _FusedNsLossParts.apply(pos, neg, self.kind, self.arg, 1.0)
+
+
 class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
     """`_process_subbatch` is the reference's (train_negative_sampling.py:103-164), called unchanged: labels,
     positive scores, loss, averaging, backward and every timing key are its code.  What changes is what
@@ -714,6 +811,14 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             fused_loss = True
         if str(self.device).startswith("cuda") and _fusable_ns_loss(self.loss) and fused_loss:
             self.loss = _HipNsBceLoss(self.loss)
+        # kl / margin_ranking / soft_margin / se on a GPU through kge_ns_loss (hip_negative_sampling.fused_other_losses,
+        # false by default: the reference's loss object, untouched)
+        try:
+            fused_other = bool(config.get("hip_negative_sampling.fused_other_losses"))
+        except KeyError:
+            fused_other = False
+        if str(self.device).startswith("cuda") and fused_other and _other_ns_loss_kind(self.loss) is not None:
+            self.loss = _HipNsLoss(self.loss)
         # shared samples of the subject / object slot through kge_score_neg_shared (false: the sampler's own score)
         try:
             self._fused_shared = bool(config.get("hip_negative_sampling.fused_shared"))
@@ -723,6 +828,7 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         self._graph_step_ok = None    # decided at the first batch
         self._graph_slots = ()
         self._graph_labels = {}
+        self.graph_batches = 0        # batches that went through the GraphedStep (replayed or eager)
         self._skip_optimizer_step = False
         if self.__class__ == HipTrainingJobNegativeSampling:
             for f in Job.job_created_hooks:
@@ -746,8 +852,9 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             slots = tuple(slot for slot in (S, O) if self._sampler.num_samples[slot] > 0)
             ok = ok and len(slots) > 0 and self._sampler.num_samples[P] <= 0
             ok = ok and all(type(batch["negative_samples"][slot]) is DefaultBatchNegativeSample for slot in slots)
-            # losses that are launches only: the kl loss (log_softmax + kl_div), plain bce, the one-kernel bce stand-ins
-            ok = ok and (isinstance(self.loss, (KLDivWithSoftmaxKgeLoss, _HipNsBceLoss))
+            # losses that are launches only: the kl loss (log_softmax + kl_div), plain bce, the one-kernel stand-ins
+            # (margin ranking only as its stand-in: the reference's form waits on two nonzero() calls)
+            ok = ok and (isinstance(self.loss, (KLDivWithSoftmaxKgeLoss, _HipNsBceLoss, _HipNsLoss))
                          or (isinstance(self.loss, BCEWithLogitsKgeLoss) and self.loss._bce_type is None))
             ok = ok and _optimizer_is_capturable(self.optimizer)
             ok = ok and (_fold_penalties(self) or _no_penalty(self, batch_index, batch))
@@ -773,8 +880,13 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         blocks = None
         if hasattr(self.model, "score_neg_blocks"):  # positives + both slots' blocks as one autograd node
             blocks = self.model.score_neg_blocks(s, p, o, by_slot.get(S), by_slot.get(O))
+        parts = isinstance(self.loss, _HipNsLoss)  # positives + the slot's block straight into kge_ns_loss: no cat
         for slot, neg in zip(self._graph_slots, negs):
             K = neg.shape[1]
+            if parts and blocks is not None:
+                part = self.loss.parts(blocks[0], blocks[1 if slot == S else 2]) * inv
+                total = part if total is None else total + part
+                continue
             labels = self._graph_labels.get((slot, n, K))
             if labels is None:
                 labels = self._graph_labels[(slot, n, K)] = torch.zeros((n, 1 + K), device=triples.device)
@@ -802,6 +914,7 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             result.prepare_time += time.time()
             result.forward_time -= time.time()
             loss_value = gs(triples, *negs, inv)
+            self.graph_batches += 1
             self._skip_optimizer_step = True  # (replayed or eager: GraphedStep has taken the optimizer's step)
             result.avg_loss += loss_value.item()
             result.forward_time += time.time()
