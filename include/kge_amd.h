@@ -530,6 +530,35 @@ int kge_ns_loss(const float* pos, int64_t pos_stride, const float* neg, int64_t 
                 float arg, float temperature, float* loss_rows, float* g_pos, int64_t g_pos_stride, float* g_neg,
                 int64_t g_neg_ld, void* stream);
 
+/* The negative samples of one slot drawn ON THE DEVICE (KgeSampler.sample, kge/util/sampler.py:80-137, with
+ * _filter_and_resample*, :163-196 / 700-752): one launch draws, filters and redraws.
+ *   out[i * ld + k], i < n, k < K  = the draw of the first attempt t = 0, 1, 2, ... that is NOT among the known answers
+ *   of row i's key a[i] * mult + b[i] in the filter index (sorted_keys / starts / values as for kge_filter_lookup; a key
+ *   absent from the index has no known answers).  Rejection sampling: the same distribution as the reference's resample
+ *   loop -- uniform, or frequency weighted, over the non-positives.
+ * Random numbers: Philox4x32-10, counter based, no state, no library.  One block r0..r3 per (row, column, attempt):
+ *   key = (seed low 32, seed high 32),  counter = (k, i, t, (uint32)call * 4 + slot)
+ *   uniform (alias_prob == alias_idx == NULL):  id = umul64hi((r0 << 32) | r1, vocab)
+ *   frequency (alias tables [vocab]):  bucket = umul64hi((r0 << 32) | r1, vocab), u = (r2 >> 8) * 2^-24,
+ *                                      id = u < alias_prob[bucket] ? bucket : alias_idx[bucket]
+ * so a draw is a pure function of (seed, call, slot, i, k, t): two runs give the same bits, whatever the launch.
+ * sorted_keys == NULL: unfiltered (starts, values, a, b, mult ignored; every first draw is kept).
+ * A column stops after KGE_NEG_SAMPLE_MAX_ATTEMPTS attempts and keeps its last draw (a key whose answers cover the
+ * vocabulary: the reference never returns).  stats (NULL or int32 [n, 2]): stats[i * 2] = row i's number of rejected
+ * attempts (the kept draw of a capped column included), stats[i * 2 + 1] = its columns that hit the cap; plain
+ * stores, no atomics.
+ * slot: 0 (subject) or 2 (object); it only enters the counter -- the caller passes the matching index and key columns
+ * (slot 0: the po index, a = p, b = o, mult = num_ent; slot 2: the sp index, a = s, b = p, mult = num_rel).
+ * n == 0 or K == 0: KGE_OK, nothing written; nothing outside [n, K] is written when ld > K.
+ * KGE_ERR_INVALID_ARG: vocab < 1, slot 1 (the relation slot) or any other slot, one alias pointer without the other,
+ * sorted_keys without starts / values / a / b, ld < K, out NULL; n or K above 2^32: KGE_ERR_UNSUPPORTED. */
+#define KGE_NEG_SAMPLE_MAX_ATTEMPTS 256
+int kge_neg_sample(int64_t n, int64_t K, int64_t vocab, int slot, uint64_t seed, uint64_t call,
+                   const float* alias_prob, const int64_t* alias_idx,
+                   const int64_t* sorted_keys, int64_t num_keys, const int64_t* starts, const int64_t* values,
+                   kge_index a, kge_index b, int64_t mult,
+                   int64_t* out, int64_t ld, int32_t* stats, void* stream);
+
 /* The two row moves of the entity-sharded exchange (kge_amd/sharded.py: ShardedEntityTable.exchange_rows),
  * the id arithmetic evaluated inside the kernel, one launch each:
  *   kge_shard_gather   t->ent = THIS RANK's rows [lo, lo + t->num_ent) of the entity table.  For j < num_ids (1 or 2

@@ -118,6 +118,8 @@ PROTOTYPES = {
                                        c_i64, c_vp]),
     "kge_ns_loss": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                    c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kge_neg_sample": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,
+                                      c_vp, c_i64, c_vp, c_vp, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "kge_shard_gather": (ctypes.c_int, [_PT, c_i64, ctypes.POINTER(KgeIndex), ctypes.c_int, c_i64, c_vp, c_i64,
                                         KgeIndex, c_vp, c_i64, c_vp]),
     "kge_shard_pick": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_int,

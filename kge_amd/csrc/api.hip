@@ -107,6 +107,10 @@ int run_ns_bce(int kind, const float* scores, long long ld, long long n, long lo
 int run_ns_loss(int kind, const float* pos, long long pos_stride, const float* neg, long long neg_ld, long long n,
                 long long K, float arg, float temp, float* loss_rows, float* g_pos, long long g_pos_stride, float* g_neg,
                 long long g_neg_ld, hipStream_t st);
+int run_neg_sample(long long n, long long K, long long vocab, int slot, unsigned long long seed, unsigned long long call,
+                   const float* alias_prob, const long long* alias_idx, const long long* keys, long long num_keys,
+                   const long long* starts, const long long* values, const Index& a, const Index& b, long long mult,
+                   long long* out, long long ld, int* stats, hipStream_t st);
 int run_shard_rows(const ShardJob& a, const ShardJob& b, const ShardJob& c, int rowbytes01, int rowbytes2, int esize,
                    hipStream_t st);
 int run_rank(const float* scores, long long lds, long long n, long long c,
@@ -873,6 +877,28 @@ int kge_ns_loss(const float* pos, int64_t pos_stride, const float* neg, int64_t 
   if (!pos || !neg || !loss_rows) return KGE_ERR_INVALID_ARG;
   return run_ns_loss(kind, pos, pos_stride, neg, neg_ld, n, K, arg, temperature, loss_rows, g_pos, g_pos_stride, g_neg,
                      g_neg_ld, (hipStream_t)stream);
+}
+
+int kge_neg_sample(int64_t n, int64_t K, int64_t vocab, int slot, uint64_t seed, uint64_t call, const float* alias_prob,
+                   const int64_t* alias_idx, const int64_t* sorted_keys, int64_t num_keys, const int64_t* starts,
+                   const int64_t* values, kge_index a, kge_index b, int64_t mult, int64_t* out, int64_t ld, int32_t* stats,
+                   void* stream) {
+  KGE_RANGE();
+  if (n < 0 || K < 0 || vocab < 1 || (slot != 0 && slot != 2) || num_keys < 0) return KGE_ERR_INVALID_ARG;
+  if ((alias_prob == nullptr) != (alias_idx == nullptr)) return KGE_ERR_INVALID_ARG;  // the alias table comes whole
+  if (sorted_keys) {
+    if (!starts || !values) return KGE_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = check_index(a, false, n)) || (rc = check_index(b, false, n))) return rc;
+  }
+  if (n == 0 || K == 0) return KGE_OK;
+  if (!out || ld < K) return KGE_ERR_INVALID_ARG;
+  if (n > 0xFFFFFFFFll || K > 0xFFFFFFFFll) return KGE_ERR_UNSUPPORTED;  // (row and column are 32-bit counter words)
+  const kge_index none{nullptr, KGE_I64, 0, 1};
+  return run_neg_sample(n, K, vocab, slot, seed, call, alias_prob, (const long long*)alias_idx,
+                        (const long long*)sorted_keys, num_keys, (const long long*)starts, (const long long*)values,
+                        make_index(sorted_keys ? a : none), make_index(sorted_keys ? b : none), mult, (long long*)out, ld,
+                        stats, (hipStream_t)stream);
 }
 
 int kge_shard_gather(const kge_tables* t, int64_t lo, const kge_index* ids, int num_ids, int64_t n, void* send,

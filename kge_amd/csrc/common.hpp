@@ -47,6 +47,31 @@ __device__ __forceinline__ long long index_at(const Index& ix, long long i) {
   return (long long)((const int*)ix.ptr)[i * ix.stride];
 }
 
+// The key search of a device-resident filter index (sorted unique keys: include/kge_amd.h, kge_filter_lookup) by one
+// WAVE: the first position with keys[pos] >= key, in every lane.  A 64-ary search: a thread-per-row binary search over
+// the ~3e5 keys of an FB15k-237-sized index is 18 DEPENDENT loads; with 64 probes per step the range shrinks 64-fold
+// per round trip: 3-4 steps.  All 64 lanes of the wave must call it with the same arguments.
+__device__ __forceinline__ long long filter_key_pos(const long long* __restrict__ keys, long long num_keys, long long key,
+                                                    int lane) {
+  long long lo = 0, hi = num_keys;  // invariant: the first position with keys[pos] >= key lies in [lo, hi]
+  while (hi - lo > 64) {
+    const long long step = (hi - lo + 63) >> 6;
+    const long long pos = lo + lane * step;  // probes, ascending
+    const bool below = pos < hi && keys[pos] < key;
+    const int c = __popcll(__ballot(below));  // the probes below the key are a prefix
+    if (c == 0) {
+      hi = lo;
+    } else {
+      const long long nhi = lo + c * step;  // the first probe that is not below (or past the end)
+      lo = lo + (c - 1) * step + 1;
+      hi = nhi < hi ? nhi : hi;
+    }
+  }
+  const long long pos = lo + lane;
+  const bool below = pos < hi && keys[pos] < key;
+  return lo + __popcll(__ballot(below));
+}
+
 // One kernel operand: rows `idx[i]` of a row-major matrix (table or dense embeddings).
 struct Operand {
   const void* base;

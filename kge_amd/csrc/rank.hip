@@ -131,23 +131,7 @@ __global__ __launch_bounds__(256) void filter_lookup_kernel(const long long* __r
   if (i >= n) return;
   const int lane = threadIdx.x & 63;
   const long long key = index_at(a, i) * mult + index_at(b, i);
-  long long lo = 0, hi = num_keys;  // invariant: the first position with keys[pos] >= key lies in [lo, hi]
-  while (hi - lo > 64) {
-    const long long step = (hi - lo + 63) >> 6;
-    const long long pos = lo + lane * step;  // probes, ascending
-    const bool below = pos < hi && keys[pos] < key;
-    const int c = __popcll(__ballot(below));  // the probes below the key are a prefix
-    if (c == 0) {
-      hi = lo;
-    } else {
-      const long long nhi = lo + c * step;  // the first probe that is not below (or past the end)
-      lo = lo + (c - 1) * step + 1;
-      hi = nhi < hi ? nhi : hi;
-    }
-  }
-  const long long pos = lo + lane;
-  const bool below = pos < hi && keys[pos] < key;
-  lo += __popcll(__ballot(below));
+  const long long lo = filter_key_pos(keys, num_keys, key, lane);  // (common.hpp: shared with neg_sample.hip)
   if (lane == 0) {
     const bool hit = lo < num_keys && keys[lo] == key;
     begin[i] = hit ? starts[lo] : 0;
@@ -176,23 +160,7 @@ __global__ __launch_bounds__(256) void filter_lookup_multi_kernel(FilterQueries 
   const long long* __restrict__ keys = Q.keys[q];
   const long long num_keys = Q.num_keys[q];
   const long long key = index_at(Q.a[q], i) * Q.mult[q] + index_at(Q.b[q], i);
-  long long lo = 0, hi = num_keys;  // the 64-ary search of filter_lookup_kernel
-  while (hi - lo > 64) {
-    const long long step = (hi - lo + 63) >> 6;
-    const long long pos = lo + lane * step;
-    const bool below = pos < hi && keys[pos] < key;
-    const int c = __popcll(__ballot(below));
-    if (c == 0) {
-      hi = lo;
-    } else {
-      const long long nhi = lo + c * step;
-      lo = lo + (c - 1) * step + 1;
-      hi = nhi < hi ? nhi : hi;
-    }
-  }
-  const long long pos = lo + lane;
-  const bool below = pos < hi && keys[pos] < key;
-  lo += __popcll(__ballot(below));
+  const long long lo = filter_key_pos(keys, num_keys, key, lane);  // the 64-ary search of filter_lookup_kernel
   if (lane == 0) {
     const bool hit = lo < num_keys && keys[lo] == key;
     Q.begin[q][i] = hit ? Q.starts[q][lo] : 0;

@@ -515,6 +515,53 @@ std::vector<at::Tensor> ns_loss_parts(const at::Tensor& pos, const at::Tensor& n
   return {rows, g_pos, g_neg};
 }
 
+// ---- one slot's negative samples drawn on the device (kge_neg_sample): -> (out int64 [n, K], stats int32 [n, 2] or an
+// undefined tensor).  alias = (prob float32 [vocab], idx int64 [vocab]) or neither; index = (sorted_keys, starts, values)
+// int64 with the key columns a, b [n], or none of them (unfiltered).  `like` names the device.
+std::vector<at::Tensor> neg_sample(const at::Tensor& like, int64_t n, int64_t K, int64_t vocab, int64_t slot, uint64_t seed,
+                                   uint64_t call, const c10::optional<at::Tensor>& alias_prob,
+                                   const c10::optional<at::Tensor>& alias_idx, const c10::optional<at::Tensor>& sorted_keys,
+                                   const c10::optional<at::Tensor>& starts, const c10::optional<at::Tensor>& values,
+                                   const c10::optional<at::Tensor>& a, const c10::optional<at::Tensor>& b, int64_t mult,
+                                   bool want_stats) {
+  TORCH_CHECK(like.is_cuda(), "kge_amd: neg_sample draws on a GPU (no CPU path)");
+  TORCH_CHECK_VALUE(n >= 0 && K >= 0, "kge_amd: neg_sample: negative shape");
+  const auto on_dev = [&](const c10::optional<at::Tensor>& t, at::ScalarType ty, const char* what) -> const void* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->get_device() == like.get_device(), "kge_amd: neg_sample: ", what, " on ", t->device());
+    TORCH_CHECK_VALUE(t->scalar_type() == ty && t->is_contiguous(), "kge_amd: neg_sample: ", what, ": dtype / layout");
+    return t->data_ptr();
+  };
+  const float* ap = (const float*)on_dev(alias_prob, at::kFloat, "alias_prob");
+  const int64_t* ai = (const int64_t*)on_dev(alias_idx, at::kLong, "alias_idx");
+  TORCH_CHECK_VALUE(!ap || (ai && alias_prob->numel() == vocab && alias_idx->numel() == vocab),
+                    "kge_amd: neg_sample: the alias tables are [vocab] each");
+  const int64_t* keys = (const int64_t*)on_dev(sorted_keys, at::kLong, "sorted_keys");
+  const int64_t* st = (const int64_t*)on_dev(starts, at::kLong, "starts");
+  const int64_t* vals = (const int64_t*)on_dev(values, at::kLong, "values");
+  std::vector<at::Tensor> keep;
+  kge_index ia{nullptr, KGE_I64, 0, 1}, ib = ia;
+  int64_t num_keys = 0;
+  if (keys) {
+    TORCH_CHECK_VALUE(st && vals && starts->numel() == sorted_keys->numel() + 1, "kge_amd: neg_sample: starts is [num_keys + 1]");
+    num_keys = sorted_keys->numel();
+    int64_t len = n;
+    ia = index_of(a, like, keep, &len);
+    ib = index_of(b, like, keep, &len);
+  }
+  at::Tensor out, stats;
+  try {
+    out = at::empty({n, K}, like.options().dtype(at::kLong));
+    if (want_stats) stats = at::empty({n, 2}, like.options().dtype(at::kInt));
+  } catch (const c10::OutOfMemoryError& e) {
+    TORCH_CHECK(false, "CUDA out of memory (kge_amd, ROCm: ", e.what_without_backtrace(), ")");
+  }
+  check(kge_neg_sample(n, K, vocab, (int)slot, seed, call, ap, ai, keys, num_keys, st, vals, ia, ib, mult,
+                       out.data_ptr<int64_t>(), K, want_stats ? stats.data_ptr<int32_t>() : nullptr, stream_of(like)),
+        "kge_neg_sample");
+  return {out, stats};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -543,4 +590,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("bce_f32_bwd", &bce_f32_bwd, "its backward: (g_a, g_p, g_entities)");
   mod.def("ns_loss_parts", &ns_loss_parts,
           "negative-sampling loss of one slot from (pos [n], neg [n, K]): (loss_rows, g_pos, g_neg)");
+  mod.def("neg_sample", &neg_sample, "one slot's negative samples drawn, filtered and redrawn on the device: (out, stats)");
 }

@@ -21,7 +21,7 @@ from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT
                    SCORERS, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
 
 __all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "shared_samples",
-           "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
+           "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "neg_sample", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
            "FLAG_SPLIT_QUERY", "reserve_cus", "Queries", "build_queries", "score_queries", "ScorePipeline"]
 
 
@@ -1072,6 +1072,88 @@ def ns_loss(scores: torch.Tensor, kind: str, arg: float = 0.0, temperature: floa
     rows, _, _ = ns_loss_parts(scores[:, 0], scores[:, 1:], kind, arg, temperature, want_grad,
                                None if grad is None else grad[:, 0], None if grad is None else grad[:, 1:])
     return rows, grad
+
+
+NEG_SAMPLE_MAX_ATTEMPTS = 256  # KGE_NEG_SAMPLE_MAX_ATTEMPTS
+
+
+def neg_sample(n: int, K: int, vocab: int, slot: int, seed: int, call: int, alias=None, index=None, a=None, b=None,
+               mult: int = 0, out: torch.Tensor = None, stats=None, device=None):
+    """The negative samples of one slot drawn, filtered and redrawn on the GPU in one launch (kge_neg_sample): int64
+    [n, K], a pure function of (seed, call, slot, row, column) -- Philox4x32-10, include/kge_amd.h has the layout.
+      alias   None (uniform over [0, vocab)) or (prob float32 [vocab], idx int64 [vocab]): frequency sampling
+      index   None (unfiltered) or (sorted_keys, starts, values), int64 device tensors in kge_amd.eval.FilterIndex's
+              layout: no sample of row i is a known answer of key a[i] * mult + b[i] (a, b: int32 / int64 [n], any
+              stride), unless the column hit the cap of NEG_SAMPLE_MAX_ATTEMPTS attempts
+      out     None or a preallocated int64 [n, K] with unit inner stride (a slice of a wider matrix is fine)
+      stats   None / False (no statistics), True (allocate) or an int32 [n, 2] tensor: per row the rejected attempts
+              and the columns that hit the cap
+    -> out, or (out, stats) when stats is asked for.  The device is out's, the index's, the alias tables' or `device`."""
+    n, K = int(n), int(K)
+    for cand in (out, index[0] if index is not None else None, alias[0] if alias is not None else None):
+        if cand is not None:
+            device = cand.device
+            break
+    if device is None:
+        raise ValueError("kge_amd: neg_sample needs a device (out, index, alias or device=)")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"kge_amd: neg_sample draws on a GPU, not on '{device}' (no CPU path)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    keep = []
+
+    def dev_tensor(x, dtype, what):
+        if not (torch.is_tensor(x) and x.device == device and x.dtype == dtype and x.is_contiguous()):
+            raise ValueError(f"kge_amd: neg_sample: {what} must be a contiguous {dtype} tensor on {device}")
+        keep.append(x)
+        return x.data_ptr()
+
+    ap = ai = keys = starts = values = None
+    if alias is not None:
+        ap, ai = dev_tensor(alias[0], torch.float32, "alias prob"), dev_tensor(alias[1], torch.int64, "alias idx")
+        if alias[0].numel() != vocab or alias[1].numel() != vocab:
+            raise ValueError("kge_amd: neg_sample: the alias tables are [vocab] each")
+    ia = ib = KgeIndex(None, I64, 0, 1)
+    num_keys = 0
+    if index is not None:
+        keys, starts = dev_tensor(index[0], torch.int64, "sorted_keys"), dev_tensor(index[1], torch.int64, "starts")
+        values = dev_tensor(index[2], torch.int64, "values")
+        num_keys = index[0].numel()
+        if index[1].numel() != num_keys + 1:
+            raise ValueError("kge_amd: neg_sample: starts is [num_keys + 1]")
+        k0 = len(keep)
+        ia, ib = _index(a, device, keep), _index(b, device, keep)
+        if _same_len(keep[k0:k0 + 2], "neg_sample") != n:
+            raise ValueError("kge_amd: neg_sample: a and b have n entries")
+    want_stats = stats is not None and stats is not False
+    ex = _ext()
+    if ex and out is None and (stats is None or isinstance(stats, bool)):
+        with _on_device(device):
+            o, st = ex.neg_sample(torch.empty(0, device=device), n, K, int(vocab), int(slot), int(seed) & (2 ** 64 - 1),
+                                  int(call) & (2 ** 64 - 1), None if alias is None else alias[0],
+                                  None if alias is None else alias[1], None if index is None else index[0],
+                                  None if index is None else index[1], None if index is None else index[2],
+                                  keep[-2] if index is not None else None, keep[-1] if index is not None else None,
+                                  int(mult), want_stats)
+        return (o, st) if want_stats else o
+    if out is None:
+        out = _empty((n, K), device, torch.int64)
+    elif not (out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (n, K) and (K <= 1 or out.stride(1) == 1)
+              and (n <= 1 or out.stride(0) >= K)):
+        raise ValueError("kge_amd: neg_sample: out is int64 [n, K] with unit inner stride on the GPU")
+    if want_stats:
+        if stats is True:
+            stats = _empty((n, 2), device, torch.int32)
+        elif not (stats.device == device and stats.dtype == torch.int32 and tuple(stats.shape) == (n, 2)
+                  and stats.is_contiguous()):
+            raise ValueError("kge_amd: neg_sample: stats is a contiguous int32 [n, 2] tensor")
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_neg_sample(
+            n, K, int(vocab), int(slot), int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1), ap, ai, keys, num_keys,
+            starts, values, ia, ib, int(mult), out.data_ptr(), out.stride(0) if n > 1 and K > 0 else max(K, 1),
+            stats.data_ptr() if want_stats else None, _stream_handle(device)), "kge_neg_sample")
+    return (out, stats) if want_stats else out
 
 
 def shard_gather(t: Tables, lo: int, ids, rel_idx, send: torch.Tensor, rel_out=None):

@@ -824,6 +824,15 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             self._fused_shared = bool(config.get("hip_negative_sampling.fused_shared"))
         except KeyError:
             self._fused_shared = False
+        # the samples of the subject / object slot drawn on the device (hip_negative_sampling.device_sampler, false by
+        # default: every slot's samples come from the reference's sampler on the host)
+        try:
+            device_sampler = bool(config.get("hip_negative_sampling.device_sampler"))
+        except KeyError:
+            device_sampler = False
+        self._device_sampler, self._device_slots = None, ()
+        if device_sampler:
+            self._setup_device_sampler()
         self._graph_step = None       # kge_amd.train_graph.GraphedStep (hip_negative_sampling.graph_step)
         self._graph_step_ok = None    # decided at the first batch
         self._graph_slots = ()
@@ -833,6 +842,70 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         if self.__class__ == HipTrainingJobNegativeSampling:
             for f in Job.job_created_hooks:
                 f(self)
+
+    # ---- hip_negative_sampling.device_sampler: the [n, K] sample blocks of the subject / object slot drawn, filtered
+    # and redrawn on the GPU (kge_amd.sampler.DeviceSampler -> kge_neg_sample, one launch per slot) instead of
+    # KgeSampler.sample on the host for each slot (train_negative_sampling.py:64-84; with filtering a per-row loop,
+    # sampler.py:163-196, 700-752) and the copy of the blocks to the device (:86-101).  The block is wrapped in the
+    # reference's own DefaultBatchNegativeSample: everything downstream sees the object it sees today.  The draw happens
+    # in _prepare_batch, outside the captured step.
+    def _setup_device_sampler(self):
+        """Which slots qualify (none: the job is the plain one) and the sampler over the training split."""
+        smp, cfg = self._sampler, self.config
+        if not str(self.device).startswith("cuda") or smp.shared or not smp.with_replacement:
+            return
+        sampling_type = cfg.get("negative_sampling.sampling_type")
+        if sampling_type not in ("uniform", "frequency"):
+            return
+        if smp.filtering_split != cfg.get("train.split"):  # ('' = the training split: sampler.py:34-36)
+            return
+        slots = tuple(slot for slot in (S, O) if int(smp.num_samples[slot]) > 0)  # (empty blocks: the reference's)
+        if not slots:
+            return
+        from ..sampler import DeviceSampler
+        seed = cfg.get("random_seed.torch")
+        if seed is None or int(seed) < 0:
+            seed = torch.initial_seed()
+        self._device_sampler = DeviceSampler(
+            self.dataset.split(cfg.get("train.split")), self.dataset.num_entities(), self.dataset.num_relations(),
+            sampling_type=sampling_type, smoothing=float(cfg.get("negative_sampling.frequency.smoothing")),
+            filter_s=S in slots and bool(smp.filter_positives[S]), filter_o=O in slots and bool(smp.filter_positives[O]),
+            seed=int(seed), device=self.device)
+        self._device_slots = slots
+
+    def _get_collate_fun(self):
+        if not self._device_slots:
+            return super()._get_collate_fun()
+
+        def collate(batch):
+            """The reference's collate (train_negative_sampling.py:66-82) without the host draw of the device slots."""
+            triples = self.dataset.split(self.train_split)[batch, :].long()
+            negative_samples = [None if slot in self._device_slots else self._sampler.sample(triples, slot)
+                                for slot in (S, P, O)]
+            return {"triples": triples, "negative_samples": negative_samples}
+
+        return collate
+
+    def _prepare_batch(self, batch_index, batch, result):
+        if not self._device_slots:
+            return super()._prepare_batch(batch_index, batch, result)
+        from kge.util.sampler import DefaultBatchNegativeSample
+        result.prepare_time -= time.time()
+        triples = batch["triples"] = batch["triples"].to(self.device)
+        samples = []
+        for slot, ns in enumerate(batch["negative_samples"]):
+            if ns is None:  # a device slot: drawn now that the triples are on the device
+                K = int(self._sampler.num_samples[slot])
+                ns = DefaultBatchNegativeSample(self.config, self._sampler.configuration_key, triples, slot, K,
+                                                self._device_sampler.sample(triples, slot, K))
+            else:
+                ns.positive_triples = triples
+                ns = ns.to(self.device)
+            samples.append(ns)
+        batch["negative_samples"] = samples
+        batch["labels"] = [None] * 3  # reuse label tensors b/w subbatches
+        result.size = len(triples)
+        result.prepare_time += time.time()
 
     # ---- hip_negative_sampling.graph_step: the whole step of a full batch -- positives, the slots' negative blocks, the
     # loss of every slot, backward, optimizer.step -- as ONE hipGraph replay (kge_amd.train_graph.GraphedStep).  Through
