@@ -12,7 +12,8 @@
 //   sum = sum + g * g
 //   p   = p + (minus_clr * g) / (sqrt(sum) + eps)
 // (-ffp-contract=off; torch's kernels may contract the first two lines into fma: results agree to
-// an ulp or two, tests/test_gpu_optim.py states the tolerance.)
+// an ulp or two, tests/test_gpu_optim.py states the tolerance.  tests/_optim_ref.py restates every kernel of this
+// file op by op in numpy float32; tests/test_gpu_optim_exact.py holds the kernels to its BITS.)
 #include "common.hpp"
 
 namespace kge {
@@ -291,7 +292,8 @@ int run_adagrad(float* param, const float* grad, float* sum, long long count, fl
 //   g          = grad + weight_decay * param            (only if weight_decay != 0)
 //   exp_avg    = exp_avg + (g - exp_avg) * (1 - beta1)   (lerp)
 //   exp_avg_sq = exp_avg_sq * beta2 + (1 - beta2) * g * g
-//   param      = param + (-step_size) * exp_avg / (sqrt(exp_avg_sq) / bias_corr2_sqrt + eps)
+//   param      = param + (-step_size) * (exp_avg / (sqrt(exp_avg_sq) / bias_corr2_sqrt + eps))
+// (the quotient first, then the product -- torch's addcdiv multiplies first; (1 - beta2) * g first, then * g.)
 // step_size = lr / (1 - beta1^t), bias_corr2_sqrt = sqrt(1 - beta2^t): computed by the caller.
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ param, const float* __restrict__ grad,
                                                    float* __restrict__ m1, float* __restrict__ m2, long long count,

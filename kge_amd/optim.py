@@ -4,8 +4,8 @@ maintaining the bf16 copies of the tables that mixed-precision scoring reads.
 
 Drop-in for `torch.optim.Adagrad` (same constructor arguments, same `state_dict`: per-parameter
 "step" and "sum"), so LibKGE's optimizer checkpoints load either way.  Parameters the kernel does
-not cover (CPU tensors, non-float32, sparse gradients) are stepped by torch's own functional
-Adagrad.  kge/util/optimizer.py:15-20 resolves `train.optimizer.default.type` with
+not cover (CPU tensors, non-float32, sparse gradients, a parameter / gradient / state tensor
+whose data pointer is not 16-byte aligned) are stepped by torch's own functional Adagrad.  kge/util/optimizer.py:15-20 resolves `train.optimizer.default.type` with
 `getattr(torch.optim, ...)`; the LibKGE plugin registers this class there as `HipAdagrad`.
 """
 import torch
@@ -99,10 +99,17 @@ class Adagrad(_TorchAdagrad):
         return (self._pen_acc[param.device][self._pen_slot[param]] * spec[4]).to(torch.float32)
 
     @staticmethod
+    def _aligned(*tensors) -> bool:
+        """The dense kernels load and store four floats at a time: kge_adagrad_step* / kge_adam_step refuse a param,
+        grad or state pointer that is not 16-byte aligned.  A contiguous view at an odd element offset of a flat
+        buffer (nn.Parameter(flat[1:1 + k]), a gradient that is a slice of a flattened gradient buffer) is not."""
+        return all(t.data_ptr() % 16 == 0 for t in tensors)
+
+    @staticmethod
     def _kernel_ok(p: torch.Tensor) -> bool:
         g = p.grad
         return (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and g is not None
-                and not g.is_sparse and g.dtype == torch.float32 and g.is_contiguous())
+                and not g.is_sparse and g.dtype == torch.float32 and g.is_contiguous() and Adagrad._aligned(p, g))
 
     @staticmethod
     def _rows_ok(p: torch.Tensor, group) -> bool:
@@ -162,7 +169,7 @@ class Adagrad(_TorchAdagrad):
                 if self._rows_ok(p, group):
                     self._step_rows(p, group)
                     continue
-                if not self._kernel_ok(p):
+                if not self._kernel_ok(p) or not self._aligned(self.state[p]["sum"]):
                     rest.append(p)
                     continue
                 state = self.state[p]
@@ -256,10 +263,11 @@ class Adam(torch.optim.Adam):
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                if not Adagrad._kernel_ok(p):
+                state = self.state[p]
+                if not Adagrad._kernel_ok(p) or (len(state) != 0 and not Adagrad._aligned(state["exp_avg"],
+                                                                                         state["exp_avg_sq"])):
                     held = True
                     continue
-                state = self.state[p]
                 if len(state) == 0:
                     state["step"] = torch.tensor(0.0, dtype=torch.float32)
                     state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
