@@ -1033,7 +1033,8 @@ int kge_adagrad_step_rows(float* param, int64_t param_ld, const float* grad_rows
  * kge_score_sp / kge_score_po (dir = KGE_SP_ / KGE_PO_):
  *   g_a   [n, dim]      grad of the gathered entity query rows (s for SP_, o for PO_)
  *   g_p   [n, rel_dim]  grad of the gathered relation rows
- *   g_tgt [m, dim]      grad of the target rows (dense; caller scatter-adds)   */
+ *   g_tgt [m, dim]      grad of the target rows (dense; caller scatter-adds)
+ * An empty side leaves zeros on the other: n == 0 writes g_tgt = 0, m == 0 writes g_a = g_p = 0. */
 int64_t kge_score_bwd_workspace_bytes(const kge_tables* t, int64_t n, int64_t m);
 int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p,
                         int64_t n, kge_index targets, int64_t m,

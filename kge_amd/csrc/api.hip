@@ -1545,6 +1545,19 @@ int64_t kge_score_bwd_workspace_bytes(const kge_tables* t, int64_t n, int64_t m)
   return pairs_bwd_workspace_bytes(t->dtype, t->scorer, (int)t->dim, n, m);
 }
 
+namespace {
+// kge_score_pairs_bwd with an empty side: the gradients are OVERWRITTEN (include/kge_amd.h), and a sum over no pairs
+// is zero -- no queries: g_tgt [m, dim] = 0; no targets: g_a [n, dim] = g_p [n, rel_dim] = 0.
+int pairs_bwd_empty(const kge_tables* t, int64_t n, int64_t m, float* g_a, float* g_p, float* g_tgt, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  bool ok = true;
+  if (m > 0 && g_tgt) ok = kge::fill_words_async(g_tgt, 0, (size_t)m * t->dim * sizeof(float), st) && ok;
+  if (n > 0 && g_a) ok = kge::fill_words_async(g_a, 0, (size_t)n * t->dim * sizeof(float), st) && ok;
+  if (n > 0 && g_p) ok = kge::fill_words_async(g_p, 0, (size_t)n * t->rel_dim * sizeof(float), st) && ok;
+  return ok ? KGE_OK : KGE_ERR_LAUNCH;
+}
+}  // namespace
+
 int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
                         kge_index targets, int64_t m, const float* gout, int64_t ldg,
                         const float* scores, int64_t lds, float* g_a, float* g_p, float* g_tgt,
@@ -1559,6 +1572,7 @@ int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, 
     if ((rc = check_index(a, false)) || (rc = check_index(p, false)) || (rc = check_index(targets, true)))
       return rc;
     if (!targets.ptr && m != t->num_ent) return KGE_ERR_INVALID_ARG;
+    if (n == 0 || m == 0) return pairs_bwd_empty(t, n, m, g_a, g_p, g_tgt, stream);
     return run_pairs_bwd_gemm16(t->scorer, dir, ent_op(t, a), rel_op(t, p), ent_op(t, targets), (int)t->dim,
                                 (int)t->rel_dim, n, m, gout, ldg, g_a, g_p, g_tgt, workspace, workspace_bytes,
                                 (hipStream_t)stream);
@@ -1572,6 +1586,7 @@ int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, 
     return rc;
   if (!targets.ptr && m != t->num_ent) return KGE_ERR_INVALID_ARG;
   if (n > 65535LL * 64 || m > 65535LL * 64) return KGE_ERR_UNSUPPORTED;
+  if (n == 0 || m == 0) return pairs_bwd_empty(t, n, m, g_a, g_p, g_tgt, stream);
   return run_pairs_bwd(t->scorer, t->l_norm, dir, ent_op(t, a), rel_op(t, p), ent_op(t, targets),
                        (int)t->dim, (int)t->rel_dim, n, m, gout, ldg, scores, lds, g_a, g_p, g_tgt,
                        (hipStream_t)stream, (t->flags & KGE_FLAG_EXACT) != 0);

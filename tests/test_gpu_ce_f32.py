@@ -7,7 +7,8 @@ The backward's bound is not fixed in advance: per case the COMPOSED path's own m
 measured, and the fused path is allowed 4 x that (another summation order on the same products and operand precision).
 Measured on an MI355X over the 96 comparisons below (max |err| / max(1, |want|max), entity and relation table
 gradients): composed 1.96e-8 .. 1.06e-6, fused at most 1.04e-6, fused / composed at most 2.60; the bound 4 x composed was
-therefore between 7.8e-8 and 4.3e-6."""
+therefore between 7.8e-8 and 4.3e-6.  The composed path's own error -- kge_score_pairs_bwd on
+float32 tables, the yardstick here -- is asserted against a derived rounding bound in tests/test_gpu_pairs_bwd.py."""
 import ctypes
 import functools
 
