@@ -559,6 +559,69 @@ int kge_neg_sample(int64_t n, int64_t K, int64_t vocab, int slot, uint64_t seed,
                    kge_index a, kge_index b, int64_t mult,
                    int64_t* out, int64_t ld, int32_t* stats, void* stream);
 
+/* A KvsAll batch built ON THE DEVICE from the batch's example numbers: what TrainingJobKvsAll's collate function does
+ * on the host (kge/job/train_KvsAll.py:118-201, a Python loop over the examples) plus the cut of its label_coords into
+ * one CSR per query type that the fused KvsAll losses read (kge_kl_* / kge_bce_* and their _dist / _f32 forms), padded
+ * or not.  The index arrays never change during training and stay on the device; integer work only, no atomics.
+ *
+ * types[t], t < num_types (1..3), ordered as the job's query_types: the KvsAllIndex of the type -- keys int64 [M_t, 2],
+ *   offsets int64 [M_t + 1], values int64 [offsets[M_t]], all on the device -- with
+ *     last        the example number right after the type's last example (query_last_example: type t owns
+ *                 [types[t-1].last, types[t].last), type 0 starts at 0; M_t = last - previous last)
+ *     target_col  the triple column its labels go to: 2 for sp_, 1 for s_o, 0 for _po; its two key columns go to the
+ *                 remaining triple columns in S, P, O order (train_KvsAll.py:165-170)
+ * examples  int64 [n] on the device: the batch; a number may occur more than once.  A number outside
+ *           [0, types[num_types-1].last) is read as the nearest valid one (nothing is read out of bounds).
+ * nnz_cap   the label entries the batch form holds; the caller computes the batch's label count on the host from its own
+ *           copy of the offsets.  Label positions >= nnz_cap are copied to neither form.
+ *
+ * Batch form (queries, query_type, label_coords, triples: all four or none; the last two may be NULL when nnz_cap == 0)
+ * -- the collate function's dictionary:
+ *   queries int64 [n, 2], query_type int64 [n], label_coords int32 [nnz_cap, 2] = (batch row, label), triples int64
+ *   [nnz_cap, 3]; rows in batch order, the labels of a row in index order.  Entries at label positions >= the batch's
+ *   label count are left as they are.
+ * Typed form (typed == NULL or [num_types]; ids, rowptr, col required -- ids / col may be NULL at capacity 0 --, weight
+ * and rows optional, each type its own):
+ *   ids int64 [rows_cap, 2], rowptr int64 [rows_cap + 1], col int64 [lab_cap], weight float32 [rows_cap], rows int64
+ *   [rows_cap].  The real rows are the type's batch rows in batch order with their labels in index order, weight =
+ *   `weight`, rows = the batch row.  The remaining rows are padding: ids (0, 0), ONE label 0 each (rowptr goes on in
+ *   steps of 1), weight 0, rows -1; col is 0 beyond the real labels.  rows_cap == n_t and lab_cap == nnz_t: the exact
+ *   CSR.
+ * counts (NULL or int64 [3 * num_types]): per type n_t, nnz_t, fits; fits = 1 iff n_t <= rows_cap and
+ *   nnz_t + (rows_cap - n_t) <= lab_cap (1 without a typed form).  The contents of the typed outputs of a type with
+ *   fits == 0 are unspecified; nothing is written outside any output's stated extent in any case.
+ * workspace: device scratch of kge_kvsall_collate_workspace_bytes(n) = 8 * (2 n + 4) bytes, 8-byte aligned (too small:
+ *   KGE_ERR_WORKSPACE).
+ * Two launches on `stream` (the scans in one workgroup, then the label copy); no allocation, no host wait, capturable.
+ * Rows without labels (offsets[e] == offsets[e + 1]) are legal.  n == 0: KGE_OK, nothing written.
+ * KGE_ERR_INVALID_ARG: num_types outside 1..3, a NULL index array, last values that decrease or no example at all, a
+ * target_col outside 0..2, negative sizes or capacities, examples / workspace NULL, a batch or typed form given in part.
+ * The scans run in ONE workgroup: n > KGE_KVSALL_COLLATE_MAX_N (2^20) is KGE_ERR_UNSUPPORTED, as is nnz_cap >= 2^31
+ * (label_coords is int32). */
+#define KGE_KVSALL_COLLATE_MAX_N (1 << 20)
+typedef struct kge_kvsall_index {
+  const int64_t* keys;
+  const int64_t* offsets;
+  const int64_t* values;
+  int64_t last;
+  int32_t target_col;
+  int32_t reserved_; /* 0 */
+} kge_kvsall_index;
+typedef struct kge_kvsall_typed {
+  int64_t* ids;
+  int64_t* rowptr;
+  int64_t* col;
+  float* weight;
+  int64_t* rows;
+  int64_t rows_cap;
+  int64_t lab_cap;
+} kge_kvsall_typed;
+int64_t kge_kvsall_collate_workspace_bytes(int64_t n);
+int kge_kvsall_collate(const kge_kvsall_index* types, int num_types, const int64_t* examples, int64_t n, int64_t nnz_cap,
+                       int64_t* queries, int64_t* query_type, int32_t* label_coords, int64_t* triples,
+                       const kge_kvsall_typed* typed, float weight, int64_t* counts, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* The two row moves of the entity-sharded exchange (kge_amd/sharded.py: ShardedEntityTable.exchange_rows),
  * the id arithmetic evaluated inside the kernel, one launch each:
  *   kge_shard_gather   t->ent = THIS RANK's rows [lo, lo + t->num_ent) of the entity table.  For j < num_ids (1 or 2

@@ -84,6 +84,18 @@ class KgeFilterQuery(ctypes.Structure):
                 ("mult", c_i64), ("begin", c_vp), ("end", c_vp)]
 
 
+class KgeKvsallIndex(ctypes.Structure):
+    _fields_ = [("keys", c_vp), ("offsets", c_vp), ("values", c_vp), ("last", c_i64), ("target_col", ctypes.c_int32),
+                ("reserved_", ctypes.c_int32)]
+
+
+class KgeKvsallTyped(ctypes.Structure):
+    _fields_ = [("ids", c_vp), ("rowptr", c_vp), ("col", c_vp), ("weight", c_vp), ("rows", c_vp), ("rows_cap", c_i64),
+                ("lab_cap", c_i64)]
+
+
+KVSALL_COLLATE_MAX_N = 1 << 20  # KGE_KVSALL_COLLATE_MAX_N
+
 # every symbol include/kge_amd.h declares: name -> (restype, argtypes)
 _PT = ctypes.POINTER(KgeTables)
 PROTOTYPES = {
@@ -120,6 +132,10 @@ PROTOTYPES = {
                                    c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_neg_sample": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,
                                       c_vp, c_i64, c_vp, c_vp, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "kge_kvsall_collate_workspace_bytes": (c_i64, [c_i64]),
+    "kge_kvsall_collate": (ctypes.c_int, [ctypes.POINTER(KgeKvsallIndex), ctypes.c_int, c_vp, c_i64, c_i64, c_vp, c_vp,
+                                          c_vp, c_vp, ctypes.POINTER(KgeKvsallTyped), ctypes.c_float, c_vp, c_vp, c_i64,
+                                          c_vp]),
     "kge_shard_gather": (ctypes.c_int, [_PT, c_i64, ctypes.POINTER(KgeIndex), ctypes.c_int, c_i64, c_vp, c_i64,
                                         KgeIndex, c_vp, c_i64, c_vp]),
     "kge_shard_pick": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_int,

@@ -111,6 +111,11 @@ int run_neg_sample(long long n, long long K, long long vocab, int slot, unsigned
                    const float* alias_prob, const long long* alias_idx, const long long* keys, long long num_keys,
                    const long long* starts, const long long* values, const Index& a, const Index& b, long long mult,
                    long long* out, long long ld, int* stats, hipStream_t st);
+long long kvsall_collate_workspace_bytes(long long n);
+int run_kvsall_collate(const kge_kvsall_index* types, int num_types, const long long* examples, long long n,
+                       long long nnz_cap, long long* queries, long long* query_type, int* label_coords,
+                       long long* triples, const kge_kvsall_typed* typed, float weight, long long* counts, void* ws,
+                       hipStream_t st);
 int run_shard_rows(const ShardJob& a, const ShardJob& b, const ShardJob& c, int rowbytes01, int rowbytes2, int esize,
                    hipStream_t st);
 int run_rank(const float* scores, long long lds, long long n, long long c,
@@ -899,6 +904,39 @@ int kge_neg_sample(int64_t n, int64_t K, int64_t vocab, int slot, uint64_t seed,
                         (const long long*)sorted_keys, num_keys, (const long long*)starts, (const long long*)values,
                         make_index(sorted_keys ? a : none), make_index(sorted_keys ? b : none), mult, (long long*)out, ld,
                         stats, (hipStream_t)stream);
+}
+
+int64_t kge_kvsall_collate_workspace_bytes(int64_t n) { return n > 0 ? kvsall_collate_workspace_bytes(n) : 0; }
+
+int kge_kvsall_collate(const kge_kvsall_index* types, int num_types, const int64_t* examples, int64_t n, int64_t nnz_cap,
+                       int64_t* queries, int64_t* query_type, int32_t* label_coords, int64_t* triples,
+                       const kge_kvsall_typed* typed, float weight, int64_t* counts, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  if (!types || num_types < 1 || num_types > 3 || n < 0 || nnz_cap < 0 || workspace_bytes < 0) return KGE_ERR_INVALID_ARG;
+  int64_t prev = 0;
+  for (int t = 0; t < num_types; ++t) {
+    const kge_kvsall_index& ix = types[t];
+    if (!ix.keys || !ix.offsets || !ix.values || ix.last < prev || ix.target_col < 0 || ix.target_col > 2)
+      return KGE_ERR_INVALID_ARG;
+    prev = ix.last;
+    if (typed) {
+      const kge_kvsall_typed& ty = typed[t];
+      if (ty.rows_cap < 0 || ty.lab_cap < 0 || !ty.rowptr) return KGE_ERR_INVALID_ARG;
+      if ((ty.rows_cap > 0 && !ty.ids) || (ty.lab_cap > 0 && !ty.col)) return KGE_ERR_INVALID_ARG;  // (empty: no address)
+    }
+  }
+  if (n == 0) return KGE_OK;
+  // the batch form comes whole or not at all (its label arrays need no address when they hold nothing)
+  if ((queries == nullptr) != (query_type == nullptr) || (label_coords == nullptr) != (triples == nullptr))
+    return KGE_ERR_INVALID_ARG;
+  if (queries ? (nnz_cap > 0 && !label_coords) : label_coords != nullptr) return KGE_ERR_INVALID_ARG;
+  if (!examples || !workspace || prev < 1 || ((uintptr_t)workspace & 7)) return KGE_ERR_INVALID_ARG;
+  if (n > KGE_KVSALL_COLLATE_MAX_N || nnz_cap >= (1ll << 31)) return KGE_ERR_UNSUPPORTED;
+  if (workspace_bytes < kvsall_collate_workspace_bytes(n)) return KGE_ERR_WORKSPACE;
+  return run_kvsall_collate(types, num_types, (const long long*)examples, n, nnz_cap, (long long*)queries,
+                            (long long*)query_type, label_coords, (long long*)triples, typed, weight, (long long*)counts,
+                            workspace, (hipStream_t)stream);
 }
 
 int kge_shard_gather(const kge_tables* t, int64_t lo, const kge_index* ids, int num_ids, int64_t n, void* send,

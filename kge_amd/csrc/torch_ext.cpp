@@ -562,6 +562,72 @@ std::vector<at::Tensor> neg_sample(const at::Tensor& like, int64_t n, int64_t K,
   return {out, stats};
 }
 
+// ---- a KvsAll batch collated on the device (kge_kvsall_collate; train_KvsAll.py:118-201 + the per-type CSR cut).
+// keys / offsets / values: the index arrays of each query type (int64, on the GPU), lasts / target_cols per type; caps
+// empty (no typed form) or (rows_cap, lab_cap) per type, flat.  -> [queries, query_type, label_coords, triples] if
+// want_batch, then (ids, rowptr, col, weight, rows) per type if caps, then counts int64 [num_types, 3].
+std::vector<at::Tensor> kvsall_collate(const at::Tensor& examples, const std::vector<at::Tensor>& keys,
+                                       const std::vector<at::Tensor>& offsets, const std::vector<at::Tensor>& values,
+                                       const std::vector<int64_t>& lasts, const std::vector<int64_t>& target_cols,
+                                       int64_t nnz, bool want_batch, const std::vector<int64_t>& caps, double weight) {
+  TORCH_CHECK(examples.is_cuda(), "kge_amd: kvsall_collate builds the batch on a GPU (no CPU path)");
+  const size_t T = keys.size();
+  TORCH_CHECK_VALUE(T >= 1 && T <= 3 && offsets.size() == T && values.size() == T && lasts.size() == T &&
+                        target_cols.size() == T && (caps.empty() || caps.size() == 2 * T),
+                    "kge_amd: kvsall_collate: 1 to 3 query types, every list one entry per type");
+  TORCH_CHECK_VALUE(examples.scalar_type() == at::kLong && examples.dim() == 1 && examples.is_contiguous() && nnz >= 0,
+                    "kge_amd: kvsall_collate: examples is a contiguous int64 vector");
+  const auto ptr = [&](const at::Tensor& t, const char* what) -> const int64_t* {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == examples.get_device(), "kge_amd: kvsall_collate: ", what, " on ", t.device());
+    TORCH_CHECK_VALUE(t.scalar_type() == at::kLong && t.is_contiguous(), "kge_amd: kvsall_collate: ", what, ": dtype / layout");
+    return t.data_ptr<int64_t>();
+  };
+  kge_kvsall_index ix[3];
+  kge_kvsall_typed ty[3];
+  const int64_t n = examples.numel();
+  const auto i64 = examples.options();
+  std::vector<at::Tensor> res;
+  at::Tensor ws, counts;
+  try {
+    if (want_batch) {
+      res.push_back(at::empty({n, 2}, i64));
+      res.push_back(at::empty({n}, i64));
+      res.push_back(at::empty({nnz, 2}, i64.dtype(at::kInt)));
+      res.push_back(at::empty({nnz, 3}, i64));
+    }
+    for (size_t t = 0; t < T; ++t) {
+      int64_t prev = t ? lasts[t - 1] : 0;
+      TORCH_CHECK_VALUE(lasts[t] >= prev && keys[t].numel() == 2 * (lasts[t] - prev) &&
+                            offsets[t].numel() == lasts[t] - prev + 1,
+                        "kge_amd: kvsall_collate: keys [M, 2] and offsets [M + 1] with M = the type's examples");
+      ix[t] = kge_kvsall_index{ptr(keys[t], "keys"), ptr(offsets[t], "offsets"), ptr(values[t], "values"), lasts[t],
+                               (int32_t)target_cols[t], 0};
+      if (!caps.empty()) {
+        const int64_t rc = caps[2 * t], lc = caps[2 * t + 1];
+        TORCH_CHECK_VALUE(rc >= 0 && lc >= 0, "kge_amd: kvsall_collate: negative capacity");
+        at::Tensor ids = at::empty({rc, 2}, i64), rp = at::empty({rc + 1}, i64), col = at::empty({lc}, i64);
+        at::Tensor w = at::empty({rc}, i64.dtype(at::kFloat)), rows = at::empty({rc}, i64);
+        ty[t] = kge_kvsall_typed{ids.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
+                                 w.data_ptr<float>(), rows.data_ptr<int64_t>(), rc, lc};
+        res.insert(res.end(), {ids, rp, col, w, rows});
+      }
+    }
+    counts = at::empty({(int64_t)T, 3}, i64);
+    ws = at::empty({kge_kvsall_collate_workspace_bytes(n) / 8}, i64);
+  } catch (const c10::OutOfMemoryError& e) {
+    TORCH_CHECK(false, "CUDA out of memory (kge_amd, ROCm: ", e.what_without_backtrace(), ")");
+  }
+  check(kge_kvsall_collate(ix, (int)T, examples.data_ptr<int64_t>(), n, nnz,
+                           want_batch ? res[0].data_ptr<int64_t>() : nullptr,
+                           want_batch ? res[1].data_ptr<int64_t>() : nullptr,
+                           want_batch ? res[2].data_ptr<int32_t>() : nullptr,
+                           want_batch ? res[3].data_ptr<int64_t>() : nullptr, caps.empty() ? nullptr : ty, (float)weight,
+                           counts.data_ptr<int64_t>(), n ? ws.data_ptr() : nullptr, ws.numel() * 8, stream_of(examples)),
+        "kge_kvsall_collate");
+  res.push_back(counts);
+  return res;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -591,4 +657,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ns_loss_parts", &ns_loss_parts,
           "negative-sampling loss of one slot from (pos [n], neg [n, K]): (loss_rows, g_pos, g_neg)");
   mod.def("neg_sample", &neg_sample, "one slot's negative samples drawn, filtered and redrawn on the device: (out, stats)");
+  mod.def("kvsall_collate", &kvsall_collate,
+          "a KvsAll batch from its example numbers, on the device: the collate dictionary and / or the per-type CSR");
 }

@@ -21,7 +21,7 @@ from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT
                    SCORERS, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
 
 __all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "shared_samples",
-           "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "neg_sample", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
+           "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "neg_sample", "kvsall_collate", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
            "FLAG_SPLIT_QUERY", "reserve_cus", "Queries", "build_queries", "score_queries", "ScorePipeline"]
 
 
@@ -1154,6 +1154,112 @@ def neg_sample(n: int, K: int, vocab: int, slot: int, seed: int, call: int, alia
             starts, values, ia, ib, int(mult), out.data_ptr(), out.stride(0) if n > 1 and K > 0 else max(K, 1),
             stats.data_ptr() if want_stats else None, _stream_handle(device)), "kge_neg_sample")
     return (out, stats) if want_stats else out
+
+
+KVSALL_COLLATE_MAX_N = _lib.KVSALL_COLLATE_MAX_N
+
+
+def kvsall_collate(types, examples: torch.Tensor, nnz: int, batch: bool = True, caps=None, weight: float = 1.0, out=None):
+    """A KvsAll batch built on the GPU from its example numbers (kge_kvsall_collate): what TrainingJobKvsAll's collate
+    function returns (train_KvsAll.py:118-201) and / or the per-type CSR the fused KvsAll losses read.
+      types     per query type, in the job's order: (keys int64 [M, 2], offsets int64 [M + 1], values int64 [.], last,
+                target_col) -- the KvsAllIndex arrays on the GPU, the example number right after the type's last example
+                and the triple column of its labels (sp_: 2, s_o: 1, _po: 0)
+      examples  int64 [n] on the GPU, numbers in the concatenated numbering of the types
+      nnz       the batch's label count, computed by the caller on the host (the extent of label_coords / triples, and
+                the number of label positions copied)
+      batch     the dictionary form: queries [n, 2], query_type_indexes [n], label_coords int32 [nnz, 2], triples [nnz, 3]
+      caps      None, or per type (rows_cap, lab_cap): the typed form (ids [rows_cap, 2], rowptr [rows_cap + 1], col
+                [lab_cap], weight float32 [rows_cap], rows [rows_cap]) -- real rows first, then padding rows of query
+                (0, 0) with the single label 0, weight 0 and rows -1; exact capacities give the unpadded CSR
+      out       None, or preallocated outputs under the names of the result (plus "workspace": int64 [2 n + 4]); what is
+                missing is allocated.  A typed entry is (ids, rowptr, col, weight or None, rows or None).
+    -> {"queries", "query_type_indexes", "label_coords", "triples"} if batch, {"typed": [...]} if caps, and "counts":
+    int64 [num_types, 3] = (n_t, nnz_t, fits) on the GPU.  Two launches, no host wait."""
+    if not (torch.is_tensor(examples) and examples.is_cuda):
+        where = examples.device if torch.is_tensor(examples) else type(examples).__name__
+        raise RuntimeError(f"kge_amd: kvsall_collate builds the batch on a GPU, not on '{where}' (no CPU path)")
+    device = examples.device
+    if not (examples.dtype == torch.int64 and examples.dim() == 1 and examples.is_contiguous()):
+        raise ValueError("kge_amd: kvsall_collate: examples is a contiguous int64 vector")
+    T, n, nnz = len(types), int(examples.numel()), int(nnz)
+    if not 1 <= T <= 3 or (caps is not None and len(caps) != T):
+        raise ValueError("kge_amd: kvsall_collate: 1 to 3 query types, one (rows_cap, lab_cap) pair per type")
+    if n > KVSALL_COLLATE_MAX_N:
+        raise ValueError(f"kge_amd: kvsall_collate: a batch of {n} examples (at most {KVSALL_COLLATE_MAX_N})")
+    prev = 0
+    for keys, offsets, values, last, target in types:
+        for x, what in ((keys, "keys"), (offsets, "offsets"), (values, "values")):
+            if not (torch.is_tensor(x) and x.device == device and x.dtype == torch.int64 and x.is_contiguous()):
+                raise ValueError(f"kge_amd: kvsall_collate: {what} must be a contiguous int64 tensor on {device}")
+        if last < prev or keys.numel() != 2 * (last - prev) or offsets.numel() != last - prev + 1 or target not in (0, 1, 2):
+            raise ValueError("kge_amd: kvsall_collate: keys [M, 2], offsets [M + 1], M = last - the previous type's last")
+        prev = last
+    ex = _ext()
+    if ex and out is None:
+        with _on_device(device):
+            flat = ex.kvsall_collate(examples, [t[0] for t in types], [t[1] for t in types], [t[2] for t in types],
+                                     [int(t[3]) for t in types], [int(t[4]) for t in types], nnz, bool(batch),
+                                     [int(c) for pair in (caps or ()) for c in pair], float(weight))
+        res, k = {}, 0
+        if batch:
+            res.update(zip(("queries", "query_type_indexes", "label_coords", "triples"), flat[:4]))
+            k = 4
+        if caps is not None:
+            res["typed"] = [tuple(flat[k + 5 * t:k + 5 * t + 5]) for t in range(T)]
+        res["counts"] = flat[-1]
+        return res
+    out = dict(out or {})
+
+    def take(name, shape, dtype):
+        x = out.get(name)
+        if x is None:
+            return _empty(shape, device, dtype)
+        if not (x.device == device and x.dtype == dtype and tuple(x.shape) == tuple(shape) and x.is_contiguous()):
+            raise ValueError(f"kge_amd: kvsall_collate: out[{name!r}] must be a contiguous {dtype} {tuple(shape)} on {device}")
+        return x
+
+    res = {}
+    if batch:
+        res["queries"] = take("queries", (n, 2), torch.int64)
+        res["query_type_indexes"] = take("query_type_indexes", (n,), torch.int64)
+        res["label_coords"] = take("label_coords", (nnz, 2), torch.int32)
+        res["triples"] = take("triples", (nnz, 3), torch.int64)
+    typed_arr = None
+    if caps is not None:
+        given = out.get("typed") or [None] * T
+        typed_arr, res["typed"] = (_lib.KgeKvsallTyped * T)(), []
+        for t, (rc, lc) in enumerate(caps):
+            rc, lc = int(rc), int(lc)
+            if rc < 0 or lc < 0:
+                raise ValueError("kge_amd: kvsall_collate: negative capacity")
+            if given[t] is None:
+                tup = (_empty((rc, 2), device, torch.int64), _empty((rc + 1,), device, torch.int64),
+                       _empty((lc,), device, torch.int64), _empty((rc,), device, torch.float32),
+                       _empty((rc,), device, torch.int64))
+            else:
+                tup = tuple(given[t])
+                want = (((rc, 2), torch.int64), ((rc + 1,), torch.int64), ((lc,), torch.int64), ((rc,), torch.float32),
+                        ((rc,), torch.int64))
+                for x, (shape, dtype) in zip(tup, want):
+                    if x is not None and not (x.device == device and x.dtype == dtype and tuple(x.shape) == shape
+                                              and x.is_contiguous()):
+                        raise ValueError(f"kge_amd: kvsall_collate: a typed output must be a contiguous {dtype} {shape}")
+                if len(tup) != 5 or any(x is None for x in tup[:3]):
+                    raise ValueError("kge_amd: kvsall_collate: a typed entry is (ids, rowptr, col, weight | None, rows | None)")
+            typed_arr[t] = _lib.KgeKvsallTyped(*[None if x is None else x.data_ptr() for x in tup], rc, lc)
+            res["typed"].append(tup)
+    res["counts"] = take("counts", (T, 3), torch.int64)
+    ws = take("workspace", (2 * n + 4,), torch.int64)
+    arr = (_lib.KgeKvsallIndex * T)(*[_lib.KgeKvsallIndex(k.data_ptr(), o.data_ptr(), v.data_ptr(), int(last), int(tc), 0)
+                                      for k, o, v, last, tc in types])
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_kvsall_collate(
+            arr, T, examples.data_ptr(), n, nnz, *[res[k].data_ptr() if batch else None
+                                                   for k in ("queries", "query_type_indexes", "label_coords", "triples")],
+            typed_arr, float(weight), res["counts"].data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_handle(device)),
+            "kge_kvsall_collate")
+    return res
 
 
 def shard_gather(t: Tables, lo: int, ids, rel_idx, send: torch.Tensor, rel_out=None):

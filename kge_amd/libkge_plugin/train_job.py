@@ -84,6 +84,63 @@ def _has_repeated_labels(coords) -> bool:
     return bool((key[1:] == key[:-1]).any())
 
 
+def _kvsall_per_type_cut(queries, coords, qtype, query_types, batch_size, row0=0):
+    """A KvsAll subbatch's `label_coords` ([nnz, 2]: batch row, label; rows ascending, the whole batch's) cut into one
+    CSR per query type: -> (per_type, totals) with per_type[query_type] = (query column 0, query column 1, rowptr, col)
+    over the subbatch's rows of that type in batch order, totals[query_type] = its label count (one host read each).
+    queries / qtype are the subbatch's, row0 its first batch row; a type without a row is left out."""
+    # label ranges of all batch rows: counts -> offsets (no host sync)
+    counts = torch.bincount(coords[:, 0].long(), minlength=batch_size)
+    offsets = torch.zeros(batch_size + 1, dtype=torch.long, device=coords.device)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    per_type, totals = {}, {}
+    for query_type_index, query_type in enumerate(query_types):
+        examples = (qtype == query_type_index).nonzero(as_tuple=False).view(-1)
+        if len(examples) == 0:
+            continue
+        rows = examples + row0
+        cnt = counts[rows]
+        rowptr = torch.zeros(len(rows) + 1, dtype=torch.long, device=cnt.device)
+        torch.cumsum(cnt, 0, out=rowptr[1:])
+        total = int(rowptr[-1])
+        idx = torch.repeat_interleave(offsets[rows] - rowptr[:-1], cnt, output_size=total) \
+            + torch.arange(total, device=cnt.device)
+        per_type[query_type] = (queries[examples, 0], queries[examples, 1], rowptr, coords[idx, 1].long())
+        totals[query_type] = total
+    return per_type, totals
+
+
+def _kvsall_pad_inputs(per_type, batch_size, dev, caps, query_types=("sp_", "_po")):
+    """The per-type CSRs padded to caps = (rows per type, label entries per type): per query type (ids [rows, 2], rowptr
+    [rows + 1], col [labels], weight [rows]) in one flat list, or None if a type does not fit.  A padding row is query
+    (0, 0) with the single label 0 and weight 0; a real row weighs 1 / batch_size; a type without rows is all padding."""
+    rows_cap, lab_cap = caps
+    out = []
+    for qt in query_types:
+        if qt in per_type:
+            q0, q1, rowptr, col = per_type[qt]
+            n, nnz = len(q0), int(col.numel())
+        else:
+            q0 = q1 = col = torch.zeros(0, dtype=torch.long, device=dev)
+            rowptr = torch.zeros(1, dtype=torch.long, device=dev)
+            n, nnz = 0, 0
+        pad = rows_cap - n
+        if pad < 0 or nnz + pad > lab_cap:
+            return None
+        ids = torch.zeros(rows_cap, 2, dtype=torch.long, device=dev)
+        ids[:n, 0], ids[:n, 1] = q0, q1
+        rp = torch.empty(rows_cap + 1, dtype=torch.long, device=dev)
+        rp[:n + 1] = rowptr
+        if pad:
+            rp[n + 1:] = nnz + torch.arange(1, pad + 1, device=dev)
+        cl = torch.zeros(lab_cap, dtype=torch.long, device=dev)
+        cl[:nnz] = col
+        w = torch.zeros(rows_cap, dtype=torch.float32, device=dev)
+        w[:n] = 1.0 / batch_size
+        out += [ids, rp, cl, w]
+    return out
+
+
 def _declined_late(what):
     raise RuntimeError(f"kge_amd: {what} declined after part of the subbatch was already back-propagated "
                        "(tables or options changed inside a subbatch)")
@@ -380,6 +437,14 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         self._skip_optimizer_step = False
         _set_fused_dist_loss(self, "hip_KvsAll")
         _set_fused_f32_loss(self, "hip_KvsAll")
+        # the batch built on the device (hip_KvsAll.device_collate, false by default: the reference's collate function);
+        # the collator itself is made where the loader is (_get_collate_fun: the indexes exist by then)
+        try:
+            self._device_collate = bool(config.get("hip_KvsAll.device_collate"))
+        except KeyError:
+            self._device_collate = False
+        self._collator = None
+        self._inputs_hook = None      # tests: called with ("per_type" | "graph_inputs", value) per subbatch
         if self.__class__ == HipTrainingJobKvsAll:
             for f in Job.job_created_hooks:
                 f(self)
@@ -393,31 +458,57 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
     # three such batches in a row grow the capacities and capture again.
     def _graph_inputs(self, per_type, batch_size, dev):
         """-> the eight padded input tensors of the captured step, or None if the batch does not fit."""
-        rows_cap, lab_cap = self._graph_caps
+        return _kvsall_pad_inputs(per_type, batch_size, dev, self._graph_caps)
+
+    def _device_graph_inputs(self, batch, subbatch_slice, batch_size, dev):
+        """The same eight tensors straight from the collator's padded typed form (hip_KvsAll.device_collate); a query
+        type the job does not ask is all padding, as in _kvsall_pad_inputs."""
+        ex, dev_ex = batch["examples"][subbatch_slice], batch["examples_device"][subbatch_slice]
+        typed = self._collator.typed(ex, caps=self._graph_caps, weight=1.0 / batch_size, device_examples=dev_ex)
+        if typed is None:
+            return None
+        by_type = dict(zip(self.query_types, typed))
         out = []
         for qt in ("sp_", "_po"):
-            if qt in per_type:
-                q0, q1, rowptr, col = per_type[qt]
-                n, nnz = len(q0), int(col.numel())
+            if qt in by_type:
+                out += list(by_type[qt][:4])
             else:
-                q0 = q1 = col = torch.zeros(0, dtype=torch.long, device=dev)
-                rowptr = torch.zeros(1, dtype=torch.long, device=dev)
-                n, nnz = 0, 0
-            pad = rows_cap - n
-            if pad < 0 or nnz + pad > lab_cap:
-                return None
-            ids = torch.zeros(rows_cap, 2, dtype=torch.long, device=dev)
-            ids[:n, 0], ids[:n, 1] = q0, q1
-            rp = torch.empty(rows_cap + 1, dtype=torch.long, device=dev)
-            rp[:n + 1] = rowptr
-            if pad:
-                rp[n + 1:] = nnz + torch.arange(1, pad + 1, device=dev)
-            cl = torch.zeros(lab_cap, dtype=torch.long, device=dev)
-            cl[:nnz] = col
-            w = torch.zeros(rows_cap, dtype=torch.float32, device=dev)
-            w[:n] = 1.0 / batch_size
-            out += [ids, rp, cl, w]
+                out += _kvsall_pad_inputs({}, batch_size, dev, self._graph_caps, query_types=(qt,))
         return out
+
+    def _device_per_type(self, batch, subbatch_slice, batch_size, rows_of):
+        """per_type of _kvsall_per_type_cut from the collator's exact-size typed form: no torch op sequence, no host wait."""
+        ex, dev_ex = batch["examples"][subbatch_slice], batch["examples_device"][subbatch_slice]
+        typed = self._collator.typed(ex, weight=1.0 / batch_size, device_examples=dev_ex)
+        return {qt: (ids[:, 0], ids[:, 1], rowptr, col)
+                for qt, (ids, rowptr, col, _, _) in zip(self.query_types, typed) if qt in rows_of}
+
+    # ---- hip_KvsAll.device_collate: the batch is built on the GPU (kge_amd.kvsall.DeviceKvsAllCollator ->
+    # kge_kvsall_collate) from its example numbers instead of the reference's collate function on the host
+    # (train_KvsAll.py:118-201, a Python loop over the examples) and the copy of label_coords.  The loader hands over the
+    # example numbers alone; _prepare_batch copies them and fills in the reference's dictionary as device tensors, so
+    # the reference's _process_subbatch / _process_batch work on it unmodified; the fused paths take their per-type CSR
+    # (padded for the captured step) from the collator as well.  On a CPU job the option is ignored.
+    def _get_collate_fun(self):
+        if not self._device_collate or not str(self.device).startswith("cuda"):
+            return super()._get_collate_fun()
+        from ..kvsall import DeviceKvsAllCollator
+        self._collator = DeviceKvsAllCollator(self.query_indexes, self.query_types, self.device)
+
+        def collate(batch):
+            return {"examples": torch.as_tensor(batch, dtype=torch.long)}
+
+        return collate
+
+    def _prepare_batch(self, batch_index, batch, result):
+        if self._collator is None:
+            return super()._prepare_batch(batch_index, batch, result)
+        result.prepare_time -= time.time()
+        ex = batch["examples"]
+        dev_ex = batch["examples_device"] = ex.to(self.device)
+        batch.update(self._collator.batch(ex, device_examples=dev_ex))
+        result.size = len(ex)
+        result.prepare_time += time.time()
 
     def _graph_loss(self, ids_sp, rp_sp, cl_sp, w_sp, ids_po, rp_po, cl_po, w_po):
         offset = _plain_bce(self.loss)
@@ -426,8 +517,9 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
             cl_po, 0.0 if offset is None else offset)
         return (rows_sp * w_sp).sum() + (rows_po * w_po).sum()
 
-    def _graph_step_for(self, batch_index, batch, subbatch_slice, per_type, totals):
-        """The GraphedStep for this batch (made or re-made when the capacities change), or None."""
+    def _graph_step_for(self, batch_index, batch, subbatch_slice, rows_of, totals):
+        """The GraphedStep for this batch (made or re-made when the capacities change), or None.  rows_of / totals: the
+        subbatch's rows and label entries per query type."""
         if self._graph_step_ok is False or self.is_forward_only:
             return None
         n = len(batch["queries"])
@@ -450,8 +542,8 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         if caps is None or self._graph_overflows >= 3:
             # capacities from this batch with head room (the split of a batch into sp_ / _po queries is binomial, the
             # label counts follow the data's degree distribution); never below the previous ones
-            need_rows = max([len(v[0]) for v in per_type.values()] + [1])
-            need_lab = max([totals[k] for k in per_type] + [1])
+            need_rows = max(list(rows_of.values()) + [1])
+            need_lab = max([totals[k] for k in rows_of] + [1])
             up = lambda x, m: (int(x) + m - 1) // m * m
             rows_cap = min(up(max(need_rows * 1.15 + 16, (caps or (0, 0))[0]), 32), up(n, 32))
             rows_cap = max(rows_cap, up(need_rows, 32))
@@ -476,35 +568,60 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
         # (a batch with a repeated (query, label) pair -- a split that repeats a triple -- takes the composed path)
         # hip_KvsAll.fused_f32_loss (hip_complex / hip_distmult in float32, label smoothing included): the same per-type loop
         dist = dist or (not takes and _model_takes_f32_loss(self.model))
-        dist = dist and self._fused_ok() and not _has_repeated_labels(batch["label_coords"])
+        # (with hip_KvsAll.device_collate the question is asked of the indexes, once, at set-up: conservative)
+        dist = dist and self._fused_ok() and not (
+            any(self._collator.repeated_labels) if self._collator is not None
+            else _has_repeated_labels(batch["label_coords"]))
         if not self._fused_ok() or not (takes or dist):
             return super()._process_subbatch(batch_index, batch, subbatch_slice, result)
         batch_size = result.size
         result.prepare_time -= time.time()
         queries = batch["queries"][subbatch_slice].to(self.device)
-        coords = batch["label_coords"]  # [nnz, 2] (batch row, label), rows ascending; on the device
-        qtype = batch["query_type_indexes"][subbatch_slice].to(self.device)
-        row0 = subbatch_slice.start or 0
-        # label ranges of all batch rows: counts -> offsets (no host sync)
-        counts = torch.bincount(coords[:, 0].long(), minlength=batch_size)
-        offsets = torch.zeros(batch_size + 1, dtype=torch.long, device=coords.device)
-        torch.cumsum(counts, 0, out=offsets[1:])
+        if self._collator is None:
+            coords = batch["label_coords"]  # [nnz, 2] (batch row, label), rows ascending; on the device
+            qtype = batch["query_type_indexes"][subbatch_slice].to(self.device)
+            per_type, totals = _kvsall_per_type_cut(queries, coords, qtype, self.query_types, batch_size,
+                                                    subbatch_slice.start or 0)
+            rows_of = {k: len(v[0]) for k, v in per_type.items()}
+        else:  # sizes on the host from the collator's copy of the offsets; the tensors when a path asks for them
+            n_t, nnz_t = self._collator.sizes(batch["examples"][subbatch_slice])
+            rows_of = {qt: int(n) for qt, n in zip(self.query_types, n_t) if n > 0}
+            totals = {qt: int(z) for qt, n, z in zip(self.query_types, n_t, nnz_t) if n > 0}
+            per_type = None
         result.prepare_time += time.time()
         offset, ls = _plain_bce(self.loss), float(self.label_smoothing)
-        per_type, totals = {}, {}
-        for query_type_index, query_type in enumerate(self.query_types):
-            examples = (qtype == query_type_index).nonzero(as_tuple=False).view(-1)
-            if len(examples) == 0:
-                continue
-            rows = examples + row0
-            cnt = counts[rows]
-            rowptr = torch.zeros(len(rows) + 1, dtype=torch.long, device=cnt.device)
-            torch.cumsum(cnt, 0, out=rowptr[1:])
-            total = int(rowptr[-1])
-            idx = torch.repeat_interleave(offsets[rows] - rowptr[:-1], cnt, output_size=total) \
-                + torch.arange(total, device=cnt.device)
-            per_type[query_type] = (queries[examples, 0], queries[examples, 1], rowptr, coords[idx, 1].long())
-            totals[query_type] = total
+        # both query types of the subbatch: their loss rows with ONE backward (two d loss / d score passes, the gradient
+        # products once over all rows, no index_add / accumulation passes of autograd in between); the reference
+        # back-propagates the two losses one after the other -- the same gradients, accumulated
+        if (not dist and ls == 0.0 and len(rows_of) >= 1 and hasattr(self.model, "multilabel_loss_sp_po")
+                and "s_o" not in self.query_types):
+            gs = self._graph_step_for(batch_index, batch, subbatch_slice, rows_of, totals)
+            if gs is not None and gs.enabled:
+                result.prepare_time -= time.time()
+                if self._collator is None:
+                    inputs = self._graph_inputs(per_type, batch_size, queries.device)
+                else:
+                    inputs = self._device_graph_inputs(batch, subbatch_slice, batch_size, queries.device)
+                result.prepare_time += time.time()
+                if inputs is None:
+                    self._graph_overflows += 1
+                else:
+                    if self._inputs_hook is not None:
+                        self._inputs_hook("graph_inputs", inputs)
+                    self._graph_overflows = 0
+                    result.forward_time -= time.time()
+                    loss_value = gs(*inputs)
+                    self._skip_optimizer_step = True  # (replayed or eager: GraphedStep has taken the optimizer's step)
+                    self.graph_batches += 1
+                    result.avg_loss += loss_value.item()
+                    result.forward_time += time.time()
+                    return
+        if per_type is None:
+            result.prepare_time -= time.time()
+            per_type = self._device_per_type(batch, subbatch_slice, batch_size, rows_of)
+            result.prepare_time += time.time()
+        if self._inputs_hook is not None:
+            self._inputs_hook("per_type", dict(per_type))
         if "s_o" in per_type:
             # relation targets: score_so + the job's loss on the dense [n_q, R] label matrix, exactly as the reference does
             # it (train_KvsAll.py:255-258, 279-291; label smoothing is for entity targets only there, :262-266)
@@ -523,27 +640,6 @@ class HipTrainingJobKvsAll(_CudaOomText, TrainingJobKvsAll):
             if not self.is_forward_only:
                 loss_value.backward()
             result.backward_time += time.time()
-        # both query types of the subbatch: their loss rows with ONE backward (two d loss / d score passes, the gradient
-        # products once over all rows, no index_add / accumulation passes of autograd in between); the reference
-        # back-propagates the two losses one after the other -- the same gradients, accumulated
-        if (not dist and ls == 0.0 and len(per_type) >= 1 and hasattr(self.model, "multilabel_loss_sp_po")
-                and "s_o" not in self.query_types):
-            gs = self._graph_step_for(batch_index, batch, subbatch_slice, per_type, totals)
-            if gs is not None and gs.enabled:
-                result.prepare_time -= time.time()
-                inputs = self._graph_inputs(per_type, batch_size, queries.device)
-                result.prepare_time += time.time()
-                if inputs is None:
-                    self._graph_overflows += 1
-                else:
-                    self._graph_overflows = 0
-                    result.forward_time -= time.time()
-                    loss_value = gs(*inputs)
-                    self._skip_optimizer_step = True  # (replayed or eager: GraphedStep has taken the optimizer's step)
-                    self.graph_batches += 1
-                    result.avg_loss += loss_value.item()
-                    result.forward_time += time.time()
-                    return
         if not dist and ls == 0.0 and len(per_type) == 2 and hasattr(self.model, "multilabel_loss_sp_po"):
             result.forward_time -= time.time()
             (s_, p_sp, rp_sp, cl_sp), (p_po, o_, rp_po, cl_po) = per_type["sp_"], per_type["_po"]
