@@ -1126,7 +1126,7 @@ int kge_score_spo_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
  * of sum_{i,k} gout[i*ldg + k] * score(triple i with `slot` replaced by neg[i*neg_ld + k])
  * ACCUMULATED into the dense table gradients like kge_score_spo_bwd_accum.  The relation row and
  * the uncorrupted entity row of a positive are read once and their gradients summed in registers
- * over 64 negatives; only the corrupted rows stream.  `scores` = the forward output [n, num_neg]
+ * over a chunk of clamp(n * num_neg / 8192, 4, 64) negatives; only the corrupted rows stream.  `scores` = the forward output [n, num_neg]
  * (row pitch lds; needed for TransE / RotatE with l_norm != 1, may be NULL otherwise).
  * f32 tables, dim <= 1024. */
 int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o,

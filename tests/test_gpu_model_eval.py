@@ -220,7 +220,9 @@ def test_score_neg_forward_and_backward(name, l_norm, d):
     the expanded triples, for both corruptible slots, int32 and int64 samples, duplicates included."""
     if name in ("complex", "rotate") and d % 2:
         pytest.skip("even dimensionality only")
-    E, R, n, K = 60, 4, 19, 70  # K > 64: more than one chunk of negatives per positive
+    # n K = 1,330 < 5 * 8192: chunks of 4 negatives (run_neg_bwd_accum: ch = clamp(n K / 8192, 4, 64)), 18 per positive,
+    # the last 2 long; the longer chunks run in tests/test_gpu_neg_bwd.py
+    E, R, n, K = 60, 4, 19, 70
     m = _model(name, E, R, d, l_norm=l_norm).train()
     ent0 = m.get_s_embedder().weight.detach().cpu().clone()
     rel0 = m.get_p_embedder().weight.detach().cpu().clone()
