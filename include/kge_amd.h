@@ -1073,6 +1073,49 @@ int kge_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   float step_size, float bias_correction2_sqrt, double beta1, double beta2,
                   float weight_decay, float eps, void* bf16_copy, void* stream);
 
+/* kge_adam_step on up to KGE_ADAM_MAX_SEGS tables in ONE launch, with the step count kept on the device
+ * (kge/job/train.py:471-474 optimizer.step() over all parameters; kge/util/optimizer.py:15-20 with
+ * train.optimizer.default.type: Adam).  kge_adam_step takes lr / (1 - beta1^t) and sqrt(1 - beta2^t) from the host: a
+ * captured step would replay the values of the capture step for ever.  Here every parameter has a clock record in
+ * device memory; a one-workgroup kernel in front of the update advances the records of the call's non-empty segments,
+ * in float64 with IEEE division and square root:
+ *   t += 1;  beta1_pow *= beta1;  beta2_pow *= beta2;
+ *   step_size = (float)(lr / (1 - beta1_pow));  bias_correction2_sqrt = (float)sqrt(1 - beta2_pow)
+ * and the update reads the two floats of its segment's record; per element it is kge_adam_step's arithmetic, operation
+ * for operation (the same bits, given the same two floats).  A fresh record is {T, beta1^T, beta2^T, 0, 0}, written by
+ * the caller: T = 0 at the start, T = the restored step count after a checkpoint was loaded.  lr and the betas are
+ * launch arguments: a caller that replays a captured call must capture again when they change.
+ *
+ * pens != NULL: the embedders' penalty terms folded into the pass as in kge_adagrad_step_multi_penalty -- the term's
+ * gradient is added to grad (in registers; grad is not written) before weight decay and the moments, and sum |x|^p
+ * (sum |z|^3) of the PRE-step parameters is added to *value.  A segment of kind 0 is the plain update.
+ *
+ * KGE_ERR_INVALID_ARG: num_segs outside 0..KGE_ADAM_MAX_SEGS; count < 0; a NULL (non-empty segment) or not 16-byte
+ * aligned param, grad, exp_avg or exp_avg_sq; a bf16_copy that is not 8-byte aligned; a NULL (non-empty segment) or not
+ * 8-byte aligned clock; two non-empty segments with the same clock; beta1 or beta2 outside [0, 1); a penalty kind
+ * other than 0, 1, 2; kind != 0 with a NULL or misaligned value; kind 2 with count % row_dim != 0 or row_dim % 8 != 0.
+ * KGE_ERR_UNSUPPORTED: kind 1 with p outside 1..3; more than 2^31 - 1 workgroups.  num_segs == 0, or every segment
+ * empty: KGE_OK, no launch, no clock advances.  An empty segment among non-empty ones: its clock does not advance. */
+#define KGE_ADAM_MAX_SEGS 8
+typedef struct kge_adam_clock {
+  int64_t t;
+  double beta1_pow, beta2_pow;
+  float step_size, bias_correction2_sqrt;
+} kge_adam_clock;
+typedef struct kge_adam_seg {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  void* bf16_copy;            /* or NULL */
+  kge_adam_clock* clock;      /* device */
+  int64_t count;
+  double lr, beta1, beta2;
+  float weight_decay, eps;
+} kge_adam_seg;
+int kge_adam_step_multi(const kge_adam_seg* segs, const kge_penalty_seg* pens /* or NULL */, int num_segs,
+                        void* stream);
+
 /* Row-sparse Adagrad step: only the `num_rows` listed rows (unique ids, int64) of a [*, dim] table
  * have a gradient, grad_rows[r, :] belonging to row rows[r] -- torch.optim.Adagrad's update for the
  * sparse gradients of lookup_embedder.sparse: True (kge/model/embedder/lookup_embedder.yaml:78-81):

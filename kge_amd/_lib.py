@@ -70,6 +70,20 @@ class KgePenaltySeg(ctypes.Structure):
                 ("value", c_vp)]
 
 
+class KgeAdamClock(ctypes.Structure):
+    _fields_ = [("t", c_i64), ("beta1_pow", ctypes.c_double), ("beta2_pow", ctypes.c_double),
+                ("step_size", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float)]
+
+
+class KgeAdamSeg(ctypes.Structure):
+    _fields_ = [("param", c_vp), ("grad", c_vp), ("exp_avg", c_vp), ("exp_avg_sq", c_vp), ("bf16_copy", c_vp),
+                ("clock", c_vp), ("count", c_i64), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("weight_decay", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
+ADAM_MAX_SEGS = 8  # KGE_ADAM_MAX_SEGS
+
+
 class KgeRankBand(ctypes.Structure):
     _fields_ = [("table_max_norm", c_vp), ("list", c_vp), ("list_bytes", c_i64), ("status", c_vp)]
 
@@ -194,6 +208,8 @@ PROTOTYPES = {
                                        ctypes.c_float, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "kge_adam_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_float, ctypes.c_float, c_vp, c_vp]),
+    "kge_adam_step_multi": (ctypes.c_int, [ctypes.POINTER(KgeAdamSeg), ctypes.POINTER(KgePenaltySeg), ctypes.c_int,
+                                           c_vp]),
     "kge_adagrad_step_rows": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64,
                                              ctypes.c_float, ctypes.c_float, c_vp, c_i64, c_vp]),
     "kge_score_pairs_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, KgeIndex,

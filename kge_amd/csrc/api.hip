@@ -199,6 +199,7 @@ int run_adagrad(float* param, const float* grad, float* sum, long long count, fl
                 float eps, unsigned short* copy16, hipStream_t st);
 int run_adam(float* param, const float* grad, float* m1, float* m2, long long count, float step_size, float bc2_sqrt,
              float omb1, float beta2, float omb2, float weight_decay, float eps, unsigned short* copy16, hipStream_t st);
+int run_adam_multi(const kge_adam_seg* segs, const kge_penalty_seg* pens, int num, hipStream_t st);
 int run_adagrad_rows(float* param, long long param_ld, const float* grows, long long g_ld, float* sum, long long sum_ld,
                      const long long* rows, long long nrows, int dim, float minus_clr, float eps,
                      unsigned short* copy16, long long c_ld, hipStream_t st);
@@ -2270,6 +2271,29 @@ int kge_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
   return run_adam(param, grad, exp_avg, exp_avg_sq, count, step_size, bias_correction2_sqrt, (float)(1.0 - beta1),
                   (float)beta2, (float)(1.0 - beta2),
                   weight_decay, eps, (unsigned short*)bf16_copy, (hipStream_t)stream);
+}
+
+int kge_adam_step_multi(const kge_adam_seg* segs, const kge_penalty_seg* pens, int num_segs, void* stream) {
+  KGE_RANGE();
+  if (num_segs < 0 || num_segs > KGE_ADAM_MAX_SEGS || (num_segs > 0 && !segs)) return KGE_ERR_INVALID_ARG;
+  for (int j = 0; j < num_segs; ++j) {
+    const kge_adam_seg& g = segs[j];
+    if (g.count < 0 || (g.count > 0 && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq || !g.clock)))
+      return KGE_ERR_INVALID_ARG;
+    if (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15)
+      return KGE_ERR_INVALID_ARG;
+    if (((uintptr_t)g.bf16_copy | (uintptr_t)g.clock) & 7) return KGE_ERR_INVALID_ARG;
+    if (!(g.beta1 >= 0.0 && g.beta1 < 1.0 && g.beta2 >= 0.0 && g.beta2 < 1.0)) return KGE_ERR_INVALID_ARG;
+    for (int i = 0; i < j; ++i)  // a record shared by two segments would be advanced twice
+      if (g.count > 0 && segs[i].count > 0 && segs[i].clock == g.clock) return KGE_ERR_INVALID_ARG;
+    if (!pens) continue;
+    const kge_penalty_seg& q = pens[j];
+    if (q.kind < 0 || q.kind > 2) return KGE_ERR_INVALID_ARG;
+    if (q.kind != 0 && (!q.value || ((uintptr_t)q.value & 7))) return KGE_ERR_INVALID_ARG;
+    if (q.kind == 1 && (q.p < 1 || q.p > 3)) return KGE_ERR_UNSUPPORTED;
+    if (q.kind == 2 && (q.row_dim <= 0 || q.row_dim % 8 != 0 || g.count % q.row_dim != 0)) return KGE_ERR_INVALID_ARG;
+  }
+  return run_adam_multi(segs, pens, num_segs, (hipStream_t)stream);
 }
 
 int kge_adagrad_step_rows(float* param, int64_t param_ld, const float* grad_rows, int64_t grad_ld, float* state_sum,

@@ -12,7 +12,9 @@ Usage inside an unmodified LibKGE installation (config-default.yaml:137, README.
     #           eval.type: hip_sharded_entity_ranking  (entity table sharded over the ranks of a torch.distributed job:
     #           torchrun ... -m kge_amd.libkge_plugin.launch start cfg.yaml; sharded_job.py)
     # optional: train.optimizer.default.type: HipAdagrad / HipAdam  (one-pass update; args as for Adagrad / Adam,
-    #           plus bf16_copies: true to keep the bf16 scoring tables fresh without a cast)
+    #           plus bf16_copies: true to keep the bf16 scoring tables fresh without a cast; HipAdam also takes
+    #           device_step: true -- the step count on the device, one launch over all tables, folded penalty terms
+    #           and a capturable step, so hip_1vsAll / hip_KvsAll / hip_negative_sampling graph_step work under Adam)
 
 `Config._import("hip_complex")` finds hip_complex.yaml in this package (config.py:280-325)
 and `init_from(class_name, modules)` (misc.py:13-42) resolves the classes below.  They

@@ -156,7 +156,8 @@ from kge.util.loss import (BCEWithLogitsKgeLoss, KLDivWithSoftmaxKgeLoss, Margin
 
 def _optimizer_is_capturable(opt) -> bool:
     """Only optimizers whose captured step() replays correctly: kge_amd.optim.Adagrad says so itself (without lr_decay),
-    HipAdam says no (host-computed bias correction would be frozen at the capture step), of torch's own only SGD."""
+    HipAdam says no (host-computed bias correction would be frozen at the capture step) unless it keeps the step count
+    on the device (`args: {device_step: true}`: the instance says yes), of torch's own only SGD."""
     return (all(g.get("lr_decay", 0) == 0 for g in opt.param_groups)
             and bool(getattr(opt, "graph_capturable", type(opt) is torch.optim.SGD)))
 
@@ -175,8 +176,9 @@ def _no_penalty(job, batch_index, batch) -> bool:
 
 def _fold_penalties(job) -> bool:
     """The embedders' UNWEIGHTED Lp / N3 penalty terms (lookup_embedder.py:122-147 through KgeModel.penalty,
-    kge_model.py:603-649) folded into HipAdagrad's pass: their gradient is a function of the element alone, so the
-    optimizer adds it in registers and sums the term's value on the way (kge_adagrad_step_multi_penalty).  A step taken
+    kge_model.py:603-649) folded into the pass of an optimizer that offers the penalty interface -- HipAdagrad, or a
+    HipAdam with device_step: their gradient is a function of the element alone, so the optimizer adds it in registers
+    and sums the term's value on the way (kge_adagrad_step_multi_penalty, kge_adam_step_multi).  A step taken
     inside `_process_batch` (a GraphedStep, replayed or eager) then carries the penalty; TrainingJob.run_epoch still
     calls `model.penalty()` afterwards, back-propagates what it gets and writes the values to the trace
     (train.py:417-436): it gets leaf scalars holding the values the step computed -- their backward is a no-op.  A
@@ -186,13 +188,14 @@ def _fold_penalties(job) -> bool:
     -> True if every term of this model is folded (the job may capture its step), False if the model has no foldable
     shape (weighted terms, other embedders, other regularizers, another optimizer): nothing is changed then."""
     from kge.model import KgeModel, LookupEmbedder
-    from ..optim import Adagrad as HipAdagrad
+    from ..optim import Adagrad as HipAdagrad, Adam as HipAdam
     model, opt = job.model, job.optimizer
+    folds = isinstance(opt, HipAdagrad) or (isinstance(opt, HipAdam) and opt.device_step)
     if getattr(job, "_folded_penalties", None) is not None:
         return bool(job._folded_penalties)
     job._folded_penalties = []
     from .models import _FusedScoring  # (its penalty() is KgeModel.penalty behind a shortcut for "no terms")
-    if not isinstance(opt, HipAdagrad) or type(model).penalty not in (KgeModel.penalty, _FusedScoring.penalty):
+    if not folds or type(model).penalty not in (KgeModel.penalty, _FusedScoring.penalty):
         return False
     pe, se, oe = model.get_p_embedder(), model.get_s_embedder(), model.get_o_embedder()
     plan = []

@@ -1,5 +1,6 @@
-"""torch.optim.Adagrad / torch.optim.Adam with the update done by one HIP kernel per parameter
-(kge_adagrad_step, kge_adagrad_step_rows for row-sparse gradients, kge_adam_step), optionally
+"""torch.optim.Adagrad / torch.optim.Adam with the update done by HIP kernels (kge_adagrad_step_multi: every dense
+table of a device in one launch, kge_adagrad_step_rows for row-sparse gradients, kge_adam_step per parameter, or
+kge_adam_step_multi with Adam(device_step=True): the step count on the device, one launch, capturable), optionally
 maintaining the bf16 copies of the tables that mixed-precision scoring reads.
 
 Drop-in for `torch.optim.Adagrad` (same constructor arguments, same `state_dict`: per-parameter
@@ -30,7 +31,81 @@ def bf16_copy_of(param: torch.Tensor):
     return rec[0]
 
 
-class Adagrad(_TorchAdagrad):
+class _FoldedPenalties:
+    """The embedders' unweighted penalty terms inside the optimizer's own pass (kge_adagrad_step_multi_penalty,
+    kge_adam_step_multi with penalty segments): what Adagrad and the device-step Adam share."""
+
+    def _init_penalties(self):
+        self._penalties = {}       # parameter -> (kind, p, gradient factor, row_dim, value factor)
+        self._pen_acc = {}         # device -> float64 accumulators, one per parameter with a penalty
+        self._pen_slot = {}        # parameter -> index into its device's accumulators
+        self._pen_off_once = False
+
+    def set_penalty(self, param, kind: str, p: int, weight: float, times: float = 1.0):
+        """From now on every step() adds to `param`'s gradient the gradient of
+            times * weight / p * sum |x|^p                      kind "lp", p in (1, 2, 3)
+            times * weight / 3 * sum |z|^3 over complex coordinates   kind "n3_complex" (z = row[c] + i row[c + dim / 2])
+        (LookupEmbedder.penalty unweighted, lookup_embedder.py:122-147; `times` = 2 for an entity embedder that serves the
+        subject and the object slot, kge_model.py:620-625) inside the update's own pass, and `penalty_value(param)`
+        holds the term's value at the parameters the step started from.  The caller must then NOT back-propagate the
+        term itself.  kind None removes it."""
+        name = f"kge_amd.optim.{type(self).__name__}"
+        if kind is None:
+            self._penalties.pop(param, None)
+        else:
+            if kind not in ("lp", "n3_complex") or (kind == "lp" and p not in (1, 2, 3)):
+                raise ValueError(f"{name}: no fused form of penalty {kind} p={p}")
+            if not (param.is_cuda and param.dtype == torch.float32 and param.is_contiguous()):
+                raise ValueError(f"{name}: fused penalties are for dense float32 GPU parameters")
+            if kind == "n3_complex":
+                p = 3
+                if param.dim() != 2 or param.shape[1] % 8 != 0:
+                    raise ValueError(f"{name}: n3_complex needs a [*, dim] table with dim % 8 == 0")
+            self._penalties[param] = (1 if kind == "lp" else 2, int(p), float(times) * float(weight),
+                                      int(param.shape[-1]), float(times) * float(weight) / float(p))
+        self._pen_acc, self._pen_slot = {}, {}
+        for q in self._penalties:
+            acc = self._pen_acc.get(q.device)
+            self._pen_slot[q] = 0 if acc is None else acc.numel()
+            self._pen_acc[q.device] = torch.zeros(self._pen_slot[q] + 1, dtype=torch.float64, device=q.device)
+
+    def has_penalties(self) -> bool:
+        return bool(self._penalties)
+
+    def skip_penalties_once(self):
+        """The next step() is the plain update (the caller back-propagated the terms itself for that batch)."""
+        self._pen_off_once = True
+
+    def penalty_value(self, param) -> torch.Tensor:
+        """0-d float32 device tensor: the term's value the LAST step() saw (pre-step parameters)."""
+        spec = self._penalties[param]
+        return (self._pen_acc[param.device][self._pen_slot[param]] * spec[4]).to(torch.float32)
+
+    def _fold_this_step(self) -> bool:
+        """Whether this step() carries the terms; if so their accumulators are cleared.  Ends a skip_penalties_once."""
+        fold = bool(self._penalties) and not self._pen_off_once
+        self._pen_off_once = False
+        if fold:
+            for acc in self._pen_acc.values():
+                acc.zero_()  # (a fill kernel: captured with the step)
+        return fold
+
+    def _penalty_segs(self, params, device):
+        """The kge_penalty_seg array of one launch over `params`, or None if none of them has a term."""
+        if not any(q in self._penalties for q in params):
+            return None
+        pens = []
+        for q in params:
+            spec = self._penalties.get(q)
+            if spec is None:
+                pens.append(_lib.KgePenaltySeg(0, 0, 0.0, 0, None))
+            else:
+                pens.append(_lib.KgePenaltySeg(spec[0], spec[1], spec[2], spec[3],
+                                               self._pen_acc[device].data_ptr() + 8 * self._pen_slot[q]))
+        return (_lib.KgePenaltySeg * len(pens))(*pens)
+
+
+class Adagrad(_FoldedPenalties, _TorchAdagrad):
     # kge_amd.train_graph.GraphedStep: the step's launch arguments do not depend on the step count (lr_decay != 0 is
     # refused there), so a captured step() replays correctly; `after_graph_replay` keeps state["step"] -- which the
     # checkpoint carries -- counting.
@@ -53,50 +128,7 @@ class Adagrad(_TorchAdagrad):
         super().__init__(params, lr=lr, lr_decay=lr_decay, weight_decay=weight_decay,
                          initial_accumulator_value=initial_accumulator_value, eps=eps, foreach=False, **kw)
         self.bf16_copies = bool(bf16_copies)
-        self._penalties = {}       # parameter -> (kind, p, gradient factor, row_dim, value factor)
-        self._pen_acc = {}         # device -> float64 accumulators, one per parameter with a penalty
-        self._pen_slot = {}        # parameter -> index into its device's accumulators
-        self._pen_off_once = False
-
-    # ---- the embedders' unweighted penalty terms inside the step (kge_adagrad_step_multi_penalty) ------------------
-    def set_penalty(self, param, kind: str, p: int, weight: float, times: float = 1.0):
-        """From now on every step() adds to `param`'s gradient the gradient of
-            times * weight / p * sum |x|^p                      kind "lp", p in (1, 2, 3)
-            times * weight / 3 * sum |z|^3 over complex coordinates   kind "n3_complex" (z = row[c] + i row[c + dim / 2])
-        (LookupEmbedder.penalty unweighted, lookup_embedder.py:122-147; `times` = 2 for an entity embedder that serves the
-        subject and the object slot, kge_model.py:620-625) inside the update's own pass, and `penalty_value(param)`
-        holds the term's value at the parameters the step started from.  The caller must then NOT back-propagate the
-        term itself.  kind None removes it."""
-        if kind is None:
-            self._penalties.pop(param, None)
-        else:
-            if kind not in ("lp", "n3_complex") or (kind == "lp" and p not in (1, 2, 3)):
-                raise ValueError(f"kge_amd.optim.Adagrad: no fused form of penalty {kind} p={p}")
-            if not (param.is_cuda and param.dtype == torch.float32 and param.is_contiguous()):
-                raise ValueError("kge_amd.optim.Adagrad: fused penalties are for dense float32 GPU parameters")
-            if kind == "n3_complex":
-                p = 3
-                if param.dim() != 2 or param.shape[1] % 8 != 0:
-                    raise ValueError("kge_amd.optim.Adagrad: n3_complex needs a [*, dim] table with dim % 8 == 0")
-            self._penalties[param] = (1 if kind == "lp" else 2, int(p), float(times) * float(weight),
-                                      int(param.shape[-1]), float(times) * float(weight) / float(p))
-        self._pen_acc, self._pen_slot = {}, {}
-        for q in self._penalties:
-            acc = self._pen_acc.get(q.device)
-            self._pen_slot[q] = 0 if acc is None else acc.numel()
-            self._pen_acc[q.device] = torch.zeros(self._pen_slot[q] + 1, dtype=torch.float64, device=q.device)
-
-    def has_penalties(self) -> bool:
-        return bool(self._penalties)
-
-    def skip_penalties_once(self):
-        """The next step() is the plain update (the caller back-propagated the terms itself for that batch)."""
-        self._pen_off_once = True
-
-    def penalty_value(self, param) -> torch.Tensor:
-        """0-d float32 device tensor: the term's value the LAST step() saw (pre-step parameters)."""
-        spec = self._penalties[param]
-        return (self._pen_acc[param.device][self._pen_slot[param]] * spec[4]).to(torch.float32)
+        self._init_penalties()
 
     @staticmethod
     def _aligned(*tensors) -> bool:
@@ -195,29 +227,17 @@ class Adagrad(_TorchAdagrad):
                 _functional_adagrad(rest, grads, sums, steps, has_sparse_grad=any(g.is_sparse for g in grads),
                                     foreach=False, lr=group["lr"], weight_decay=group["weight_decay"],
                                     lr_decay=group["lr_decay"], eps=group["eps"], maximize=False)
-        with_pen = bool(self._penalties) and not self._pen_off_once
-        self._pen_off_once = False
-        if with_pen:
-            for acc in self._pen_acc.values():
-                acc.zero_()  # (a fill kernel: captured with the step)
+        with_pen = self._fold_this_step()
         for device, items in dense.items():
             with torch.cuda.device(device):
                 for i in range(0, len(items), _lib.ADAGRAD_MAX_SEGS):
                     chunk = items[i:i + _lib.ADAGRAD_MAX_SEGS]
                     segs = (_lib.KgeAdagradSeg * len(chunk))(*(c[2] for c in chunk))
-                    if with_pen and any(c[0] in self._penalties for c in chunk):
-                        pens = []
-                        for c in chunk:
-                            spec = self._penalties.get(c[0])
-                            if spec is None:
-                                pens.append(_lib.KgePenaltySeg(0, 0, 0.0, 0, None))
-                            else:
-                                acc = self._pen_acc[device]
-                                pens.append(_lib.KgePenaltySeg(spec[0], spec[1], spec[2], spec[3],
-                                                               acc.data_ptr() + 8 * self._pen_slot[c[0]]))
-                        _lib.check(_lib.lib().kge_adagrad_step_multi_penalty(
-                            segs, (_lib.KgePenaltySeg * len(chunk))(*pens), len(chunk), engine._stream(device)),
-                            "kge_adagrad_step_multi_penalty")
+                    pens = self._penalty_segs([c[0] for c in chunk], device) if with_pen else None
+                    if pens is not None:
+                        _lib.check(_lib.lib().kge_adagrad_step_multi_penalty(segs, pens, len(chunk),
+                                                                             engine._stream(device)),
+                                   "kge_adagrad_step_multi_penalty")
                         continue
                     _lib.check(_lib.lib().kge_adagrad_step_multi(segs, len(chunk), engine._stream(device)),
                                "kge_adagrad_step_multi")
@@ -228,19 +248,29 @@ class Adagrad(_TorchAdagrad):
         return loss
 
 
-class Adam(torch.optim.Adam):
+class Adam(_FoldedPenalties, torch.optim.Adam):
     """torch.optim.Adam (same constructor arguments and `state_dict`: "step", "exp_avg", "exp_avg_sq")
     with the dense update of float32 GPU parameters done by kge_adam_step: one pass instead of the
     multi-tensor sequence, optionally writing the bf16 scoring copies in the same pass.  amsgrad,
     maximize, capturable and differentiable are not supported; parameters the kernel does not cover
-    are stepped by torch's own Adam."""
+    are stepped by torch's own Adam.
+
+    device_step=True: the step count lives on the device too.  Every parameter gets a 32-byte clock record
+    (state[p]["clock"]: t, beta1^t, beta2^t and the two bias-correction floats; include/kge_amd.h kge_adam_clock) that
+    a small kernel advances in front of the update; step() computes nothing from the step count, updates every dense
+    table of a device in one launch (kge_adam_step_multi) and can fold the embedders' penalty terms into it
+    (set_penalty, as kge_amd.optim.Adagrad).  Such an instance is `graph_capturable`.  The record is seeded from the
+    host's state["step"] (T = 0, or the step count a checkpoint restored) with beta ** T and is not part of
+    `state_dict()`: the checkpoint format stays step / exp_avg / exp_avg_sq.  The record carries powers of the betas
+    it was seeded with: change a group's betas only together with dropping state[p]["clock"]."""
 
     # step() computes lr / (1 - beta1^t) and sqrt(1 - beta2^t) on the host from the step count and hands them to the
-    # kernel as launch arguments: a hipGraph capture would freeze them at the capture step.  GraphedStep refuses.
+    # kernel as launch arguments: a hipGraph capture would freeze them at the capture step.  GraphedStep refuses --
+    # unless the instance keeps the step count on the device (device_step=True sets the instance's attribute).
     graph_capturable = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
-                 bf16_copies: bool = False, **kw):
+                 bf16_copies: bool = False, device_step: bool = False, **kw):
         kw.pop("foreach", None)
         kw.pop("fused", None)
         if amsgrad:
@@ -248,6 +278,99 @@ class Adam(torch.optim.Adam):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, foreach=False,
                          **kw)
         self.bf16_copies = bool(bf16_copies)
+        self.device_step = bool(device_step)
+        self._init_penalties()
+        if self.device_step:
+            self.graph_capturable = True
+
+    def set_penalty(self, param, kind, p, weight, times=1.0):
+        if not self.device_step:
+            raise ValueError("kge_amd.optim.Adam: fused penalties need device_step=True (kge_adam_step_multi)")
+        super().set_penalty(param, kind, p, weight, times)
+
+    def after_graph_replay(self, params):
+        """`params`: the parameters the captured step() updated.  The replayed clock kernel advanced their device
+        records; the host's state["step"] -- what the checkpoint carries and a record is seeded from -- follows."""
+        for p in params:
+            st = self.state.get(p)
+            if st is not None and "step" in st:
+                st["step"] += 1
+
+    def device_step_count(self, param) -> int:
+        """`t` of the parameter's device clock record (a host read: synchronizes)."""
+        return int(self.state[param]["clock"][0])
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = {k: {n: v for n, v in st.items() if n != "clock"} for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            st.pop("clock", None)  # seeded again from the restored state["step"] by the next step()
+
+    def _clock_of(self, p, state, beta1, beta2) -> torch.Tensor:
+        clock = state.get("clock")
+        if clock is None or clock.device != p.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("kge_amd.optim.Adam: the first step() of a parameter cannot be captured "
+                                   "(its state and clock record are made on the host): take one step eagerly first")
+            import struct
+            t = int(state["step"])
+            rec = struct.pack("<qddff", t, float(beta1) ** t, float(beta2) ** t, 0.0, 0.0)
+            clock = state["clock"] = torch.frombuffer(bytearray(rec), dtype=torch.int64).to(p.device)
+        return clock
+
+    def _step_device(self):
+        dense, held = {}, False  # device -> [(p, copy, segment)]: every dense table of a device in ONE launch
+        for group in self.param_groups:
+            if group.get("maximize") or group.get("differentiable") or group.get("capturable"):
+                raise NotImplementedError("kge_amd.optim.Adam: maximize / differentiable / capturable are not supported")
+            beta1, beta2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                state = self.state[p]
+                if not Adagrad._kernel_ok(p) or (len(state) != 0 and not Adagrad._aligned(state["exp_avg"],
+                                                                                         state["exp_avg_sq"])):
+                    if p in self._penalties and not self._pen_off_once:
+                        raise RuntimeError("kge_amd.optim.Adam: a parameter with a fused penalty left the kernel path")
+                    held = True
+                    continue
+                if len(state) == 0:
+                    if torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError("kge_amd.optim.Adam: the first step() of a parameter cannot be captured "
+                                           "(its moments would be zeroed by every replay): take one step eagerly first")
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                clock = self._clock_of(p, state, beta1, beta2)
+                state["step"] += 1  # (the checkpoint's count; the kernel's own is the record's t)
+                copy = None
+                if self.bf16_copies and p.dim() == 2:
+                    rec = getattr(p, BF16_ATTR, None)
+                    copy = rec[0] if rec is not None and rec[0].shape == p.shape else \
+                        torch.empty(p.shape, dtype=torch.bfloat16, device=p.device)
+                seg = _lib.KgeAdamSeg(p.data_ptr(), p.grad.data_ptr(), state["exp_avg"].data_ptr(),
+                                      state["exp_avg_sq"].data_ptr(), None if copy is None else copy.data_ptr(),
+                                      clock.data_ptr(), p.numel(), float(group["lr"]), float(beta1), float(beta2),
+                                      float(group["weight_decay"]), float(group["eps"]))
+                dense.setdefault(p.device, []).append((p, copy, seg))
+        with_pen = self._fold_this_step()
+        for device, items in dense.items():
+            with torch.cuda.device(device):
+                for i in range(0, len(items), _lib.ADAM_MAX_SEGS):
+                    chunk = items[i:i + _lib.ADAM_MAX_SEGS]
+                    segs = (_lib.KgeAdamSeg * len(chunk))(*(c[2] for c in chunk))
+                    pens = self._penalty_segs([c[0] for c in chunk], device) if with_pen else None
+                    _lib.check(_lib.lib().kge_adam_step_multi(segs, pens, len(chunk), engine._stream(device)),
+                               "kge_adam_step_multi")
+            for p, copy, _seg in items:
+                torch.autograd.graph.increment_version(p)  # the kernel wrote through the raw pointer
+                if copy is not None:
+                    setattr(p, BF16_ATTR, (copy, p._version, p.data_ptr()))
+        return [c[0] for items in dense.values() for c in items], held
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -255,6 +378,11 @@ class Adam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.device_step:
+            done, held = self._step_device()
+            if held:
+                self._torch_step_of_the_rest(done)
+            return loss
         done, held = [], False
         for group in self.param_groups:
             if group.get("maximize") or group.get("differentiable") or group.get("capturable"):
@@ -291,13 +419,17 @@ class Adam(torch.optim.Adam):
                 if copy is not None:
                     setattr(p, BF16_ATTR, (copy, p._version, p.data_ptr()))
                 done.append(p)
-        if held:  # torch's own update for everything else: hide the stepped parameters' gradients for the call
-            stash = [(q, q.grad) for q in done]
-            for q, _ in stash:
-                q.grad = None
-            try:
-                torch.optim.Adam.step(self)
-            finally:
-                for q, g in stash:
-                    q.grad = g
+        if held:
+            self._torch_step_of_the_rest(done)
         return loss
+
+    def _torch_step_of_the_rest(self, done):
+        """torch's own update for everything else: hide the stepped parameters' gradients for the call."""
+        stash = [(q, q.grad) for q in done]
+        for q, _ in stash:
+            q.grad = None
+        try:
+            torch.optim.Adam.step(self)
+        finally:
+            for q, g in stash:
+                q.grad = g

@@ -70,7 +70,8 @@ class GraphedStep:
                 self._disable("the optimizer's lr_decay makes the step size a function of the step count")
         # A captured step() freezes every launch argument the host computed.  Adam's bias correction (lr / (1 - b1^t),
         # sqrt(1 - b2^t)) is such an argument: a replay would keep the values of the capture step for ever.
-        # An optimizer says so itself (`graph_capturable`, kge_amd.optim); of torch's own only SGD is known to be safe.
+        # An optimizer says so itself (`graph_capturable`, kge_amd.optim: Adagrad, and an Adam that keeps its step count
+        # on the device, device_step=True); of torch's own only SGD is known to be safe.
         cap = getattr(optimizer, "graph_capturable", None)
         if cap is None:
             cap = type(optimizer) is torch.optim.SGD
