@@ -1126,6 +1126,43 @@ int kge_adagrad_step_rows(float* param, int64_t param_ld, const float* grad_rows
                           int64_t dim, float minus_clr, float eps, void* bf16_copy, int64_t copy_ld,
                           void* stream);
 
+/* ---- Adagrad over the rows a batch touched (csrc/touched.hip) --------------------------------
+ * The step of TrainingJob.run_epoch (kge/job/train.py:452-474: zero_grad, backward, optimizer.step) without a pass over
+ * the whole table: the backward accumulates into a PERSISTENT dense gradient buffer and marks the rows it adds to in a
+ * bitmap; the step visits the marked rows only, and leaves buffer and bitmap zero for the next batch.  The row-wise
+ * update of kge/model/embedder/lookup_embedder.yaml:78-81 (`sparse: True`) needs a coalesced sparse gradient, which
+ * the fused backward kernels never produce; this one needs a bit per row.
+ *
+ * Bytes of the bitmap of a table of num_rows rows: 4 * ceil(num_rows / 32), rounded up to 16.  Bit r % 32 of the
+ * 32-bit word r / 32 means that row r has a gradient.  (train.py:452-474, lookup_embedder.yaml:78-81) */
+int64_t kge_touched_bitmap_bytes(int64_t num_rows);
+
+/* Sets the bit of every id of an [n, k] block: element (i, j) is ids.ptr[(i * ld + j) * ids.stride], int32 or int64
+ * (k = 1, ld = 1: a plain index vector, e.g. the stride-3 triples[:, 0]).  Ordinary global atomic OR: duplicates are
+ * fine, calls on one bitmap may follow each other in any order.  An id outside [0, num_rows) sets nothing.  Nothing is
+ * read on the host (capturable); n * k == 0: KGE_OK without a launch.  What is marked is what the backward of
+ * train.py:452-474 would give a gradient row under lookup_embedder.yaml:78-81's sparse embeddings.
+ * KGE_ERR_INVALID_ARG: n, k or num_rows < 0, ld < k, a NULL bitmap or ids.ptr (n * k > 0), an ids.itype other than
+ * int32 / int64, ids.stride < 1, ids.start != 0. */
+int kge_touched_mark(kge_index ids, int64_t n, int64_t k, int64_t ld, int64_t num_rows, uint32_t* bitmap,
+                     void* stream);
+
+/* For every set bit r of `bitmap` (bits of rows >= num_rows are ignored) the arithmetic of kge_adagrad_step_multi with
+ * weight_decay == 0 on row r, operation for operation:
+ *   state_sum[r] += g*g;  param[r] = param[r] + (minus_clr * g) / (sqrt(state_sum[r]) + eps);  bf16_copy[r] = bf16(param[r])
+ * then zeros are stored over grad[r, 0:dim] and, once all rows of a word are done, over the word.  On return the
+ * bitmap is all zero, and grad is all zero provided it was zero outside the marked rows on entry.  Rows whose bit is
+ * clear are neither read nor written, in any of the four arrays.  A dense Adagrad step (train.py:452-474 with
+ * torch.optim.Adagrad) leaves a row whose gradient is zero bit for bit as it was, so this is that step; there is no
+ * weight decay here because it would move untouched rows (lookup_embedder.yaml:78-81's sparse route has none either).
+ * Every shape is taken: four floats per lane when dim % 4 == 0, param, grad and state_sum are 16-byte aligned with
+ * pitches % 4 == 0 (and bf16_copy, if given, 8-byte aligned with copy_ld % 4 == 0), one float per lane otherwise.
+ * KGE_ERR_INVALID_ARG: num_rows or dim < 0, dim > 2^31 - 1, a pitch < dim, a NULL param, grad, state_sum or bitmap
+ * (num_rows > 0).  KGE_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups (256 rows each). */
+int kge_adagrad_step_touched(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* state_sum,
+                             int64_t sum_ld, uint32_t* bitmap, int64_t num_rows, int64_t dim, float minus_clr,
+                             float eps, void* bf16_copy, int64_t copy_ld, void* stream);
+
 /* ---- backward (autograd twins) ------------------------------------------ */
 /* All gradients are f32 and OVERWRITTEN; tables/embeddings must be f32, except
  * kge_score_pairs_bwd for ComplEx/DistMult, which also takes bf16 tables (mixed-precision

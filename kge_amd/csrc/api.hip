@@ -203,6 +203,11 @@ int run_adam_multi(const kge_adam_seg* segs, const kge_penalty_seg* pens, int nu
 int run_adagrad_rows(float* param, long long param_ld, const float* grows, long long g_ld, float* sum, long long sum_ld,
                      const long long* rows, long long nrows, int dim, float minus_clr, float eps,
                      unsigned short* copy16, long long c_ld, hipStream_t st);
+int run_touched_mark(const Index& ids, long long n, long long k, long long ld, long long num_rows, unsigned int* bitmap,
+                     hipStream_t st);
+int run_adagrad_touched(float* param, long long param_ld, float* grad, long long grad_ld, float* sum, long long sum_ld,
+                        unsigned int* bitmap, long long num_rows, int dim, float minus_clr, float eps,
+                        unsigned short* copy16, long long c_ld, hipStream_t st);
 int run_kl_fwd(int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n,
                long long m, const long long* rowptr, const long long* col, float* loss_rows, float* lse, void* ws,
                long long ws_bytes, hipStream_t st, const float* label_weight = nullptr, long long col_lo = 0);
@@ -2305,6 +2310,33 @@ int kge_adagrad_step_rows(float* param, int64_t param_ld, const float* grad_rows
   if (param_ld < dim || grad_ld < dim || sum_ld < dim || (bf16_copy && copy_ld < dim)) return KGE_ERR_INVALID_ARG;
   return run_adagrad_rows(param, param_ld, grad_rows, grad_ld, state_sum, sum_ld, (const long long*)rows, num_rows,
                           (int)dim, minus_clr, eps, (unsigned short*)bf16_copy, copy_ld, (hipStream_t)stream);
+}
+
+int64_t kge_touched_bitmap_bytes(int64_t num_rows) {
+  if (num_rows <= 0) return 0;
+  return ((num_rows + 31) / 32 * 4 + 15) / 16 * 16;
+}
+
+int kge_touched_mark(kge_index ids, int64_t n, int64_t k, int64_t ld, int64_t num_rows, uint32_t* bitmap,
+                     void* stream) {
+  KGE_RANGE();
+  if (n < 0 || k < 0 || num_rows < 0 || ld < k) return KGE_ERR_INVALID_ARG;
+  if (n * k == 0) return KGE_OK;
+  int rc = check_index(ids, false, n * k);
+  if (rc) return rc;
+  if (!ids.ptr || !bitmap) return KGE_ERR_INVALID_ARG;
+  return run_touched_mark(make_index(ids), n, k, ld, num_rows, bitmap, (hipStream_t)stream);
+}
+
+int kge_adagrad_step_touched(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* state_sum,
+                             int64_t sum_ld, uint32_t* bitmap, int64_t num_rows, int64_t dim, float minus_clr,
+                             float eps, void* bf16_copy, int64_t copy_ld, void* stream) {
+  KGE_RANGE();
+  if (num_rows < 0 || dim < 0 || dim > 0x7fffffff) return KGE_ERR_INVALID_ARG;
+  if (num_rows > 0 && (!param || !grad || !state_sum || !bitmap)) return KGE_ERR_INVALID_ARG;
+  if (param_ld < dim || grad_ld < dim || sum_ld < dim || (bf16_copy && copy_ld < dim)) return KGE_ERR_INVALID_ARG;
+  return run_adagrad_touched(param, param_ld, grad, grad_ld, state_sum, sum_ld, bitmap, num_rows, (int)dim, minus_clr,
+                             eps, (unsigned short*)bf16_copy, copy_ld, (hipStream_t)stream);
 }
 
 int kge_bce_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,

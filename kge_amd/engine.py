@@ -1156,6 +1156,84 @@ def neg_sample(n: int, K: int, vocab: int, slot: int, seed: int, call: int, alia
     return (out, stats) if want_stats else out
 
 
+# ---- the Adagrad step over the rows a batch touched (csrc/touched.hip) -------------------------
+def touched_bitmap(num_rows: int, device) -> torch.Tensor:
+    """A zero bitmap for a table of `num_rows` rows (kge_touched_bitmap_bytes): int32 words, bit r % 32 of word r // 32
+    = row r has a gradient."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"kge_amd: the touched-row bitmap lives on a GPU, not on '{device}' (no CPU path)")
+    nbytes = int(_lib.lib().kge_touched_bitmap_bytes(int(num_rows)))
+    return torch.zeros(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def _bitmap_ok(bitmap, num_rows, device, what):
+    if not (torch.is_tensor(bitmap) and bitmap.device == device and bitmap.dtype == torch.int32
+            and bitmap.dim() == 1 and bitmap.is_contiguous() and bitmap.numel() * 32 >= num_rows):
+        raise ValueError(f"kge_amd: {what}: the bitmap is a contiguous int32 vector of at least ceil(num_rows / 32) "
+                         f"words on {device}")
+
+
+def touched_mark(ids: torch.Tensor, bitmap: torch.Tensor, num_rows: int) -> None:
+    """Sets the bit of every id in `ids` (kge_touched_mark): an int32 / int64 index vector of any positive stride
+    (triples[:, 0]) or an [n, k] block (a slice of a wider matrix is fine).  Ids outside [0, num_rows) set nothing;
+    nothing is read on the host."""
+    device = bitmap.device if torch.is_tensor(bitmap) else None
+    if device is None or device.type != "cuda":
+        raise RuntimeError("kge_amd: touched_mark marks on a GPU (no CPU path)")
+    _bitmap_ok(bitmap, int(num_rows), device, "touched_mark")
+    if not torch.is_tensor(ids) or ids.device != device:
+        raise RuntimeError(f"kge_amd: touched_mark: ids and bitmap must be on the same GPU ({device})")
+    if ids.dtype not in (torch.int32, torch.int64):
+        ids = ids.long()
+    if ids.dim() == 2:
+        n, k = ids.shape
+        s0, s1 = ids.stride()
+        if n * k > 0 and (s1 < 1 or (n > 1 and (s0 < k * s1 or s0 % s1 != 0))):
+            ids = ids.contiguous()
+            s0, s1 = ids.stride()
+        stride, ld = (max(s1, 1), s0 // max(s1, 1)) if n > 1 else (max(s1, 1), max(k, 1))
+    else:
+        if ids.dim() != 1:
+            ids = ids.reshape(-1)
+        n, k, ld = ids.numel(), 1, 1
+        stride = ids.stride(0) if n > 1 else 1
+        if stride < 1:
+            ids, stride = ids.contiguous(), 1
+    if n * k == 0:
+        return
+    ix = KgeIndex(ids.data_ptr(), I32 if ids.dtype == torch.int32 else I64, 0, stride)
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_touched_mark(ix, n, k, ld, int(num_rows), bitmap.data_ptr(), _stream_handle(device)),
+                   "kge_touched_mark")
+
+
+def adagrad_step_touched(param: torch.Tensor, grad: torch.Tensor, state_sum: torch.Tensor, bitmap: torch.Tensor,
+                         minus_clr: float, eps: float, bf16_copy: torch.Tensor = None) -> None:
+    """The dense Adagrad step (weight_decay 0) on the rows whose bit is set (kge_adagrad_step_touched); afterwards the
+    marked rows of `grad` and the bitmap are zero.  param, grad, state_sum: float32 [E, d] with unit inner stride (any
+    row pitch), bf16_copy: bfloat16 / int16 [E, d] or None; rows whose bit is clear are neither read nor written."""
+    device = param.device
+    if device.type != "cuda":
+        raise RuntimeError(f"kge_amd: adagrad_step_touched steps on a GPU, not on '{device}' (no CPU path)")
+    E, d = param.shape
+    for t, what in ((param, "param"), (grad, "grad"), (state_sum, "state_sum")):
+        if not (t.device == device and t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (E, d)
+                and (d <= 1 or t.stride(1) == 1) and (E <= 1 or t.stride(0) >= d)):
+            raise ValueError(f"kge_amd: adagrad_step_touched: {what} is float32 [E, d] with unit inner stride on {device}")
+    if bf16_copy is not None and not (bf16_copy.device == device and bf16_copy.element_size() == 2
+                                      and tuple(bf16_copy.shape) == (E, d) and (d <= 1 or bf16_copy.stride(1) == 1)
+                                      and (E <= 1 or bf16_copy.stride(0) >= d)):
+        raise ValueError("kge_amd: adagrad_step_touched: bf16_copy is a 2-byte [E, d] tensor with unit inner stride")
+    _bitmap_ok(bitmap, E, device, "adagrad_step_touched")
+    ld = lambda t: t.stride(0) if E > 1 else max(d, 1)
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_adagrad_step_touched(
+            param.data_ptr(), ld(param), grad.data_ptr(), ld(grad), state_sum.data_ptr(), ld(state_sum),
+            bitmap.data_ptr(), E, d, float(minus_clr), float(eps), None if bf16_copy is None else bf16_copy.data_ptr(),
+            0 if bf16_copy is None else ld(bf16_copy), _stream_handle(device)), "kge_adagrad_step_touched")
+
+
 KVSALL_COLLATE_MAX_N = _lib.KVSALL_COLLATE_MAX_N
 
 

@@ -96,6 +96,15 @@ class _FusedScoring:
     def _w(self):
         return (self.get_s_embedder()._embeddings.weight, self.get_p_embedder()._embeddings.weight)
 
+    def set_touched_rows(self, pair):
+        """hip_negative_sampling.touched_rows: `pair` = HipAdagrad.enable_touched_rows(entity table) -> (grad, bitmap),
+        or None.  score_spo / score_neg / score_neg_blocks hand it to their autograd nodes while the model trains: the
+        backward accumulates the entity gradient into the persistent buffer and marks the rows (kge_amd.model)."""
+        self._touched_rows = pair
+
+    def _touched_pair(self):
+        return getattr(self, "_touched_rows", None) if self.training else None
+
     def penalty(self, **kwargs):
         """KgeModel.penalty (kge_model.py:603-640) first copies the batch's triples to the device -- a blocking
         host-to-device copy in every batch -- and then asks the embedders, which answer with nothing when their
@@ -129,7 +138,7 @@ class _FusedScoring:
         if not self._fused():
             return super().score_spo(s, p, o, direction)
         ent, rel = self._w()
-        return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o)
+        return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, self._touched_pair())
 
     def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor) -> Tensor:
         """[n, K] scores of the positives with slot (0 = s, 2 = o) replaced by neg[i, k]: what
@@ -141,7 +150,8 @@ class _FusedScoring:
         ent, rel = self._w()
         if not ent.is_cuda:
             return None
-        return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), neg)
+        return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), neg,
+                               self._touched_pair())
 
     def score_neg_shared(self, s: Tensor, p: Tensor, o: Tensor, slot: int, unique: Tensor, drop: Tensor = None,
                          repeat: Tensor = None):
@@ -166,7 +176,8 @@ class _FusedScoring:
         ent, rel = self._w()
         if not neg_blocks_fusable(ent, rel):
             return None
-        return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o)
+        return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o,
+                                     self._touched_pair())
 
     def _padded(self) -> bool:
         """`padded_scores` (hip_*.yaml, default true): where no gradient is recorded -- evaluation, scoring under

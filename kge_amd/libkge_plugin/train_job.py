@@ -255,6 +255,8 @@ def _graphed_step_of(job, loss_fn):
         step = staticmethod(real_step)
         graph_capturable = True  # (the caller checked the real optimizer: _optimizer_is_capturable)
         after_graph_replay = staticmethod(getattr(opt, "after_graph_replay", lambda params: None))
+        # (None: GraphedStep takes the parameters that have a .grad; HipAdagrad names the touched-row ones too)
+        stepped_params = staticmethod(opt.stepped_params) if callable(getattr(opt, "stepped_params", None)) else None
 
     def step_or_skip(*a, **k):
         if job._skip_optimizer_step:
@@ -938,6 +940,8 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         self._graph_labels = {}
         self.graph_batches = 0        # batches that went through the GraphedStep (replayed or eager)
         self._skip_optimizer_step = False
+        self.touched_rows = None           # hip_negative_sampling.touched_rows: decided at the first batch
+        self.touched_rows_declined = None  # why the dense path runs although the option is on
         if self.__class__ == HipTrainingJobNegativeSampling:
             for f in Job.job_created_hooks:
                 f(self)
@@ -1075,7 +1079,64 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             total = part if total is None else total + part
         return total
 
+    # ---- hip_negative_sampling.touched_rows: the entity table stepped on the rows the batch touched only (DESIGN.md
+    # section 25).  The step of TrainingJob.run_epoch (kge/job/train.py:452-474) pays a zeros_like(ent) fill per
+    # backward node and HipAdagrad's sweep of the whole table, a batch touches n (2 + K_s + K_o) rows.  Switched on, the
+    # entity table's gradient lives in a persistent buffer of HipAdagrad (enable_touched_rows), the backward nodes of
+    # score_spo / score_neg / score_neg_blocks accumulate into it and mark the rows, the optimizer visits the marked
+    # rows.  Decided once, at the first batch, like graph_step; anything the row step does not cover runs as before.
+    def _touched_rows_why_not(self, batch):
+        """None if the job qualifies, else the reason it stays on the dense path."""
+        from kge.model import LookupEmbedder
+        from kge.util.sampler import DefaultBatchNegativeSample
+        from ..model import neg_blocks_fusable
+        from ..optim import Adagrad as HipAdagrad
+        from .models import _FusedScoring
+        model, opt = self.model, self.optimizer
+        if not str(self.device).startswith("cuda"):
+            return "not a CUDA device"
+        if not isinstance(model, _FusedScoring) or not model._fused():
+            return "the model's fused gather + score path does not apply"
+        if not isinstance(opt, HipAdagrad):
+            return "the optimizer is not HipAdagrad (dense Adam moves rows without a gradient)"
+        emb = model.get_s_embedder()
+        w = emb._embeddings.weight
+        group = next((g for g in opt.param_groups if any(q is w for q in g["params"])), None)
+        if group is None or group["weight_decay"] != 0:
+            return "weight_decay != 0 in the entity table's parameter group"
+        if type(emb) is not LookupEmbedder or emb.dropout.p > 0:
+            return "the entity embedder is not a plain LookupEmbedder without dropout"
+        if not (emb.regularize == "" or emb.get_option("regularize_weight") == 0.0):
+            return "regularize_weight > 0 on the entity embedder (a penalty term touches every row)"
+        if self._sampler.num_samples[P] > 0:
+            return "negative samples for the relation slot"
+        slots = [slot for slot in (S, O) if self._sampler.num_samples[slot] > 0]
+        if not slots or not all(type(batch["negative_samples"][slot]) is DefaultBatchNegativeSample for slot in slots):
+            return "not per-triple samples (DefaultBatchNegativeSample) on every active slot"
+        if not neg_blocks_fusable(w, model.get_p_embedder()._embeddings.weight):
+            return "not contiguous float32 tables with dim <= 1024"
+        return None
+
+    def _decide_touched_rows(self, batch):
+        try:
+            want = bool(self.config.get_default("hip_negative_sampling.touched_rows"))
+        except KeyError:
+            want = False
+        self.touched_rows = False
+        if not want or self.is_forward_only:
+            return
+        why = self._touched_rows_why_not(batch)
+        if why is not None:
+            self.touched_rows_declined = why
+            self.config.log(f"hip_negative_sampling.touched_rows: the dense path runs: {why}")
+            return
+        pair = self.optimizer.enable_touched_rows(self.model.get_s_embedder()._embeddings.weight)
+        self.model.set_touched_rows(pair)
+        self.touched_rows = True
+
     def _process_subbatch(self, batch_index, batch, subbatch_slice, result):
+        if self.touched_rows is None:
+            self._decide_touched_rows(batch)
         gs = self._graph_step_for(batch_index, batch, subbatch_slice)
         if gs is not None and gs.enabled:
             batch_size = result.size

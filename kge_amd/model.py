@@ -140,6 +140,14 @@ class KgeModel(torch.nn.Module):
         self._relation_embedder = LookupEmbedder(num_relations, rel_dim, dtype=dtype, device=device,
                                                  **relation_args)
         self._scorer = self.scorer_cls(l_norm)
+        self._touched_rows = None  # set_touched_rows
+
+    def set_touched_rows(self, pair):
+        """`pair` = kge_amd.optim.Adagrad.enable_touched_rows(entity table) -> (grad, bitmap), or None to switch it off:
+        score_spo, score_neg and score_neg_blocks hand it to their autograd nodes, whose backward then accumulates the
+        entity gradient into the persistent `grad`, marks the rows in `bitmap` and leaves the table's `.grad` None
+        (DESIGN.md section 25).  Shared samples (score_neg_shared) keep the dense gradient: do not mix them with it."""
+        self._touched_rows = pair
 
     # -- accessors (kge_model.py:649-661)
     def get_s_embedder(self):
@@ -174,7 +182,7 @@ class KgeModel(torch.nn.Module):
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
         if self._fused():
             return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                   self._relation_embedder.weight, s, p, o)
+                                   self._relation_embedder.weight, s, p, o, self._touched_rows)
         se, pe, oe = self._entity_embedder.embed(s), self._relation_embedder.embed(p), self._entity_embedder.embed(o)
         return self._scorer.score_emb(se, pe, oe, combine="spo").view(-1)
 
@@ -183,7 +191,7 @@ class KgeModel(torch.nn.Module):
         BatchNegativeSample.score with implementation "triple" (kge/util/sampler.py:291-306)."""
         if self._fused() and slot in (0, 2):
             return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                   self._relation_embedder.weight, s, p, o, int(slot), neg)
+                                   self._relation_embedder.weight, s, p, o, int(slot), neg, self._touched_rows)
         K = neg.shape[1]
         tr = [x.reshape(-1).long().repeat_interleave(K) for x in (s, p, o)]
         tr[slot] = neg.reshape(-1).long()
@@ -205,7 +213,8 @@ class KgeModel(torch.nn.Module):
         backward); composed from the single calls where the fused node does not apply."""
         ent, rel = self._entity_embedder.weight, self._relation_embedder.weight
         if self._fused() and neg_blocks_fusable(ent, rel):
-            return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o)
+            return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o,
+                                         self._touched_rows)
         pos = self.score_spo(s, p, o)
         return (pos, None if neg_s is None else self.score_neg(s, p, o, 0, neg_s),
                 None if neg_o is None else self.score_neg(s, p, o, 2, neg_o))
@@ -485,11 +494,30 @@ def _scatter_rows(grad_table, idx, rows):
     grad_table.index_add_(0, idx.reshape(-1).long(), rows)
 
 
+def _touched_pair(t, touched):
+    """`touched` = (grad, bitmap) of kge_amd.optim.Adagrad.enable_touched_rows for the entity table, checked: the
+    backward then accumulates the entity gradient into the persistent `grad`, marks the rows it adds to in `bitmap`
+    and returns None for the table -- no zeros_like(ent) fill, no dense gradient for the optimizer to sweep."""
+    grad, bitmap = touched
+    if not (grad.shape == t.ent.shape and grad.dtype == torch.float32 and t.ent.dtype == torch.float32
+            and grad.device == t.ent.device and grad.stride(1) == 1):
+        raise ValueError("kge_amd: the touched-row gradient buffer is a float32 tensor of the entity table's shape on "
+                         "its device")
+    return grad, bitmap
+
+
+def _mark_touched(t, bitmap, *ids):
+    for x in ids:
+        if x is not None:
+            engine.touched_mark(x, bitmap, t.ent.shape[0])
+
+
 class _ScoreSPO(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, name, l_norm, ent, rel, s, p, o):
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, touched=None):
         t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
         ctx.t, ctx.idx = t, (s, p, o)
+        ctx.touched = None if touched is None else _touched_pair(t, touched)
         out = engine.score_spo(t, s, p, o)
         ctx.save_for_backward(out)
         return out
@@ -498,6 +526,13 @@ class _ScoreSPO(torch.autograd.Function):
     def backward(ctx, gout):
         s, p, o = ctx.idx
         (scores,) = ctx.saved_tensors
+        if ctx.touched is not None:  # the accumulate route on the persistent buffer, or nothing
+            ge, bitmap = ctx.touched
+            gr = torch.zeros_like(ctx.t.rel)
+            _mark_touched(ctx.t, bitmap, s, o)
+            if not engine.score_spo_bwd_accum(ctx.t, s, p, o, gout.contiguous(), scores, ge, gr):
+                raise RuntimeError("kge_amd: kge_score_spo_bwd_accum declined a shape the touched-row step admitted")
+            return None, None, None, gr, None, None, None, None
         ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
         # one kernel: row gradients accumulated into the table gradients (runs of equal s / p
         # summed in registers first); fallback: row gradients + three scatter-adds
@@ -506,7 +541,7 @@ class _ScoreSPO(torch.autograd.Function):
             _scatter_rows(ge, s, g_s)
             _scatter_rows(ge, o, g_o)
             _scatter_rows(gr, p, g_p)
-        return None, None, ge, gr, None, None, None
+        return None, None, ge, gr, None, None, None, None
 
 
 class _ScoreNeg(torch.autograd.Function):
@@ -516,10 +551,11 @@ class _ScoreNeg(torch.autograd.Function):
     tensor and no [n*K, d] gathered rows in either pass)."""
 
     @staticmethod
-    def forward(ctx, name, l_norm, ent, rel, s, p, o, slot, neg):
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, slot, neg, touched=None):
         t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
         out = engine.score_neg(t, s, p, o, slot, neg)
         ctx.t, ctx.idx, ctx.slot = t, (s, p, o, neg), slot
+        ctx.touched = None if touched is None else _touched_pair(t, touched)
         ctx.save_for_backward(out)
         return out
 
@@ -527,6 +563,13 @@ class _ScoreNeg(torch.autograd.Function):
     def backward(ctx, gout):
         s, p, o, neg = ctx.idx
         (scores,) = ctx.saved_tensors
+        if ctx.touched is not None:  # the accumulate kernel on the persistent buffer, or nothing
+            ge, bitmap = ctx.touched
+            gr = torch.zeros_like(ctx.t.rel)
+            _mark_touched(ctx.t, bitmap, s, o, neg)
+            if not engine.score_neg_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr):
+                raise RuntimeError("kge_amd: kge_score_neg_bwd_accum declined a shape the touched-row step admitted")
+            return None, None, None, gr, None, None, None, None, None, None
         ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
         if not engine.score_neg_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr):
             # shapes the accumulate kernel does not take (bf16 parameters, d > 1024): expanded triples
@@ -540,7 +583,7 @@ class _ScoreNeg(torch.autograd.Function):
             _scatter_rows(ge, tr[2], g_o)
             _scatter_rows(gr, tr[1], g_p)
             ge, gr = ge.to(ctx.t.ent.dtype), gr.to(ctx.t.rel.dtype)
-        return None, None, ge, gr, None, None, None, None, None
+        return None, None, ge, gr, None, None, None, None, None, None
 
 
 class _ScoreNegShared(torch.autograd.Function):
@@ -590,12 +633,13 @@ class _ScoreNegBlocks(torch.autograd.Function):
     (the accumulate kernels' domain; the caller checks)."""
 
     @staticmethod
-    def forward(ctx, name, l_norm, ent, rel, s, p, o, neg_s, neg_o):
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, neg_s, neg_o, touched=None):
         t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
         pos = engine.score_spo(t, s, p, o)
         sc_s = engine.score_neg(t, s, p, o, 0, neg_s) if neg_s is not None else None
         sc_o = engine.score_neg(t, s, p, o, 2, neg_o) if neg_o is not None else None
         ctx.t, ctx.idx = t, (s, p, o, neg_s, neg_o)
+        ctx.touched = None if touched is None else _touched_pair(t, touched)
         ctx.save_for_backward(pos, sc_s, sc_o)
         return pos, sc_s, sc_o
 
@@ -603,14 +647,20 @@ class _ScoreNegBlocks(torch.autograd.Function):
     def backward(ctx, g_pos, g_s, g_o):
         s, p, o, neg_s, neg_o = ctx.idx
         pos, sc_s, sc_o = ctx.saved_tensors
-        ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
+        gr = torch.zeros_like(ctx.t.rel)
+        if ctx.touched is not None:
+            # the persistent buffer in place of a fresh zeros_like(ent); s, o and the blocks differentiated are marked
+            ge, bitmap = ctx.touched
+            _mark_touched(ctx.t, bitmap, s, o, neg_s if g_s is not None else None, neg_o if g_o is not None else None)
+        else:
+            ge = torch.zeros_like(ctx.t.ent)
         if g_pos is not None and not engine.score_spo_bwd_accum(ctx.t, s, p, o, g_pos.contiguous(), pos, ge, gr):
             raise RuntimeError("kge_amd: kge_score_spo_bwd_accum declined a shape score_neg_blocks admitted")
         for slot, neg, g, sc in ((0, neg_s, g_s, sc_s), (2, neg_o, g_o, sc_o)):
             if neg is not None and g is not None:
                 if not engine.score_neg_bwd_accum(ctx.t, s, p, o, slot, neg, g, sc, ge, gr):
                     raise RuntimeError("kge_amd: kge_score_neg_bwd_accum declined a shape score_neg_blocks admitted")
-        return None, None, ge, gr, None, None, None, None, None
+        return None, None, None if ctx.touched is not None else ge, gr, None, None, None, None, None, None
 
 
 def neg_shared_fusable(ent: torch.Tensor, n: int) -> bool:

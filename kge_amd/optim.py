@@ -1,5 +1,6 @@
 """torch.optim.Adagrad / torch.optim.Adam with the update done by HIP kernels (kge_adagrad_step_multi: every dense
-table of a device in one launch, kge_adagrad_step_rows for row-sparse gradients, kge_adam_step per parameter, or
+table of a device in one launch, kge_adagrad_step_rows for row-sparse gradients, kge_adagrad_step_touched for a table
+whose backward marks the rows it touched (Adagrad.enable_touched_rows), kge_adam_step per parameter, or
 kge_adam_step_multi with Adam(device_step=True): the step count on the device, one launch, capturable), optionally
 maintaining the bf16 copies of the tables that mixed-precision scoring reads.
 
@@ -129,6 +130,70 @@ class Adagrad(_FoldedPenalties, _TorchAdagrad):
                          initial_accumulator_value=initial_accumulator_value, eps=eps, foreach=False, **kw)
         self.bf16_copies = bool(bf16_copies)
         self._init_penalties()
+        self._touched = {}   # parameter -> (persistent dense gradient [E, d], bitmap): enable_touched_rows
+        self._stepped = []   # the parameters the last step() updated: stepped_params
+
+    # ---- the step over the rows a batch touched (kge_adagrad_step_touched) ----------------------
+    def enable_touched_rows(self, param):
+        """From now on `param` -- a 2-D contiguous float32 GPU table of a group with weight_decay == 0 -- is stepped on
+        the rows its backward MARKED only: allocates, once, a zero [E, d] gradient buffer and a zero row bitmap
+        (`touched_rows(param)`).  A backward that knows the pair (kge_amd.model's score_spo / score_neg /
+        score_neg_blocks nodes) accumulates the table's gradient into the buffer, marks the rows it adds to and leaves
+        `param.grad` None; step() runs the dense update's arithmetic on the marked rows and zeroes the buffer's rows
+        and the bitmap again.  With weight_decay == 0 a dense Adagrad step leaves a row whose gradient is zero bit for
+        bit as it was, so this is the same optimizer without the passes over the whole table."""
+        name = "kge_amd.optim.Adagrad.enable_touched_rows"
+        group = next((g for g in self.param_groups if any(q is param for q in g["params"])), None)
+        if group is None:
+            raise ValueError(f"{name}: not a parameter of this optimizer")
+        if not (torch.is_tensor(param) and param.is_cuda and param.dim() == 2 and param.dtype == torch.float32
+                and param.is_contiguous()):
+            raise ValueError(f"{name}: needs a 2-D contiguous float32 GPU parameter")
+        if group["weight_decay"] != 0:
+            raise ValueError(f"{name}: weight decay moves rows without a gradient: the group's weight_decay must be 0")
+        if param not in self._touched:
+            self._touched[param] = (torch.zeros_like(param, requires_grad=False).detach(),
+                                    engine.touched_bitmap(param.shape[0], param.device))
+        return self._touched[param]
+
+    def touched_rows(self, param):
+        """(grad, bitmap) of a parameter switched to the touched-row step, else None."""
+        return self._touched.get(param)
+
+    def stepped_params(self):
+        """The parameters the last step() updated (kge_amd.train_graph.GraphedStep: `p.grad is not None` misses the
+        touched-row parameters, whose gradient never reaches `.grad`)."""
+        return list(self._stepped)
+
+    def _step_touched(self, p, group):
+        if p.grad is not None:
+            raise RuntimeError("kge_amd.optim.Adagrad: a dense gradient reached a parameter switched to the touched-row "
+                               "step (a backward route that does not know its gradient buffer)")
+        if p in self._penalties:
+            raise RuntimeError("kge_amd.optim.Adagrad: a fused penalty on a parameter switched to the touched-row step "
+                               "(an unweighted term touches every row)")
+        if group["weight_decay"] != 0:
+            raise RuntimeError("kge_amd.optim.Adagrad: weight_decay was set on a group with a touched-row parameter")
+        grad, bitmap = self._touched[p]
+        state = self.state[p]
+        state["step"] += 1
+        step = float(state["step"])
+        minus_clr = -float(group["lr"]) / (1.0 + (step - 1.0) * group["lr_decay"])
+        copy = None
+        if self.bf16_copies:
+            # only the marked rows are rewritten: the copy must be FRESH before (as _step_rows)
+            copy = bf16_copy_of(p)
+            if copy is None:
+                rec = getattr(p, BF16_ATTR, None)
+                if rec is not None and rec[0].shape == p.shape and rec[0].data_ptr() != 0:
+                    copy = rec[0]
+                    copy.copy_(p.detach())
+                else:
+                    copy = p.detach().to(torch.bfloat16)
+        engine.adagrad_step_touched(p.detach(), grad, state["sum"], bitmap, minus_clr, float(group["eps"]), copy)
+        torch.autograd.graph.increment_version(p)
+        if copy is not None:
+            setattr(p, BF16_ATTR, (copy, p._version, p.data_ptr()))
 
     @staticmethod
     def _aligned(*tensors) -> bool:
@@ -191,13 +256,19 @@ class Adagrad(_FoldedPenalties, _TorchAdagrad):
             with torch.enable_grad():
                 loss = closure()
         dense = {}  # device -> [(p, copy, segment)]: every dense table of a device in ONE launch (kge_adagrad_step_multi)
+        stepped = self._stepped = []
         for group in self.param_groups:
             if group.get("maximize") or group.get("differentiable"):
                 raise NotImplementedError("kge_amd.optim.Adagrad: maximize / differentiable are not supported")
             rest = []
             for p in group["params"]:
+                if self._touched and p in self._touched:
+                    self._step_touched(p, group)
+                    stepped.append(p)
+                    continue
                 if p.grad is None:
                     continue
+                stepped.append(p)
                 if self._rows_ok(p, group):
                     self._step_rows(p, group)
                     continue

@@ -138,7 +138,11 @@ class GraphedStep:
         # the gradient buffers the captured backward writes and the captured optimizer reads (static: a replay fills
         # them again; the parameters' .grad attributes may be set to None by the caller in between)
         self.static_grads = [p.grad for g in self.optimizer.param_groups for p in g["params"]]
-        self._stepped = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
+        # (an optimizer that names the parameters its step() updated is asked: kge_amd.optim.Adagrad's touched-row
+        # parameters never see a `.grad`, and their step count belongs into the checkpoint all the same)
+        named = getattr(self.optimizer, "stepped_params", None)
+        self._stepped = list(named()) if callable(named) else \
+            [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
         self._graph = graph
         self._root_one = one
         self._sig = self._signature(inputs)
