@@ -486,6 +486,37 @@ int kge_rank_hist(const int64_t* rank, const int64_t* ties, int num_rankings, in
                   int tie_policy, float* hist, int64_t ldh, int64_t num_ent,
                   int64_t* ranks_out, void* stream);
 
+/* ---- filtered top-k link prediction (topk.hip) ---------------------------- */
+/* The k best entities of (s_i, p_i, ?) (dir = KGE_SP_, a = s) or (?, p_i, o_i) (dir = KGE_PO_, a = o: the direction
+ * codes of kge_ce_fwd) among the entity rows [col_begin, col_begin + m), the columns of up to two filter sets left
+ * out, without the [n, m] score matrix.  It replaces, in the reference, KgeModel.score_sp / score_po
+ * (kge/model/kge_model.py:682-725), the masking of EntityRankingJob._filter_and_rank
+ * (kge/job/eval_entity_ranking.py:233-313: known answers set to -inf) and torch.topk over the masked row.
+ *   scores      the canonical chain: every score has the bits kge_score_sp / kge_score_po store for the
+ *               same tables -- float32 tables, TransE / RotatE at either dtype, bf16 ComplEx / DistMult as under
+ *               KGE_FLAG_EXACT (the entry always takes the exact chain, whatever the flag says);
+ *   order       descending canonical score (NaN counts as -inf, -0.0 as +0.0), equal scores by ASCENDING entity id:
+ *               every element of the result is determined (torch.topk leaves the order among equal scores open);
+ *   f_*         num_filters (<= 2) filter sets as for kge_rank_counts_multi: HOST arrays of device pointers, row i's
+ *               columns are f_col[k][f_begin[k][i] .. f_end[k][i]) (global entity ids; ids outside the scored slice are
+ *               ignored).  A column listed in ANY set is left out -- except keep[i] (keep.ptr == NULL: no exception);
+ *   out_val     [n][ld] float32, out_idx [n][ld] int64, ld >= k: the first k entries of a row are written, nothing
+ *               else.  A row with fewer than k columns left is padded with (-inf, -1) BEHIND its real columns (a real
+ *               column whose score is -inf or NaN is listed, as -inf, in its id order, ahead of the padding);
+ *   workspace   >= kge_topk_workspace_bytes(t, n, m, k, num_filters) bytes, 16-byte aligned, contents irrelevant: the
+ *               call zeroes the filter bits it uses itself and leaves nothing the caller has to preserve.
+ * The result is a pure function of the arguments: it does not depend on how the launch cuts the columns into groups.
+ * Stream-ordered, no host wait.  KGE_ERR_INVALID_ARG: k < 1, k > KGE_TOPK_MAX, ld < k, NULL outputs with n > 0,
+ * m >= 2^32, a slice outside the table, a missing filter pointer; KGE_ERR_WORKSPACE: workspace too small or misaligned;
+ * KGE_ERR_UNSUPPORTED: KGE_FLAG_SPLIT_QUERY / KGE_FLAG_BF16_V3 in the tables' flags, num_filters > 2.  n == 0 or
+ * m == 0: KGE_OK (m == 0: every row is padding). */
+enum { KGE_TOPK_MAX = 128 };
+int64_t kge_topk_workspace_bytes(const kge_tables* t, int64_t n, int64_t m, int k, int num_filters);
+int kge_topk(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, int64_t col_begin, int64_t m, int k,
+             int num_filters, const int64_t* const* f_begin, const int64_t* const* f_end,
+             const int64_t* const* f_col, kge_index keep, float* out_val, int64_t* out_idx, int64_t ld,
+             void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- LookupEmbedder.embed ------------------------------------------------ */
 /* ent_out[i, :] = ent[ent_idx[i], :] (n_ent rows, leading dimension ent_ldo elements) and
  * rel_out[i, :] = rel[rel_idx[i], :] in ONE launch (table dtype; rows of 16-byte multiples).

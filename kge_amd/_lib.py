@@ -109,6 +109,7 @@ class KgeKvsallTyped(ctypes.Structure):
 
 
 KVSALL_COLLATE_MAX_N = 1 << 20  # KGE_KVSALL_COLLATE_MAX_N
+TOPK_MAX = 128  # KGE_TOPK_MAX
 
 # every symbol include/kge_amd.h declares: name -> (restype, argtypes)
 _PT = ctypes.POINTER(KgeTables)
@@ -173,6 +174,9 @@ PROTOTYPES = {
                                                  ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_float,
                                                  ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                                  c_vp, ctypes.POINTER(KgeRankBand)]),
+    "kge_topk_workspace_bytes": (c_i64, [_PT, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
+    "kge_topk": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                c_vp, c_vp, c_vp, KgeIndex, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_table_max_row_norm": (ctypes.c_int, [_PT, c_i64, c_i64, c_vp, c_vp]),
     "kge_rank_band_list_bytes": (c_i64, [c_i64]),
     "kge_score_rank_emb_sp_po": (ctypes.c_int, [_PT, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, KgeIndex, KgeIndex, c_i64,

@@ -142,6 +142,11 @@ int run_eval_end(const EvalLists& L, long long n, long long m, long long rs, lon
 int run_rank_bits(int lists, const long long* const* begin, const long long* const* end, const long long* const* col,
                   const Index* keep, unsigned int* const* bits, long long n, long long col_begin, long long m,
                   long long rs, long long us, int set, hipStream_t st);
+long long topk_groups(long long n, long long m, int* col_tiles);
+int run_topk(int scorer, int dtype, bool use_mfma, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
+             int dr, long long n, long long m, float lp, int k, int nfilt, const unsigned int* const* bits,
+             long long bits_rs, long long bits_us, unsigned long long* part, long long col_begin, float* out_val,
+             long long* out_idx, long long ld, hipStream_t st);
 int run_pairs_bf16_v4_epi(int scorer, int epi, const Operand& A, const Operand* A2, const Operand& R,
                           const Operand& TG, int dir, int d, long long n, long long m, hipStream_t st, void* ws,
                           long long ws_bytes, const CeArgs& ce, unsigned long long* dbg);
@@ -491,12 +496,12 @@ int pairs_entry(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t 
 
 // ---- measurement switches (switches.hpp, include/kge_amd_debug.h) ----
 namespace kge {
-static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-static_assert(SW_COUNT == 19, "g_switch's initialiser");
+static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(SW_COUNT == 20, "g_switch's initialiser");
 static const char* const g_switch_name[SW_COUNT] = {
     "ONE_CALL_PREPARED", "ONE_CALL_V8", "ONE_CALL_V8_MIN_ROWS", "V8_RANK", "RANK_FUSED_FRONT", "BWD_GEMM_LIB",
     "CE_V3", "CE_V8", "V4_OWN_BUILD", "V4_INTERLEAVE", "V4_STORE_SC1", "V6", "V7", "V7_NOSTORE", "V7_PROBE", "V8",
-    "V8_VAR", "V8R_PROBE", "TRANSE_GENERIC"};
+    "V8_VAR", "V8R_PROBE", "TRANSE_GENERIC", "TOPK_COL_TILES"};
 long long sw(Switch s) { return __atomic_load_n(&g_switch[(int)s], __ATOMIC_RELAXED); }
 static int switch_index(const char* name) {
   if (name == nullptr) return -1;
@@ -1356,6 +1361,81 @@ int kge_score_rank_sp_po(const kge_tables* t, kge_index s, kge_index p, kge_inde
   return score_rank_core(t, S, O, P, TG, make_index(o), make_index(s), n, col_begin, m, true_sp, true_po, num_filters,
                          sp_begin, sp_end, sp_col, po_begin, po_end, po_col, atol, rtol, rank_sp, ties_sp, rank_po,
                          ties_po, ld, filter_bits, filter_bits_bytes, workspace, workspace_bytes, stream);
+}
+
+// ---- filtered top-k prediction (topk.hip): KgeModel.score_sp / score_po + the masking of
+// EntityRankingJob._filter_and_rank + torch.topk, without the score matrix.  Workspace: [0, 256) the "no exception"
+// keep id (-1) that run_rank_bits reads when the caller gives none; then the filter bits (the one-sided layout of
+// rank_bits_layout), zeroed by the call; then the groups' lists [n][groups][k].
+namespace {
+struct TopkLayout {
+  RankBitsLayout bl;
+  int64_t bits_off, bits_bytes, part_off, total;
+};
+TopkLayout topk_layout(int64_t n, int64_t m, int k, int num_filters) {
+  TopkLayout L{};
+  L.bl = rank_bits_layout(n, m, num_filters);
+  L.bits_off = 256;
+  L.bits_bytes = num_filters > 0 ? (L.bl.words * 4 + 255) / 256 * 256 : 0;
+  L.part_off = L.bits_off + L.bits_bytes;
+  L.total = L.part_off + n * kge::topk_groups(n, m, nullptr) * (int64_t)k * 8;
+  return L;
+}
+}  // namespace
+
+int64_t kge_topk_workspace_bytes(const kge_tables* t, int64_t n, int64_t m, int k, int num_filters) {
+  if (check_tables(t, false) != KGE_OK || n <= 0 || m <= 0 || m >= (1LL << 32) || k < 1 || k > KGE_TOPK_MAX ||
+      num_filters < 0 || num_filters > 2)
+    return 0;
+  return topk_layout(n, m, k, num_filters).total;
+}
+
+int kge_topk(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, int64_t col_begin, int64_t m, int k,
+             int num_filters, const int64_t* const* f_begin, const int64_t* const* f_end,
+             const int64_t* const* f_col, kge_index keep, float* out_val, int64_t* out_idx, int64_t ld,
+             void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true);
+  if (rc) return rc;
+  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
+  if (k < 1 || k > KGE_TOPK_MAX || ld < k || num_filters < 0) return KGE_ERR_INVALID_ARG;
+  if (n < 0 || m < 0 || m >= (1LL << 32) || col_begin < 0 || col_begin + m > t->num_ent) return KGE_ERR_INVALID_ARG;
+  if (n > 0 && (!out_val || !out_idx)) return KGE_ERR_INVALID_ARG;
+  if ((t->flags & KGE_FLAG_SPLIT_QUERY) || (t->flags & KGE_FLAG_BF16_V3) || num_filters > 2) return KGE_ERR_UNSUPPORTED;
+  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n)) || (rc = check_index(keep, true, n))) return rc;
+  for (int f = 0; n > 0 && f < num_filters; ++f)
+    if (!f_begin || !f_end || !f_col || !f_begin[f] || !f_end[f] || !f_col[f]) return KGE_ERR_INVALID_ARG;
+  if (n == 0) return KGE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (m == 0)  // no column: every row is padding (the merge of no lists)
+    return run_topk(t->scorer, t->dtype, true, Operand{}, Operand{}, Operand{}, dir, (int)t->dim, (int)t->rel_dim, n, 0,
+                    t->l_norm, k, 0, nullptr, 0, 0, nullptr, col_begin, out_val, (long long*)out_idx, ld, st);
+  const TopkLayout L = topk_layout(n, m, k, num_filters);
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < L.total) return KGE_ERR_WORKSPACE;
+  char* const ws = (char*)workspace;
+  unsigned int* bits[2] = {nullptr, nullptr};
+  if (num_filters > 0) {
+    Index kp[2];
+    const long long *lb[2], *le[2], *lc[2];
+    for (int f = 0; f < num_filters; ++f) {
+      // keep.ptr == NULL would read as the identity (row i keeps column i): an id no column has, at stride 0, instead
+      kp[f] = keep.ptr ? make_index(keep) : Index{ws, 0, KGE_I64};
+      lb[f] = (const long long*)f_begin[f];
+      le[f] = (const long long*)f_end[f];
+      lc[f] = (const long long*)f_col[f];
+      bits[f] = (unsigned int*)(ws + L.bits_off) + f;
+    }
+    if (!keep.ptr && !kge::fill_words_async(ws, 0xff, 256, st)) return KGE_ERR_LAUNCH;
+    if (!kge::fill_words_async(ws + L.bits_off, 0, (size_t)L.bits_bytes, st)) return KGE_ERR_LAUNCH;
+    rc = run_rank_bits(num_filters, lb, le, lc, kp, bits, n, col_begin, m, L.bl.rs, L.bl.us, 1, st);
+    if (rc) return rc;
+  }
+  const kge_index all = {nullptr, 0, 0, 1};
+  Operand A = ent_op(t, a), P = rel_op(t, p), TG = ent_op(t, all);
+  TG.base = (const char*)TG.base + col_begin * TG.ld * (t->dtype == KGE_BF16 ? 2 : 4);
+  return run_topk(t->scorer, t->dtype, !(t->flags & KGE_FLAG_NO_MFMA), A, P, TG, dir, (int)t->dim, (int)t->rel_dim, n, m,
+                  t->l_norm, k, num_filters, bits, L.bl.rs, L.bl.us, (unsigned long long*)(ws + L.part_off), col_begin,
+                  out_val, (long long*)out_idx, ld, st);
 }
 
 int kge_score_rank_sp_po_band(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int64_t col_begin,

@@ -13,6 +13,8 @@
 // Mirrors (paths in the reference tree):
 //   score_spo / score_sp / score_po / score_sp_po   KgeModel.score_*      kge/model/kge_model.py:663-789
 //   build_queries_group / score_queries_group       the same scores for a GROUP of batches in one persistent launch
+//   topk                                            score_sp / score_po + the masking of _filter_and_rank
+//                                                   (kge/job/eval_entity_ranking.py:233-313) + torch.topk
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/extension.h>
@@ -628,6 +630,61 @@ std::vector<at::Tensor> kvsall_collate(const at::Tensor& examples, const std::ve
   return res;
 }
 
+// ---- filtered top-k prediction (kge_topk; direction: 1 = sp_, 2 = _po): (values [n, k] float32, ids [n, k] int64).
+// filters: 3 tensors per set (begin [n], end [n], col [nnz], int64); workspace: the caller's (engine.py caches one per
+// device and stream), at least topk_workspace_bytes(...) bytes.
+int64_t topk_workspace_bytes(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t flags,
+                             int64_t n, int64_t m, int64_t k, int64_t num_filters) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, flags);
+  return kge_topk_workspace_bytes(&t, n, m, (int)k, (int)num_filters);
+}
+
+std::vector<at::Tensor> topk(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t flags,
+                             int64_t direction, const at::Tensor& a, const at::Tensor& p, int64_t k,
+                             const std::vector<at::Tensor>& filters, const c10::optional<at::Tensor>& keep,
+                             int64_t col_begin, int64_t m, const c10::optional<at::Tensor>& workspace) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, flags);
+  TORCH_CHECK_VALUE(k >= 1 && k <= KGE_TOPK_MAX, "kge_amd: topk: k must be in [1, ", (int)KGE_TOPK_MAX, "], got ", k);
+  TORCH_CHECK_VALUE(filters.size() % 3 == 0 && filters.size() <= 6, "kge_amd: topk: at most two (begin, end, col) filter sets");
+  std::vector<at::Tensor> keep_alive;
+  int64_t n = -1;
+  const kge_index ai = index_of(a, ent, keep_alive, &n), pi = index_of(p, ent, keep_alive, &n);
+  const kge_index ki = index_of(keep, ent, keep_alive, &n);
+  const int K = (int)(filters.size() / 3);
+  const int64_t* fb[2] = {nullptr, nullptr};
+  const int64_t* fe[2] = {nullptr, nullptr};
+  const int64_t* fc[2] = {nullptr, nullptr};
+  for (int f = 0; f < K; ++f) {
+    for (int j = 0; j < 3; ++j) {
+      const at::Tensor& x = filters[3 * f + j];
+      TORCH_CHECK_VALUE(x.is_cuda() && x.get_device() == ent.get_device() && x.scalar_type() == at::kLong &&
+                            x.is_contiguous() && (j == 2 || x.numel() == n),
+                        "kge_amd: topk: a filter set is (begin [n], end [n], col [nnz]), contiguous int64 on the tables' GPU");
+    }
+    fb[f] = filters[3 * f].data_ptr<int64_t>();
+    fe[f] = filters[3 * f + 1].data_ptr<int64_t>();
+    fc[f] = filters[3 * f + 2].data_ptr<int64_t>();
+  }
+  void* ws = nullptr;
+  int64_t wsb = 0;
+  if (workspace.has_value() && workspace->defined()) {
+    TORCH_CHECK(workspace->is_cuda() && workspace->is_contiguous(), "kge_amd: workspace must be a contiguous GPU tensor");
+    ws = workspace->data_ptr();
+    wsb = workspace->numel() * workspace->element_size();
+  }
+  at::Tensor val = empty_f32({n, k}, ent);
+  at::Tensor idx;
+  try {
+    idx = at::empty({n, k}, ent.options().dtype(at::kLong));
+  } catch (const c10::OutOfMemoryError& e) {
+    TORCH_CHECK(false, "CUDA out of memory (kge_amd, ROCm: ", e.what_without_backtrace(), ")");
+  }
+  check(kge_topk(&t, (int)direction, ai, pi, n, col_begin, m, (int)k, K, fb, fe, fc, ki, val.data_ptr<float>(),
+                 idx.data_ptr<int64_t>(), k, ws, wsb, stream_of(ent)),
+        "kge_topk");
+  return {val, idx};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -657,6 +714,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ns_loss_parts", &ns_loss_parts,
           "negative-sampling loss of one slot from (pos [n], neg [n, K]): (loss_rows, g_pos, g_neg)");
   mod.def("neg_sample", &neg_sample, "one slot's negative samples drawn, filtered and redrawn on the device: (out, stats)");
+  mod.def("topk_workspace_bytes", &topk_workspace_bytes);
+  mod.def("topk", &topk, "the k best unfiltered entities per query without a score matrix: (values [n, k], ids [n, k])");
   mod.def("kvsall_collate", &kvsall_collate,
           "a KvsAll batch from its example numbers, on the device: the collate dictionary and / or the per-type CSR");
 }

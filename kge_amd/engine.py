@@ -1613,6 +1613,81 @@ def score_rank_emb_sp_po(scorer, s_emb, p_emb, o_emb, s_ids, o_ids, targets, col
     return True
 
 
+_TOPK_WS = {}  # (device index, stream) -> workspace of kge_topk (filter bits + the column groups' lists; no initialisation)
+_TOPK_DIR = {"sp_": SP_, "_po": PO_, SP_: SP_, PO_: PO_}
+
+
+def _topk_args(direction, k, filters):
+    """Checked (direction code, k, filter sets) of `topk` -- before any library call."""
+    if direction not in _TOPK_DIR:
+        raise ValueError(f"kge_amd: topk: direction must be 'sp_' or '_po', got {direction!r}")
+    if not isinstance(k, bool) and hasattr(k, "__index__"):
+        k = k.__index__()
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _lib.TOPK_MAX:
+        raise ValueError(f"kge_amd: topk: k must be an int in [1, {_lib.TOPK_MAX}] (KGE_TOPK_MAX), got {k!r}")
+    filters = [] if filters is None else list(filters)
+    if len(filters) > 2:
+        raise ValueError("kge_amd: topk: at most two filter sets")
+    for f in filters:
+        if not isinstance(f, (tuple, list)) or len(f) != 3 or not all(torch.is_tensor(x) for x in f):
+            raise ValueError("kge_amd: topk: a filter set is a (begin [n], end [n], col [nnz]) tuple of tensors")
+        if any(x.dtype != torch.int64 or x.dim() != 1 for x in f):
+            raise ValueError("kge_amd: topk: filter tensors must be 1-D int64")
+        if f[0].numel() != f[1].numel():
+            raise ValueError("kge_amd: topk: a filter set has one (begin, end) pair per query row")
+    return _TOPK_DIR[direction], k, filters
+
+
+def topk(t: Tables, direction, a, p, k, filters=None, keep=None, col_begin: int = 0, col_end=None, flags=None):
+    """(values [n, k] float32, ids [n, k] int64): the k best entities of (a_i, p_i, ?) (direction "sp_", a = s) or
+    (?, p_i, a_i) ("_po", a = o) among the entity rows [col_begin, col_end), without the [n, m] score matrix (kge_topk:
+    what score_sp / score_po + masking + torch.topk give).  Scores are the canonical chain's (the bits of score_sp /
+    score_po; for bf16 ComplEx / DistMult tables those under FLAG_EXACT); descending, equal scores by ascending id, NaN
+    as -inf.  filters = [(begin [n], end [n], col [nnz]), ...] as for rank_counts_multi (at most two; a column listed
+    in any set is left out, except keep[i]); rows with fewer than k columns left are padded with (-inf, -1)."""
+    code, k, filters = _topk_args(direction, k, filters)
+    keepalive = []
+    ai, pi = _index(a, t.device, keepalive), _index(p, t.device, keepalive)
+    n = _same_len(keepalive[:2], "topk")
+    ki = _index(keep, t.device, keepalive)
+    if keep is not None and keepalive[-1].numel() != n:
+        raise ValueError("kge_amd: topk: one keep id per query row")
+    col_end = t.num_ent if col_end is None else int(col_end)
+    col_begin = int(col_begin)
+    m = col_end - col_begin
+    if col_begin < 0 or m < 0 or col_end > t.num_ent:
+        raise ValueError(f"kge_amd: topk: [col_begin, col_end) must lie inside [0, {t.num_ent})")
+    fs = []
+    for f in filters:
+        f = tuple(x if x.is_contiguous() else x.contiguous() for x in f)
+        if any(x.device != t.device for x in f) or f[0].numel() != n:
+            raise ValueError("kge_amd: topk: filter tensors live on the tables' GPU, one (begin, end) pair per row")
+        fs.append(f)
+    K = len(fs)
+    fl = t.flags if flags is None else flags
+    with _on_device(t.device):
+        tc = t.c(fl)
+        st = _stream_handle(t.device)
+        need = _lib.lib().kge_topk_workspace_bytes(ctypes.byref(tc), n, m, k, K)
+        key = (t.device.index, st)
+        buf = _TOPK_WS.get(key)
+        if need > 0 and (buf is None or buf.numel() < need):
+            buf = _TOPK_WS[key] = _empty((max(need, 1 << 20),), t.device, torch.uint8)
+        ex = _ext()
+        if ex and torch.is_tensor(a) and torch.is_tensor(p) and (keep is None or torch.is_tensor(keep)):
+            val, idx = ex.topk(t.ent, t.rel, t.scorer, t.l_norm, fl, code, a, p, k, [x for f in fs for x in f], keep,
+                               col_begin, m, buf if need > 0 else None)
+            return val, idx
+        val, idx = _empty((n, k), t.device), _empty((n, k), t.device, torch.int64)
+        arr = ctypes.c_void_p * max(K, 1)
+        pb, pe, pc = (arr(*[f[j].data_ptr() for f in fs]) if K else None for j in range(3))
+        rc = _lib.lib().kge_topk(ctypes.byref(tc), code, ai, pi, n, col_begin, m, k, K, pb, pe, pc, ki, val.data_ptr(),
+                                 idx.data_ptr(), k, buf.data_ptr() if need > 0 else None, buf.numel() if need > 0 else 0, st)
+        if rc:
+            _lib.check(rc, "kge_topk")
+    return val, idx
+
+
 TIE_POLICIES = {"rounded_mean_rank": 0, "best_rank": 1, "worst_rank": 2}
 
 _EVAL_SCRATCH = {}  # (device index, stream) -> scratch of kge_eval_batch (ranges, target list, true-score block)

@@ -10,7 +10,8 @@ from kge.model.transe import TransE as _RefTransE
 from .. import engine
 from ..model import (BF16Shadow, _FusedBCEDist, _FusedBCEF32, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32,
                      _FusedKLDist, _FusedKLF32, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
-                     bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable)
+                     bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable, predict_filters,
+                     topk_composed)
 
 
 class _HipScorer(RelationalScorer):
@@ -254,6 +255,25 @@ class _FusedScoring:
         ent, rel = self._w()
         return _ScorePairs.apply(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, s,
                                  self._fwd_tables(), self._padded())
+
+    # filtered top-k link prediction (kge_topk): score_sp / score_po + the masking of _filter_and_rank + torch.topk
+    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
+        """`filters`: the sets of kge_amd.model.predict_filters (the reciprocal wrapper looks its subjects up under the
+        ORIGINAL relation and scores under the reciprocal one)."""
+        with torch.no_grad():
+            if self._fused():
+                return engine.topk(self._rank_tables(), direction, a, p, k, filters, keep)
+            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
+            return topk_composed(scores, k, filters, keep)
+
+    def predict_o(self, s: Tensor, p: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        """(values [n, k] float32, ids [n, k] int64): the k best objects of (s_i, p_i, ?), the known answers of
+        `filter_index` (a kge_amd.eval.FilterIndex) left out except keep[i]; descending score, equal scores by
+        ascending entity id, (-inf, -1) where fewer than k entities are left (kge_amd.model.KgeModel.predict_o)."""
+        return self._predict("sp_", s, p, k, predict_filters(filter_index, "sp_", s, p, self._w()[0].device), keep)
+
+    def predict_s(self, p: Tensor, o: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        return self._predict("_po", o, p, k, predict_filters(filter_index, "_po", o, p, self._w()[0].device), keep)
 
     # 1vsAll loss fused with the scoring (HipTrainingJob1vsAll; kge_ce_fwd / kge_ce_bwd)
     def _ce_tables(self):
@@ -546,6 +566,26 @@ class HipReciprocalRelationsModel(_RefReciprocal):
         # model's own check untouched)
         sub = b._targets(entity_subset) if not torch.is_grad_enabled() else entity_subset
         return torch.cat((b.score_sp(s, p, sub), b.score_sp(o, p + self._R(), sub)), dim=1)
+
+    # ---- filtered top-k link prediction: both directions are sp_ queries of the base model (as score_po above); the
+    # known subjects of (?, p, o) are looked up under the ORIGINAL relation p
+    def predict_o(self, s: Tensor, p: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        b = self._base_model
+        dev = b.get_s_embedder()._embeddings.weight.device
+        filters = predict_filters(filter_index, "sp_", s, p, dev)
+        if isinstance(b, _FusedScoring):
+            return b._predict("sp_", s, p, k, filters, keep)
+        with torch.no_grad():
+            return topk_composed(self.score_sp(s, p), k, filters, keep)
+
+    def predict_s(self, p: Tensor, o: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        b = self._base_model
+        dev = b.get_s_embedder()._embeddings.weight.device
+        filters = predict_filters(filter_index, "_po", o, p, dev)
+        if isinstance(b, _FusedScoring):
+            return b._predict("sp_", o, p + self._R(), k, filters, keep)
+        with torch.no_grad():
+            return topk_composed(self.score_po(p, o), k, filters, keep)
 
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
         # (reciprocal_relations_model.py:74-82: "o" scores the triple as it stands, "s" the reversed triple with p + R)

@@ -243,6 +243,28 @@ class KgeModel(torch.nn.Module):
         oe, pe = self._entity_embedder.embed(o), self._relation_embedder.embed(p)
         return self._scorer.score_emb(se, pe, oe, combine="_po")
 
+    # -- filtered top-k link prediction (kge_topk): score_sp / score_po + the masking of _filter_and_rank + torch.topk
+    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filter_index, keep):
+        with torch.no_grad():
+            dev = self._entity_embedder.weight.device
+            filters = predict_filters(filter_index, direction, a, p, dev)
+            if self._fused() and dev.type == "cuda":
+                return engine.topk(self.tables(), direction, a, p, k, filters, keep)
+            # CPU parameters, dropout in training mode: the same rule on the composed scores
+            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
+            return topk_composed(scores, k, filters, keep)
+
+    def predict_o(self, s: Tensor, p: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        """(values [n, k] float32, ids [n, k] int64): the k best objects of (s_i, p_i, ?), the known answers of
+        `filter_index` (a kge_amd.eval.FilterIndex) left out except keep[i]; descending score, equal scores by
+        ascending entity id, NaN as -inf, (-inf, -1) where fewer than k entities are left.  No [n, E] score matrix on
+        the fused path; the same ordering rule (never torch.topk) on the composed one."""
+        return self._predict("sp_", s, p, k, filter_index, keep)
+
+    def predict_s(self, p: Tensor, o: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        """predict_o for the subjects of (?, p_i, o_i)."""
+        return self._predict("_po", o, p, k, filter_index, keep)
+
     # -- 1vsAll loss (SURVEY.md 8f N1): train_1vsAll.py:64-65 / 75-76 in one call
     def _ce_tables(self):
         """bf16 tables for the fused loss, or None (then the loss is composed from score_sp/_po)."""
@@ -486,6 +508,77 @@ def create(model: str, num_entities: int, num_relations: int, dim: int, **kw) ->
 
 # ---- autograd glue (the reference gets backward from torch autograd; here the twins in
 # ---- csrc/bwd.hip are called explicitly) --------------------------------------------------
+def predict_filters(filter_index, direction: str, a: Tensor, p: Tensor, device):
+    """The filter sets of predict_o / predict_s for `engine.topk` / `topk_composed`: [] without an index, else one
+    (begin [n], end [n], col [nnz]) over the known answers of (a_i, p_i, ?) (direction "sp_": the index's (s, p) -> o
+    side) or (?, p_i, a_i) ("_po": its (p, o) -> s side).  The index's arrays are put on `device` once and cached on
+    the index object; on a GPU the ranges come from engine.filter_lookup (no host work per call)."""
+    if filter_index is None:
+        return []
+    cache = filter_index.__dict__.setdefault("_predict_arrays", {})
+    side = "sp" if direction == "sp_" else "po"
+    arrays = cache.get((str(device), side))
+    if arrays is None:
+        keys, starts, values = filter_index._sp if side == "sp" else filter_index._po
+        arrays = cache[(str(device), side)] = tuple(
+            torch.from_numpy(x.astype("int64")).to(device) for x in (keys, starts, values))
+    keys, starts, values = arrays
+    a, p = a.reshape(-1).to(device), p.reshape(-1).to(device)
+    first, second, mult = (a, p, filter_index.R) if side == "sp" else (p, a, filter_index.E)
+    n = a.numel()
+    begin = torch.zeros(n, dtype=torch.int64, device=device)
+    end = torch.zeros(n, dtype=torch.int64, device=device)
+    if keys.numel() and n:
+        if begin.is_cuda:
+            engine.filter_lookup(keys, starts, first, second, mult, begin, end)
+        else:
+            key = first.long() * mult + second.long()
+            pos = torch.searchsorted(keys, key).clamp_(max=keys.numel() - 1)
+            hit = keys[pos] == key
+            begin = torch.where(hit, starts[pos], begin)
+            end = torch.where(hit, starts[pos + 1], end)
+    return [(begin, end, values)]
+
+
+def topk_composed(scores: Tensor, k: int, filters=(), keep: Tensor = None, col_begin: int = 0):
+    """kge_topk's result from a score matrix [n, m] (columns = the entities col_begin ..) with torch operations --
+    predict_o / predict_s where the fused path does not apply (CPU tensors, dropout in training mode).  The same rule:
+    canonical scores (NaN -> -inf, -0.0 -> +0.0), the filters' columns dropped except keep[i], a STABLE sort on
+    (-value, id) -- never torch.topk, which leaves the order among equal scores open --, (-inf, -1) behind a row's
+    last column."""
+    s = scores.detach().float()
+    n, m = s.shape
+    neg_inf = torch.full((), float("-inf"), dtype=s.dtype, device=s.device)
+    s = torch.where(torch.isnan(s), neg_inf, s)
+    s = torch.where(s == 0, torch.zeros((), dtype=s.dtype, device=s.device), s)
+    drop = torch.zeros((n, m), dtype=torch.bool, device=s.device)
+    rows = torch.arange(n, device=s.device)
+    for begin, end, col in filters:
+        cnt = (end - begin).clamp_(min=0)
+        total = int(cnt.sum())
+        if total == 0:
+            continue
+        r = torch.repeat_interleave(rows, cnt)
+        first = torch.cumsum(cnt, 0) - cnt
+        e = torch.arange(total, device=s.device) - first[r] + begin[r]
+        j = col[e] - col_begin
+        ok = (j >= 0) & (j < m)
+        if keep is not None:
+            ok &= col[e] != keep.reshape(-1).to(s.device).long()[r]
+        drop[r[ok], j[ok]] = True
+    # lexicographic (dropped, -value, id): two stable sorts, the minor key first
+    order = torch.sort(-s, dim=1, stable=True).indices
+    order = torch.gather(order, 1, torch.sort(torch.gather(drop, 1, order).to(torch.uint8), dim=1, stable=True).indices)
+    order = order[:, :k]
+    live = ~torch.gather(drop, 1, order)
+    val = torch.where(live, torch.gather(s, 1, order), neg_inf)
+    idx = torch.where(live, order + col_begin, torch.full((), -1, dtype=torch.int64, device=s.device))
+    if k > m:
+        val = torch.cat((val, torch.full((n, k - m), float("-inf"), dtype=s.dtype, device=s.device)), dim=1)
+        idx = torch.cat((idx, torch.full((n, k - m), -1, dtype=torch.int64, device=s.device)), dim=1)
+    return val, idx
+
+
 def _needs_grad(*ts):
     return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
 
