@@ -67,7 +67,9 @@ typedef enum kge_scorer {
   KGE_COMPLEX = 0,            /* kge/model/complex.py                            */
   KGE_DISTMULT = 1,           /* kge/model/distmult.py                           */
   KGE_TRANSE = 2,             /* kge/model/transe.py                             */
-  KGE_ROTATE = 3              /* kge/model/rotate.py                             */
+  KGE_ROTATE = 3,             /* kge/model/rotate.py                             */
+  KGE_TRANSH = 4              /* kge/model/transh.py (float32 tables, l_norm 1 / 2; the entries listed under
+                                 "TransH" below -- every other entry answers KGE_ERR_UNSUPPORTED)             */
 } kge_scorer;
 
 typedef enum kge_dtype { KGE_F32 = 0, KGE_BF16 = 1 } kge_dtype;
@@ -89,7 +91,7 @@ typedef struct kge_tables {
   int64_t num_ent;
   int64_t num_rel;
   int64_t dim;                /* entity embedding size d                         */
-  int64_t rel_dim;            /* d, except RotatE: d/2                           */
+  int64_t rel_dim;            /* d, except RotatE: d/2 and TransH: 2 d           */
   int64_t ent_ld;             /* leading dimensions in elements                  */
   int64_t rel_ld;
   float l_norm;               /* TransE/RotatE `l_norm` option (transe.yaml:11)  */
@@ -145,6 +147,23 @@ typedef struct kge_index {
   int32_t start;              /* see above; 0 otherwise (until round 6 this field was `reserved`, always 0) */
   int64_t stride;             /* in elements */
 } kge_index;
+
+/* ---- TransH (KGE_TRANSH; kge/model/transh.py:11-118; csrc/transh.hip, csrc/transh_device.hpp) -------------------
+ * Tables: float32; a relation row is [d_r | w_r] (translation, then hyperplane normal: the reference's
+ * torch.chunk(p_emb, 2, dim=1)), rel_dim == 2 * dim (anything else: KGE_ERR_INVALID_ARG); l_norm > 0, of which 1 and 2
+ * have a kernel (other p, bf16 tables, dim > 1024: KGE_ERR_UNSUPPORTED).  With w^ = w / max(||w||_2, 1e-12)
+ * (F.normalize), P e = e - (w^ . e) w^ and eps = 1e-6 added to every component (F.pairwise_distance):
+ *   kge_score_spo, kge_score_sp, kge_score_neg (both slots)   score = -|| (P s + d_r) - P o + eps ||_p
+ *   kge_score_po                                              score = -|| (P o - d_r) - P s + eps ||_p
+ * A score is a pure function of its three rows and l_norm -- the same bits from every entry point that scores the
+ * triple in the same form, whatever n, m, the targets' kind (all, range, list), the layout or the launch; a zero w row
+ * gives w^ = 0 (the eps-shifted TransE distance), never NaN.  Nothing of size n * m * dim is built (the reference's
+ * score_emb materialises [m, n, dim]: transh.py:39-78).  kge_score_sp / _po / _sp_po ignore the workspace.
+ * Entry points that take KGE_TRANSH: kge_score_spo, kge_score_sp, kge_score_po, kge_score_sp_po, kge_score_neg,
+ * kge_score_pairs_bwd (no float atomics: two runs give the same bits), kge_score_spo_bwd, kge_score_spo_bwd_accum,
+ * kge_score_neg_bwd_accum.  The backward entry points RECOMPUTE ||v|| for l_norm 2: `scores` is not read and may be
+ * NULL.  Every other entry point that takes kge_tables returns KGE_ERR_UNSUPPORTED for a TransH table and launches
+ * nothing (its *_bytes query returns 0). */
 
 /* ---- library ---------------------------------------------------------- */
 int kge_abi_version(void);

@@ -17,8 +17,8 @@ LIB_PATH = os.path.join(_CSRC, "libkge_amd.so")
 
 KGE_OK = 0
 KGE_ERR_UNSUPPORTED = -2
-COMPLEX, DISTMULT, TRANSE, ROTATE = 0, 1, 2, 3
-SCORERS = {"complex": COMPLEX, "distmult": DISTMULT, "transe": TRANSE, "rotate": ROTATE}
+COMPLEX, DISTMULT, TRANSE, ROTATE, TRANSH = 0, 1, 2, 3, 4
+SCORERS = {"complex": COMPLEX, "distmult": DISTMULT, "transe": TRANSE, "rotate": ROTATE, "transh": TRANSH}
 F32, BF16 = 0, 1
 I32, I64 = 0, 1
 SPO, SP_, PO_ = 0, 1, 2

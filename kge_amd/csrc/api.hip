@@ -7,6 +7,21 @@
 #include <cstdlib>
 
 namespace kge {
+// transh.hip
+int run_transh_pairs(const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n, long long m,
+                     float lp, float* out, long long ldo, hipStream_t st);
+int run_transh_spo(bool neg_mode, const Operand& S, const Operand& R, const Operand& O, int d, long long n, int slot,
+                   const void* neg, int neg_itype, long long neg_ld, long long K, float lp, float* out, long long ldo,
+                   hipStream_t st);
+int run_transh_pairs_bwd(float lp, int dir, const Operand& A, const Operand& R, const Operand& TG, int d, long long n,
+                         long long m, const float* gout, long long ldg, float* g_a, float* g_p, float* g_tgt,
+                         hipStream_t st);
+int run_transh_spo_bwd(float lp, const Operand& S, const Operand& R, const Operand& O, int d, long long n,
+                       const float* gout, bool accum, float* g_s, long long g_s_ld, float* g_p, long long g_p_ld,
+                       float* g_o, long long g_o_ld, hipStream_t st);
+int run_transh_neg_bwd_accum(float lp, const Operand& S, const Operand& R, const Operand& O, int d, long long n, int slot,
+                             const void* neg, int neg_itype, long long neg_ld, long long K, const float* gout,
+                             long long ldg, float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st);
 int run_spo(int scorer, int dtype, bool neg_mode, const Operand& S, const Operand& R,
             const Operand& O, int d, int dr, long long n, int slot, const void* neg,
             int neg_itype, long long neg_ld, long long K, float lp, float* out,
@@ -280,24 +295,34 @@ struct RoctxRange {
 #define KGE_RANGE() RoctxRange kge_roctx_range_(__func__)
 
 
-int check_tables(const kge_tables* t, bool need_ptrs) {
+// The one gate of every entry point that takes kge_tables.  KGE_TRANSH (transh.hip) passes only where the entry says
+// `transh_ok`: the entry points that have a TransH kernel.  Everywhere else a valid TransH table is
+// KGE_ERR_UNSUPPORTED before anything is launched -- no switch over the four older scorers ever sees it.
+int check_tables(const kge_tables* t, bool need_ptrs, bool transh_ok = false) {
   if (!t) return KGE_ERR_INVALID_ARG;
-  if (t->scorer < KGE_COMPLEX || t->scorer > KGE_ROTATE) return KGE_ERR_INVALID_ARG;
+  if (t->scorer < KGE_COMPLEX || t->scorer > KGE_TRANSH) return KGE_ERR_INVALID_ARG;
   if (t->dtype != KGE_F32 && t->dtype != KGE_BF16) return KGE_ERR_INVALID_ARG;
   if (t->dim <= 0 || t->rel_dim <= 0 || t->dim > (1 << 20)) return KGE_ERR_INVALID_ARG;
   const bool cplx = t->scorer == KGE_COMPLEX || t->scorer == KGE_ROTATE;
   if (cplx && (t->dim % 2)) return KGE_ERR_INVALID_ARG;  // rotate.py:82-86
   if (t->scorer == KGE_ROTATE) {
     if (t->rel_dim != t->dim / 2) return KGE_ERR_INVALID_ARG;  // rotate.py:87-93
+  } else if (t->scorer == KGE_TRANSH) {
+    if (t->rel_dim != 2 * t->dim) return KGE_ERR_INVALID_ARG;  // [d_r | w_r]: transh.py:46 torch.chunk(p_emb, 2, dim=1)
   } else if (t->rel_dim != t->dim) {
     return KGE_ERR_INVALID_ARG;
   }
-  if ((t->scorer == KGE_TRANSE || t->scorer == KGE_ROTATE) && !(t->l_norm > 0.0f))
+  if ((t->scorer == KGE_TRANSE || t->scorer == KGE_ROTATE || t->scorer == KGE_TRANSH) && !(t->l_norm > 0.0f))
     return KGE_ERR_INVALID_ARG;
   if (need_ptrs) {
     if (!t->ent || !t->rel) return KGE_ERR_INVALID_ARG;
     if (t->num_ent <= 0 || t->num_rel <= 0) return KGE_ERR_INVALID_ARG;
     if (t->ent_ld < t->dim || t->rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
+  }
+  if (t->scorer == KGE_TRANSH) {
+    // float32 tables, l_norm 1 or 2, rows the row-wise kernels take
+    if (!transh_ok || t->dtype != KGE_F32 || t->dim > 1024 || (t->l_norm != 1.0f && t->l_norm != 2.0f))
+      return KGE_ERR_UNSUPPORTED;
   }
   return KGE_OK;
 }
@@ -482,12 +507,15 @@ int pairs_dispatch(const kge_tables* t, int dir, const Operand& A, const Operand
 int pairs_entry(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
                 kge_index targets, int64_t m, float* out, int64_t ldo, void* ws, int64_t ws_bytes,
                 void* stream) {
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, /*transh_ok=*/true);
   if (rc) return rc;
   if (n < 0 || m < 0 || (!out && n * m > 0) || ldo < m) return KGE_ERR_INVALID_ARG;
   if (n == 0 || m == 0) return KGE_OK;  // empty batch / empty subset: nothing to score
   if ((rc = check_index(a, false)) || (rc = check_index(p, false)) || (rc = check_targets(t, targets, m)))
     return rc;
+  if (t->scorer == KGE_TRANSH)  // (the workspace is not used)
+    return run_transh_pairs(ent_op(t, a), rel_op(t, p), tgt_op(t, targets), dir, (int)t->dim, n, m, t->l_norm, out, ldo,
+                            (hipStream_t)stream);
   return pairs_dispatch(t, dir, ent_op(t, a), rel_op(t, p), tgt_op(t, targets), n, m, out, ldo,
                         ws, ws_bytes, (hipStream_t)stream);
 }
@@ -543,13 +571,16 @@ int kge_device_count(void) {
 int kge_score_spo(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n,
                   float* out, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, /*transh_ok=*/true);
   if (rc) return rc;
   if (n < 0 || (!out && n > 0)) return KGE_ERR_INVALID_ARG;
   if (n == 0) return KGE_OK;
   if ((rc = check_index(s, false)) || (rc = check_index(p, false)) ||
       (rc = check_index(o, false)))
     return rc;
+  if (t->scorer == KGE_TRANSH)
+    return run_transh_spo(false, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, 2, nullptr, 0, 0, 0, t->l_norm,
+                          out, 0, (hipStream_t)stream);
   return run_spo(t->scorer, t->dtype, false, ent_op(t, s), rel_op(t, p), ent_op(t, o),
                  (int)t->dim, (int)t->rel_dim, n, 2, nullptr, 0, 0, 0, t->l_norm, out, 0,
                  (hipStream_t)stream);
@@ -774,7 +805,7 @@ int kge_score_neg(const kge_tables* t, kge_index s, kge_index p, kge_index o, in
                   int slot, const void* neg, int32_t neg_itype, int64_t neg_ld,
                   int64_t num_neg, float* out, int64_t ldo, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, /*transh_ok=*/true);
   if (rc) return rc;
   if (n < 0 || num_neg < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
   if (n * num_neg > 0 && (!out || !neg)) return KGE_ERR_INVALID_ARG;
@@ -785,6 +816,9 @@ int kge_score_neg(const kge_tables* t, kge_index s, kge_index p, kge_index o, in
   if ((rc = check_index(s, false)) || (rc = check_index(p, false)) ||
       (rc = check_index(o, false)))
     return rc;
+  if (t->scorer == KGE_TRANSH)
+    return run_transh_spo(true, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, slot, neg, neg_itype, neg_ld,
+                          num_neg, t->l_norm, out, ldo, (hipStream_t)stream);
   return run_spo(t->scorer, t->dtype, true, ent_op(t, s), rel_op(t, p), ent_op(t, o),
                  (int)t->dim, (int)t->rel_dim, n, slot, neg, neg_itype, neg_ld, num_neg,
                  t->l_norm, out, ldo, (hipStream_t)stream);
@@ -1687,7 +1721,7 @@ int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, 
                         const float* scores, int64_t lds, float* g_a, float* g_p, float* g_tgt,
                         void* workspace, int64_t workspace_bytes, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, /*transh_ok=*/true);
   if (rc) return rc;
   if (t->dtype == KGE_BF16) {  // mixed precision: ComplEx / DistMult on the bf16 matrix cores
     if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
@@ -1711,6 +1745,9 @@ int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, 
   if (!targets.ptr && m != t->num_ent) return KGE_ERR_INVALID_ARG;
   if (n > 65535LL * 64 || m > 65535LL * 64) return KGE_ERR_UNSUPPORTED;
   if (n == 0 || m == 0) return pairs_bwd_empty(t, n, m, g_a, g_p, g_tgt, stream);
+  if (t->scorer == KGE_TRANSH)  // (||v|| is recomputed: `scores` is not read)
+    return run_transh_pairs_bwd(t->l_norm, dir, ent_op(t, a), rel_op(t, p), ent_op(t, targets), (int)t->dim, n, m, gout,
+                                ldg, g_a, g_p, g_tgt, (hipStream_t)stream);
   return run_pairs_bwd(t->scorer, t->l_norm, dir, ent_op(t, a), rel_op(t, p), ent_op(t, targets),
                        (int)t->dim, (int)t->rel_dim, n, m, gout, ldg, scores, lds, g_a, g_p, g_tgt,
                        (hipStream_t)stream, (t->flags & KGE_FLAG_EXACT) != 0);
@@ -2457,13 +2494,16 @@ int kge_score_spo_bwd(const kge_tables* t, kge_index s, kge_index p, kge_index o
                       const float* gout, const float* scores, float* g_s, float* g_p, float* g_o,
                       void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, /*transh_ok=*/true);
   if (rc) return rc;
   if (t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
   if (n < 0 || (n > 0 && (!gout || !g_s || !g_p || !g_o))) return KGE_ERR_INVALID_ARG;
   if ((rc = check_index(s, false)) || (rc = check_index(p, false)) ||
       (rc = check_index(o, false)))
     return rc;
+  if (t->scorer == KGE_TRANSH)
+    return run_transh_spo_bwd(t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, gout, false, g_s,
+                              t->dim, g_p, t->rel_dim, g_o, t->dim, (hipStream_t)stream);
   return run_spo_bwd(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
                      (int)t->rel_dim, n, gout, scores, g_s, g_p, g_o, (hipStream_t)stream);
 }
@@ -2472,13 +2512,16 @@ int kge_score_spo_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
                             const float* gout, const float* scores, float* grad_ent, int64_t grad_ent_ld,
                             float* grad_rel, int64_t grad_rel_ld, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, /*transh_ok=*/true);
   if (rc) return rc;
   if (t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
   if (n < 0 || (n > 0 && (!gout || !grad_ent || !grad_rel))) return KGE_ERR_INVALID_ARG;
   if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
   if ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false)))
     return rc;
+  if (t->scorer == KGE_TRANSH)
+    return run_transh_spo_bwd(t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, gout, true, grad_ent,
+                              grad_ent_ld, grad_rel, grad_rel_ld, grad_ent, grad_ent_ld, (hipStream_t)stream);
   return run_spo_bwd_accum(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
                            (int)t->rel_dim, n, gout, scores, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld,
                            (hipStream_t)stream);
@@ -2490,7 +2533,7 @@ int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
                             int64_t lds, float* grad_ent, int64_t grad_ent_ld, float* grad_rel,
                             int64_t grad_rel_ld, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, /*transh_ok=*/true);
   if (rc) return rc;
   if (t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
   if (n < 0 || num_neg < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
@@ -2500,6 +2543,10 @@ int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
   if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
   if ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false)))
     return rc;
+  if (t->scorer == KGE_TRANSH)
+    return run_transh_neg_bwd_accum(t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, slot, neg,
+                                    neg_itype, neg_ld, num_neg, gout, ldg, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld,
+                                    (hipStream_t)stream);
   return run_neg_bwd_accum(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
                            (int)t->rel_dim, n, slot, neg, neg_itype, neg_ld, num_neg, gout, ldg, scores,
                            lds, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, (hipStream_t)stream);

@@ -723,7 +723,9 @@ def score_neg_bwd_accum(t: Tables, s, p, o, slot: int, neg: torch.Tensor, gout, 
     sc = None
     if scores is not None:
         sc = scores if (scores.dim() == 2 and scores.stride(1) == 1) else scores.contiguous().view(n, K)
-    if n * K > 0 and _neg_bwd_sorted(n, K, t.num_ent):
+    if t.scorer == _lib.TRANSH and NEG_BWD_SORTED:
+        raise ValueError("kge_amd: NEG_BWD_SORTED (the sorted negative-sampling backward) has no TransH kernel")
+    if n * K > 0 and t.scorer != _lib.TRANSH and _neg_bwd_sorted(n, K, t.num_ent):
         flat = neg if neg.is_contiguous() else neg.contiguous()
         # counting sort by entity id: histogram + exclusive prefix sums (torch: plumbing), then one cursor bump per sample
         # (kge_neg_order twice around a cumsum -- torch.bincount would wait for the host: it reads the largest id back)

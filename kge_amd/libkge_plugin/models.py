@@ -6,6 +6,9 @@ from kge import Config, Dataset
 from kge.model.kge_model import KgeModel, RelationalScorer
 from kge.model.rotate import RotatE as _RefRotatE
 from kge.model.transe import TransE as _RefTransE
+from kge.model.transh import TransH as _RefTransH
+from kge.model.transh import TransHScorer as _RefTransHScorer
+from kge.model.transh import transh_set_relation_embedder_dim
 
 from .. import engine
 from ..model import (BF16Shadow, _FusedBCEDist, _FusedBCEF32, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32,
@@ -59,6 +62,18 @@ class HipTransEScorer(_HipScorer):
 
 class HipRotatEScorer(_HipScorer):
     name = "rotate"
+
+
+class HipTransHScorer(_RefTransHScorer):
+    """The scorer of hip_transh.  Dense embeddings (embedder dropout in training mode, `job.device: cpu`, other
+    embedders) are scored by the reference's own score_emb (transh.py:24-82: torch operations, the [m, n, d] form) --
+    the library has no TransH kernel behind kge_score_emb; the index-level calls of HipTransH never come here."""
+
+    name = "transh"
+
+    def __init__(self, config: Config, dataset: Dataset, configuration_key=None):
+        super().__init__(config, dataset, configuration_key)
+        self._norm = float(self._norm)
 
 
 class _FusedScoring:
@@ -503,6 +518,52 @@ class HipTransE(_FusedScoring, _RefTransE):
 
     def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
         _init(self, HipTransEScorer, config, dataset, configuration_key, init_for_load_only)
+
+
+class HipTransH(_FusedScoring, _RefTransH):
+    """`model: hip_transh`: kge/model/transh.py with score_spo / score_sp / score_po / score_sp_po and the negative-
+    sampling blocks on the fused TransH kernels (csrc/transh.hip: no [m, n, d] tensor).  The constructor repeats
+    transh.py:88-106 with the HIP scorer; `penalty` (the soft constraints, transh.py:108-142) is the reference's.
+    float32 tables, l_norm 1 or 2.  Entry points without a TransH kernel are never taken: predict_o / predict_s compose
+    score_sp / score_po with topk_composed, shared negative samples go back to the sampler's own score, the evaluation
+    job counts on the stored score matrix, and the options that select such a kernel are refused by name."""
+
+    def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
+        self._init_configuration(config, configuration_key)
+        transh_set_relation_embedder_dim(config, dataset, self.configuration_key + ".relation_embedder")
+        if float(self.get_option("l_norm")) not in (1.0, 2.0):
+            raise ValueError("hip_transh: l_norm must be 1 or 2 (got {})".format(self.get_option("l_norm")))
+        _init(self, HipTransHScorer, config, dataset, self.configuration_key, init_for_load_only)
+        self.soft_constraint_weight = self.get_option("C")
+
+    def penalty(self, **kwargs):
+        return _RefTransH.penalty(self, **kwargs)
+
+    def _fused(self) -> bool:
+        return super()._fused() and self._w()[0].dtype == torch.float32
+
+    def __setattr__(self, name, value):
+        # hip_1vsAll / hip_KvsAll switch their fused losses on by setting these attributes on the model
+        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
+            raise ValueError("hip_transh: {} is not supported (no TransH kernel behind the fused losses)".format(
+                name.lstrip("_")))
+        super().__setattr__(name, value)
+
+    def set_touched_rows(self, pair):
+        if pair is not None:
+            raise ValueError("hip_transh: touched_rows is not supported")
+        self._touched_rows = None
+
+    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
+        return None  # (no kge_score_neg_shared kernel: the job calls the sampler's own score)
+
+    def _rank_tables(self):
+        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
+
+    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
+        with torch.no_grad():
+            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
+            return topk_composed(scores, k, filters, keep)
 
 
 class HipRotatE(_FusedScoring, _RefRotatE):

@@ -105,6 +105,45 @@ class RotatEScorer(RelationalScorer):
     name = "rotate"
 
 
+class TransHScorer(RelationalScorer):
+    """kge/model/transh.py:11-78 on torch operations: the path of dense embeddings (dropout in training mode, CPU
+    parameters).  The index-level calls of the TransH model run the fused kernels (csrc/transh.hip), which never build
+    the [m, n, d] tensor this form needs for sp_ and _po; kge_score_emb has no TransH kernel."""
+
+    name = "transh"
+
+    @staticmethod
+    def _project(emb: Tensor, norm_vec: Tensor) -> Tensor:
+        w = torch.nn.functional.normalize(norm_vec, p=2, dim=-1)
+        return emb - torch.sum(emb * w, dim=-1, keepdim=True) * w
+
+    def score_emb(self, s_emb: Tensor, p_emb: Tensor, o_emb: Tensor, combine: str) -> Tensor:
+        rel, w = torch.chunk(p_emb, 2, dim=1)  # [d_r | w_r]
+        n = p_emb.size(0)
+        dist = torch.nn.functional.pairwise_distance
+        if combine == "spo":
+            assert s_emb.size(0) == n and o_emb.size(0) == n
+            out = -dist(self._project(s_emb, w) + rel, self._project(o_emb, w), p=self._norm)
+        elif combine == "sp_":
+            m = o_emb.size(0)
+            q = (self._project(s_emb, w) + rel).repeat(m, 1)                      # [m n, d], row j n + i = query i
+            t = self._project(o_emb.repeat_interleave(n, 0), w.repeat(m, 1))     # target j on relation i's hyperplane
+            out = -dist(q, t, p=self._norm).view(m, n).transpose(0, 1)
+        elif combine == "_po":
+            m = s_emb.size(0)
+            q = (self._project(o_emb, w) - rel).repeat(m, 1)
+            t = self._project(s_emb.repeat_interleave(n, 0), w.repeat(m, 1))
+            out = -dist(q, t, p=self._norm).view(m, n).transpose(0, 1)
+        elif combine == "s_o":  # the reference's generic fallback (kge_model.py:202-209) on the spo form above
+            ns = s_emb.size(0)
+            assert o_emb.size(0) == ns
+            return self.score_emb(s_emb.repeat_interleave(n, 0), p_emb.repeat((ns, 1)), o_emb.repeat_interleave(n, 0),
+                                  "spo").view(ns, -1)
+        else:
+            raise ValueError('cannot handle combine="{}"'.format(combine))
+        return out.reshape(n, -1)
+
+
 class KgeModel(torch.nn.Module):
     """Index-level API of kge/model/kge_model.py:587-789 on the fused kernels."""
 
@@ -128,6 +167,13 @@ class KgeModel(torch.nn.Module):
         self._shadow = BF16Shadow() if (score_dtype == torch.bfloat16 and dtype == torch.float32 and
                                         self.scorer_cls in (ComplExScorer, DistMultScorer)) else None
         rel_dim = dim // 2 if self.scorer_cls is RotatEScorer else dim
+        if self.scorer_cls is TransHScorer:
+            rel_dim = 2 * dim  # [d_r | w_r]: transh.yaml's relation_embedder.dim: -1 (transh.py:88-94)
+            if fused_dist_loss:  # no TransH kernel behind kge_ce_dist_* / kge_kl_dist_* / kge_bce_dist_*
+                raise ValueError("TransH: fused_dist_loss is not supported (the losses are composed from score_sp / "
+                                 "score_po)")
+            if float(l_norm) not in (1.0, 2.0):
+                raise ValueError("TransH: l_norm must be 1 or 2 (got {})".format(l_norm))
         if self.scorer_cls in (RotatEScorer, ComplExScorer) and dim % 2:
             raise ValueError("{} requires embeddings of even dimensionality (got {})".format(
                 type(self).__name__, dim))
@@ -147,6 +193,8 @@ class KgeModel(torch.nn.Module):
         score_spo, score_neg and score_neg_blocks hand it to their autograd nodes, whose backward then accumulates the
         entity gradient into the persistent `grad`, marks the rows in `bitmap` and leaves the table's `.grad` None
         (DESIGN.md section 25).  Shared samples (score_neg_shared) keep the dense gradient: do not mix them with it."""
+        if pair is not None and self.scorer_cls is TransHScorer:
+            raise ValueError("TransH: touched_rows is not supported")
         self._touched_rows = pair
 
     # -- accessors (kge_model.py:649-661)
@@ -202,7 +250,8 @@ class KgeModel(torch.nn.Module):
         """[n, K]: score of triple i with slot (0 = s, 2 = o) replaced by the shared sample (unique, drop, repeat) --
         NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score (kge/util/sampler.py:428-463, 537-578);
         equals score_neg on engine.shared_samples(unique, drop, repeat, n)."""
-        if self._fused() and slot in (0, 2) and neg_shared_fusable(self._entity_embedder.weight, s.numel()):
+        if self._fused() and slot in (0, 2) and self._scorer.name != "transh" and \
+                neg_shared_fusable(self._entity_embedder.weight, s.numel()):
             return _ScoreNegShared.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
                                          self._relation_embedder.weight, s, p, o, int(slot), unique, drop, repeat)
         return self.score_neg(s, p, o, slot, engine.shared_samples(unique, drop, repeat, s.reshape(-1).numel()))
@@ -248,9 +297,9 @@ class KgeModel(torch.nn.Module):
         with torch.no_grad():
             dev = self._entity_embedder.weight.device
             filters = predict_filters(filter_index, direction, a, p, dev)
-            if self._fused() and dev.type == "cuda":
+            if self._fused() and dev.type == "cuda" and self._scorer.name != "transh":
                 return engine.topk(self.tables(), direction, a, p, k, filters, keep)
-            # CPU parameters, dropout in training mode: the same rule on the composed scores
+            # CPU parameters, dropout in training mode, TransH (no kge_topk kernel): the same rule on the composed scores
             scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
             return topk_composed(scores, k, filters, keep)
 
@@ -499,7 +548,12 @@ class RotatE(KgeModel):
         w[:] = torch.remainder(w + math.pi, 2.0 * math.pi) - math.pi
 
 
-MODELS = {"complex": ComplEx, "distmult": DistMult, "transe": TransE, "rotate": RotatE}
+class TransH(KgeModel):
+    """kge/model/transh.py:81-118: relation rows [d_r | w_r] of width 2 dim; float32, l_norm 1 or 2."""
+    scorer_cls = TransHScorer
+
+
+MODELS = {"complex": ComplEx, "distmult": DistMult, "transe": TransE, "rotate": RotatE, "transh": TransH}
 
 
 def create(model: str, num_entities: int, num_relations: int, dim: int, **kw) -> KgeModel:
