@@ -68,8 +68,10 @@ typedef enum kge_scorer {
   KGE_DISTMULT = 1,           /* kge/model/distmult.py                           */
   KGE_TRANSE = 2,             /* kge/model/transe.py                             */
   KGE_ROTATE = 3,             /* kge/model/rotate.py                             */
-  KGE_TRANSH = 4              /* kge/model/transh.py (float32 tables, l_norm 1 / 2; the entries listed under
+  KGE_TRANSH = 4,             /* kge/model/transh.py (float32 tables, l_norm 1 / 2; the entries listed under
                                  "TransH" below -- every other entry answers KGE_ERR_UNSUPPORTED)             */
+  KGE_RESCAL = 5              /* kge/model/rescal.py (float32 tables, dim <= KGE_RESCAL_MAX_DIM; the entries listed
+                                 under "RESCAL" below -- every other entry answers KGE_ERR_UNSUPPORTED)       */
 } kge_scorer;
 
 typedef enum kge_dtype { KGE_F32 = 0, KGE_BF16 = 1 } kge_dtype;
@@ -91,7 +93,7 @@ typedef struct kge_tables {
   int64_t num_ent;
   int64_t num_rel;
   int64_t dim;                /* entity embedding size d                         */
-  int64_t rel_dim;            /* d, except RotatE: d/2 and TransH: 2 d           */
+  int64_t rel_dim;            /* d, except RotatE: d/2, TransH: 2 d, RESCAL: d*d */
   int64_t ent_ld;             /* leading dimensions in elements                  */
   int64_t rel_ld;
   float l_norm;               /* TransE/RotatE `l_norm` option (transe.yaml:11)  */
@@ -165,6 +167,34 @@ typedef struct kge_index {
  * NULL.  Every other entry point that takes kge_tables returns KGE_ERR_UNSUPPORTED for a TransH table and launches
  * nothing (its *_bytes query returns 0). */
 
+/* ---- RESCAL (KGE_RESCAL; kge/model/rescal.py:9-52; csrc/rescal.hip, csrc/rescal_device.hpp) ----------------------
+ * Tables: float32; a relation row is the mixing matrix M_p, row-major d x d (rescal.py:25: p_emb.view(-1, d, d)),
+ * rel_dim == dim * dim (anything else: KGE_ERR_INVALID_ARG); l_norm is ignored.  bf16 tables and
+ * dim > KGE_RESCAL_MAX_DIM: KGE_ERR_UNSUPPORTED.  score(s, p, o) = s^T M_p o, computed in two stages:
+ *   query       sp_ / spo / neg slot 2:  q_b = sum_a s_a M[a][b]   (q = M^T s)
+ *               _po / neg slot 0:        q_a = sum_b M[a][b] o_b   (q = M o)
+ *               a sum of K = dim terms: term k goes to partial sum (k / 4) mod 8, every partial sum is an fma chain in
+ *               ascending k from +0, and the eight are added as ((p0 + p4) + (p2 + p6)) + ((p1 + p5) + (p3 + p7)).
+ *               q is a pure function of its two rows: the same bits from kge_rescal_queries and from every scoring
+ *               entry, whatever n, the index type or stride, the table pitch or alignment and the launch.
+ *   contraction kge_score_sp / _po / _sp_po: the float32 chain of the ComplEx / DistMult pair kernels over (q, target) --
+ *               bit-equal to kge_score_emb(KGE_DISTMULT float32, KGE_SP_ / KGE_PO_, q, ones, target rows), with and
+ *               without KGE_FLAG_NO_MFMA.  kge_score_spo / kge_score_neg: the row-wise summation of kge_score_spo over
+ *               (q, the other row) -- bit-equal to kge_score_emb(KGE_DISTMULT, KGE_SPO, q, ones, rows); q stays on chip.
+ * kge_score_neg, slot 0 (the subject varies): q' = M_p o_i is built ONCE per positive and every sampled subject s' is
+ * scored as q' . s'.  The reference's order for this triple is (s'^T M_p) . o, a d x d product per sample: the same
+ * real number, a different rounding -- inside the float64 bound of the triple, not bit-equal to kge_score_spo.  Slot 2
+ * IS bit-equal to kge_score_spo on the expanded triples.
+ * Workspace: kge_score_sp / _po / _sp_po build their queries in the caller's workspace (kge_score_workspace_bytes(t, n):
+ * two blocks of n * dim floats and one row of ones; kge_score_sp / _po use the first block); NULL or too small with
+ * n * m > 0: KGE_ERR_WORKSPACE.  No zeroing needed.  kge_score_pairs_bwd likewise (kge_score_bwd_workspace_bytes).
+ * Entry points that take KGE_RESCAL: kge_score_spo, kge_score_sp, kge_score_po, kge_score_sp_po, kge_score_neg,
+ * kge_score_pairs_bwd (no float atomics: two runs give the same bits; g_p is [n, dim * dim]), kge_score_spo_bwd,
+ * kge_score_spo_bwd_accum, kge_score_neg_bwd_accum (grad_rel is [num_rel, dim * dim]; float atomics), and
+ * kge_rescal_queries.  `scores` of the backward entries is not read and may be NULL.  Every other entry point that
+ * takes kge_tables returns KGE_ERR_UNSUPPORTED for a RESCAL table and launches nothing (its *_bytes query returns 0). */
+#define KGE_RESCAL_MAX_DIM 256
+
 /* ---- library ---------------------------------------------------------- */
 int kge_abi_version(void);
 const char* kge_status_string(int status);
@@ -192,6 +222,14 @@ int kge_device_count(void);
  * control block -- flag lines and the degraded word -- lies at its start, at an offset that does not
  * depend on n; the query vectors follow.  The same holds for the workspaces of the fused-loss entry points below. */
 int64_t kge_score_workspace_bytes(const kge_tables* t, int64_t n);
+
+/* RESCAL queries ("RESCAL" above): q[i * q_ld + :] = M_{p_i}^T ent[a_i] (dir = KGE_SP_) or M_{p_i} ent[a_i] (KGE_PO_),
+ * dim floats per row, q_ld >= dim -- the dense query rows the scoring entries contract with the targets (the same
+ * bits).  kge_rescal_queries_bytes: n * dim floats; 0 for a table the entry does not take.  Every scorer but KGE_RESCAL:
+ * KGE_ERR_UNSUPPORTED.  n == 0: KGE_OK, nothing is launched. */
+int64_t kge_rescal_queries_bytes(const kge_tables* t, int64_t n);
+int kge_rescal_queries(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, float* q, int64_t q_ld,
+                       void* stream);
 
 /* out[i] = score(s[i], p[i], o[i]), i < n.        KgeModel.score_spo */
 int kge_score_spo(const kge_tables* t, kge_index s, kge_index p, kge_index o,

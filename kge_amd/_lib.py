@@ -17,8 +17,9 @@ LIB_PATH = os.path.join(_CSRC, "libkge_amd.so")
 
 KGE_OK = 0
 KGE_ERR_UNSUPPORTED = -2
-COMPLEX, DISTMULT, TRANSE, ROTATE, TRANSH = 0, 1, 2, 3, 4
-SCORERS = {"complex": COMPLEX, "distmult": DISTMULT, "transe": TRANSE, "rotate": ROTATE, "transh": TRANSH}
+COMPLEX, DISTMULT, TRANSE, ROTATE, TRANSH, RESCAL = 0, 1, 2, 3, 4, 5
+SCORERS = {"complex": COMPLEX, "distmult": DISTMULT, "transe": TRANSE, "rotate": ROTATE, "transh": TRANSH,
+           "rescal": RESCAL}
 F32, BF16 = 0, 1
 I32, I64 = 0, 1
 SPO, SP_, PO_ = 0, 1, 2
@@ -110,6 +111,7 @@ class KgeKvsallTyped(ctypes.Structure):
 
 KVSALL_COLLATE_MAX_N = 1 << 20  # KGE_KVSALL_COLLATE_MAX_N
 TOPK_MAX = 128  # KGE_TOPK_MAX
+RESCAL_MAX_DIM = 256  # KGE_RESCAL_MAX_DIM
 
 # every symbol include/kge_amd.h declares: name -> (restype, argtypes)
 _PT = ctypes.POINTER(KgeTables)
@@ -122,6 +124,8 @@ PROTOTYPES = {
     "kge_score_sp": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_score_po": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_score_sp_po": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kge_rescal_queries_bytes": (c_i64, [_PT, c_i64]),
+    "kge_rescal_queries": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
     "kge_queries_bytes": (c_i64, [_PT, ctypes.c_int, c_i64]),
     "kge_build_queries": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
     "kge_score_queries": (ctypes.c_int, [_PT, ctypes.c_int, c_vp, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_i64,

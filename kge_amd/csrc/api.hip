@@ -7,6 +7,22 @@
 #include <cstdlib>
 
 namespace kge {
+// rescal.hip
+int run_rescal_queries(const Operand& A, const Operand* A2, const Operand& R, int dir, int d, long long n, float* q,
+                       float* q2, long long q_ld, float* ones, hipStream_t st);
+int run_rescal_rows(bool neg_mode, const Operand& S, const Operand& R, const Operand& O, int d, long long n, int slot,
+                    const void* neg, int neg_itype, long long neg_ld, long long K, float* out, long long ldo,
+                    hipStream_t st);
+long long rescal_pairs_bwd_workspace_bytes(int d, long long n);
+int run_rescal_pairs_bwd(int dir, const Operand& A, const Operand& R, const Operand& TG, int d, long long n, long long m,
+                         const float* gout, long long ldg, float* g_a, float* g_p, float* g_tgt, void* ws,
+                         long long ws_bytes, hipStream_t st);
+int run_rescal_spo_bwd(const Operand& S, const Operand& R, const Operand& O, int d, long long n, const float* gout,
+                       bool accum, float* g_s, long long g_s_ld, float* g_p, long long g_p_ld, float* g_o,
+                       long long g_o_ld, hipStream_t st);
+int run_rescal_neg_bwd_accum(const Operand& S, const Operand& R, const Operand& O, int d, long long n, int slot,
+                             const void* neg, int neg_itype, long long neg_ld, long long K, const float* gout,
+                             long long ldg, float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st);
 // transh.hip
 int run_transh_pairs(const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n, long long m,
                      float lp, float* out, long long ldo, hipStream_t st);
@@ -297,10 +313,11 @@ struct RoctxRange {
 
 // The one gate of every entry point that takes kge_tables.  KGE_TRANSH (transh.hip) passes only where the entry says
 // `transh_ok`: the entry points that have a TransH kernel.  Everywhere else a valid TransH table is
-// KGE_ERR_UNSUPPORTED before anything is launched -- no switch over the four older scorers ever sees it.
-int check_tables(const kge_tables* t, bool need_ptrs, bool transh_ok = false) {
+// KGE_ERR_UNSUPPORTED before anything is launched -- no switch over the four older scorers ever sees it.  KGE_RESCAL
+// (rescal.hip) likewise, where the entry says `rescal_ok`.
+int check_tables(const kge_tables* t, bool need_ptrs, bool transh_ok = false, bool rescal_ok = false) {
   if (!t) return KGE_ERR_INVALID_ARG;
-  if (t->scorer < KGE_COMPLEX || t->scorer > KGE_TRANSH) return KGE_ERR_INVALID_ARG;
+  if (t->scorer < KGE_COMPLEX || t->scorer > KGE_RESCAL) return KGE_ERR_INVALID_ARG;
   if (t->dtype != KGE_F32 && t->dtype != KGE_BF16) return KGE_ERR_INVALID_ARG;
   if (t->dim <= 0 || t->rel_dim <= 0 || t->dim > (1 << 20)) return KGE_ERR_INVALID_ARG;
   const bool cplx = t->scorer == KGE_COMPLEX || t->scorer == KGE_ROTATE;
@@ -309,6 +326,8 @@ int check_tables(const kge_tables* t, bool need_ptrs, bool transh_ok = false) {
     if (t->rel_dim != t->dim / 2) return KGE_ERR_INVALID_ARG;  // rotate.py:87-93
   } else if (t->scorer == KGE_TRANSH) {
     if (t->rel_dim != 2 * t->dim) return KGE_ERR_INVALID_ARG;  // [d_r | w_r]: transh.py:46 torch.chunk(p_emb, 2, dim=1)
+  } else if (t->scorer == KGE_RESCAL) {
+    if (t->rel_dim != t->dim * t->dim) return KGE_ERR_INVALID_ARG;  // M_p, d x d: rescal.py:25 p_emb.view(-1, d, d)
   } else if (t->rel_dim != t->dim) {
     return KGE_ERR_INVALID_ARG;
   }
@@ -324,7 +343,18 @@ int check_tables(const kge_tables* t, bool need_ptrs, bool transh_ok = false) {
     if (!transh_ok || t->dtype != KGE_F32 || t->dim > 1024 || (t->l_norm != 1.0f && t->l_norm != 2.0f))
       return KGE_ERR_UNSUPPORTED;
   }
+  if (t->scorer == KGE_RESCAL) {
+    // float32 tables, a matrix the workgroup-per-row kernels take (l_norm is ignored)
+    if (!rescal_ok || t->dtype != KGE_F32 || t->dim > KGE_RESCAL_MAX_DIM) return KGE_ERR_UNSUPPORTED;
+  }
   return KGE_OK;
+}
+
+// ---- RESCAL (rescal.hip): the workspace of kge_score_sp / _po / _sp_po ------------------------------------------------
+// [ ones: dim floats, rounded up to 4 | q of the first block: n * dim | q of the second block: n * dim ]
+static int64_t rescal_ones_floats(const kge_tables* t) { return (t->dim + 3) & ~(int64_t)3; }
+static int64_t rescal_score_ws_bytes(const kge_tables* t, int64_t n, int blocks) {
+  return (rescal_ones_floats(t) + blocks * n * t->dim) * (int64_t)sizeof(float);
 }
 
 int check_index(const kge_index& ix, bool allow_null, int64_t len = 1) {
@@ -504,10 +534,21 @@ int pairs_dispatch(const kge_tables* t, int dir, const Operand& A, const Operand
                          m, t->l_norm, out, ldo, st, /*round_query=*/!keep_f32_query);
 }
 
+// The second stage of a RESCAL sp_ / _po call: the float32 pair kernel of ComplEx / DistMult (score_pairs_f32.hip, its
+// matrix-core form or the KGE_FLAG_NO_MFMA twin) on the dense query rows q with a relation row of ones -- what
+// kge_score_emb(KGE_DISTMULT, dir, q, ones, targets) runs: q * 1.0f is exact.
+int rescal_contract(const kge_tables* t, int dir, const float* q, const float* ones, const Operand& TG, int64_t n,
+                    int64_t m, float* out, int64_t ldo, hipStream_t st) {
+  const Index ident{nullptr, 1, KGE_I64};
+  const Operand Q{q, t->dim, ident}, ONES{ones, 0, ident};  // (ld 0: every query reads the one row of ones)
+  return run_pairs_exact(KGE_DISTMULT, KGE_F32, !(t->flags & KGE_FLAG_NO_MFMA), Q, ONES, TG, dir, (int)t->dim, (int)t->dim,
+                         n, m, 1.0f, out, ldo, st, /*round_query=*/true);
+}
+
 int pairs_entry(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n,
                 kge_index targets, int64_t m, float* out, int64_t ldo, void* ws, int64_t ws_bytes,
                 void* stream) {
-  int rc = check_tables(t, true, /*transh_ok=*/true);
+  int rc = check_tables(t, true, /*transh_ok=*/true, /*rescal_ok=*/true);
   if (rc) return rc;
   if (n < 0 || m < 0 || (!out && n * m > 0) || ldo < m) return KGE_ERR_INVALID_ARG;
   if (n == 0 || m == 0) return KGE_OK;  // empty batch / empty subset: nothing to score
@@ -516,6 +557,15 @@ int pairs_entry(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t 
   if (t->scorer == KGE_TRANSH)  // (the workspace is not used)
     return run_transh_pairs(ent_op(t, a), rel_op(t, p), tgt_op(t, targets), dir, (int)t->dim, n, m, t->l_norm, out, ldo,
                             (hipStream_t)stream);
+  if (t->scorer == KGE_RESCAL) {
+    if (!ws || ws_bytes < rescal_score_ws_bytes(t, n, 1)) return KGE_ERR_WORKSPACE;
+    float* const ones = (float*)ws;
+    float* const q = ones + rescal_ones_floats(t);
+    rc = run_rescal_queries(ent_op(t, a), nullptr, rel_op(t, p), dir, (int)t->dim, n, q, nullptr, t->dim, ones,
+                            (hipStream_t)stream);
+    if (rc) return rc;
+    return rescal_contract(t, dir, q, ones, tgt_op(t, targets), n, m, out, ldo, (hipStream_t)stream);
+  }
   return pairs_dispatch(t, dir, ent_op(t, a), rel_op(t, p), tgt_op(t, targets), n, m, out, ldo,
                         ws, ws_bytes, (hipStream_t)stream);
 }
@@ -571,7 +621,7 @@ int kge_device_count(void) {
 int kge_score_spo(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n,
                   float* out, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true, /*transh_ok=*/true);
+  int rc = check_tables(t, true, /*transh_ok=*/true, /*rescal_ok=*/true);
   if (rc) return rc;
   if (n < 0 || (!out && n > 0)) return KGE_ERR_INVALID_ARG;
   if (n == 0) return KGE_OK;
@@ -581,12 +631,17 @@ int kge_score_spo(const kge_tables* t, kge_index s, kge_index p, kge_index o, in
   if (t->scorer == KGE_TRANSH)
     return run_transh_spo(false, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, 2, nullptr, 0, 0, 0, t->l_norm,
                           out, 0, (hipStream_t)stream);
+  if (t->scorer == KGE_RESCAL)
+    return run_rescal_rows(false, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, 2, nullptr, 0, 0, 0, out, 0,
+                           (hipStream_t)stream);
   return run_spo(t->scorer, t->dtype, false, ent_op(t, s), rel_op(t, p), ent_op(t, o),
                  (int)t->dim, (int)t->rel_dim, n, 2, nullptr, 0, 0, 0, t->l_norm, out, 0,
                  (hipStream_t)stream);
 }
 
 int64_t kge_score_workspace_bytes(const kge_tables* t, int64_t n) {
+  if (t && n > 0 && t->scorer == KGE_RESCAL)  // the dense queries of both blocks + a row of ones (rescal.hip)
+    return check_tables(t, false, false, /*rescal_ok=*/true) == KGE_OK ? rescal_score_ws_bytes(t, n, 2) : 0;
   if (!t || n <= 0 || t->dtype != KGE_BF16) return 0;
   if (t->scorer != KGE_COMPLEX && t->scorer != KGE_DISTMULT) return 0;
   if (t->dim != 128 && t->dim != 256 && t->dim != 512) return 0;
@@ -625,6 +680,25 @@ static int query_operands(const kge_tables* t, int combine, const kge_index& s, 
   A2 = ent_op(t, o);
   R = rel_op(t, p);
   return KGE_OK;
+}
+
+int64_t kge_rescal_queries_bytes(const kge_tables* t, int64_t n) {
+  if (!t || n <= 0 || t->scorer != KGE_RESCAL || check_tables(t, false, false, /*rescal_ok=*/true) != KGE_OK) return 0;
+  return n * t->dim * (int64_t)sizeof(float);
+}
+
+int kge_rescal_queries(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, float* q, int64_t q_ld,
+                       void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true, false, /*rescal_ok=*/true);
+  if (rc) return rc;
+  if (t->scorer != KGE_RESCAL) return KGE_ERR_UNSUPPORTED;
+  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
+  if (n < 0 || (n > 0 && !q) || q_ld < t->dim) return KGE_ERR_INVALID_ARG;
+  if (n == 0) return KGE_OK;
+  if ((rc = check_index(a, false)) || (rc = check_index(p, false))) return rc;
+  return run_rescal_queries(ent_op(t, a), nullptr, rel_op(t, p), dir, (int)t->dim, n, q, nullptr, q_ld, nullptr,
+                            (hipStream_t)stream);
 }
 
 int kge_build_queries(const kge_tables* t, int combine, kge_index s, kge_index p, kge_index o, int64_t n,
@@ -795,6 +869,26 @@ int kge_score_sp_po(const kge_tables* t, kge_index s, kge_index p, kge_index o, 
                                         (hipStream_t)stream);
     if (rc2 != KGE_ERR_UNSUPPORTED) return rc2;
   }
+  if (t && t->scorer == KGE_RESCAL) {  // both blocks' queries by one build launch, then the two contractions
+    int rc = check_tables(t, true, false, /*rescal_ok=*/true);
+    if (rc) return rc;
+    if (n < 0 || m < 0 || (!out && n * m > 0)) return KGE_ERR_INVALID_ARG;
+    if (n == 0 || m == 0) return KGE_OK;
+    if ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false)) ||
+        (rc = check_targets(t, targets, m)))
+      return rc;
+    if (!workspace || workspace_bytes < rescal_score_ws_bytes(t, n, 2)) return KGE_ERR_WORKSPACE;
+    float* const ones = (float*)workspace;
+    float* const q1 = ones + rescal_ones_floats(t);
+    float* const q2 = q1 + n * t->dim;
+    const Operand O = ent_op(t, o), TG = tgt_op(t, targets);
+    rc = run_rescal_queries(ent_op(t, s), &O, rel_op(t, p), KGE_SP_, (int)t->dim, n, q1, q2, t->dim, ones,
+                            (hipStream_t)stream);
+    if (rc) return rc;
+    rc = rescal_contract(t, KGE_SP_, q1, ones, TG, n, m, out, ldo, (hipStream_t)stream);
+    if (rc) return rc;
+    return rescal_contract(t, KGE_PO_, q2, ones, TG, n, m, out + m, ldo, (hipStream_t)stream);
+  }
   int rc = pairs_entry(t, KGE_SP_, s, p, n, targets, m, out, ldo, workspace, workspace_bytes, stream);
   if (rc) return rc;
   return pairs_entry(t, KGE_PO_, o, p, n, targets, m, out ? out + m : out, ldo, workspace,
@@ -805,7 +899,7 @@ int kge_score_neg(const kge_tables* t, kge_index s, kge_index p, kge_index o, in
                   int slot, const void* neg, int32_t neg_itype, int64_t neg_ld,
                   int64_t num_neg, float* out, int64_t ldo, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true, /*transh_ok=*/true);
+  int rc = check_tables(t, true, /*transh_ok=*/true, /*rescal_ok=*/true);
   if (rc) return rc;
   if (n < 0 || num_neg < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
   if (n * num_neg > 0 && (!out || !neg)) return KGE_ERR_INVALID_ARG;
@@ -819,6 +913,9 @@ int kge_score_neg(const kge_tables* t, kge_index s, kge_index p, kge_index o, in
   if (t->scorer == KGE_TRANSH)
     return run_transh_spo(true, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, slot, neg, neg_itype, neg_ld,
                           num_neg, t->l_norm, out, ldo, (hipStream_t)stream);
+  if (t->scorer == KGE_RESCAL)
+    return run_rescal_rows(true, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, slot, neg, neg_itype, neg_ld,
+                           num_neg, out, ldo, (hipStream_t)stream);
   return run_spo(t->scorer, t->dtype, true, ent_op(t, s), rel_op(t, p), ent_op(t, o),
                  (int)t->dim, (int)t->rel_dim, n, slot, neg, neg_itype, neg_ld, num_neg,
                  t->l_norm, out, ldo, (hipStream_t)stream);
@@ -1700,6 +1797,8 @@ int kge_rank_hist(const int64_t* rank, const int64_t* ties, int num_rankings, in
 
 int64_t kge_score_bwd_workspace_bytes(const kge_tables* t, int64_t n, int64_t m) {
   if (!t || n <= 0 || m <= 0) return 0;
+  if (t->scorer == KGE_RESCAL)  // the dense queries and their gradient (rescal.hip)
+    return check_tables(t, false, false, /*rescal_ok=*/true) == KGE_OK ? rescal_pairs_bwd_workspace_bytes((int)t->dim, n) : 0;
   return pairs_bwd_workspace_bytes(t->dtype, t->scorer, (int)t->dim, n, m);
 }
 
@@ -1721,7 +1820,7 @@ int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, 
                         const float* scores, int64_t lds, float* g_a, float* g_p, float* g_tgt,
                         void* workspace, int64_t workspace_bytes, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true, /*transh_ok=*/true);
+  int rc = check_tables(t, true, /*transh_ok=*/true, /*rescal_ok=*/true);
   if (rc) return rc;
   if (t->dtype == KGE_BF16) {  // mixed precision: ComplEx / DistMult on the bf16 matrix cores
     if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
@@ -1748,6 +1847,9 @@ int kge_score_pairs_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, 
   if (t->scorer == KGE_TRANSH)  // (||v|| is recomputed: `scores` is not read)
     return run_transh_pairs_bwd(t->l_norm, dir, ent_op(t, a), rel_op(t, p), ent_op(t, targets), (int)t->dim, n, m, gout,
                                 ldg, g_a, g_p, g_tgt, (hipStream_t)stream);
+  if (t->scorer == KGE_RESCAL)  // (`scores` is not read)
+    return run_rescal_pairs_bwd(dir, ent_op(t, a), rel_op(t, p), ent_op(t, targets), (int)t->dim, n, m, gout, ldg, g_a, g_p,
+                                g_tgt, workspace, workspace_bytes, (hipStream_t)stream);
   return run_pairs_bwd(t->scorer, t->l_norm, dir, ent_op(t, a), rel_op(t, p), ent_op(t, targets),
                        (int)t->dim, (int)t->rel_dim, n, m, gout, ldg, scores, lds, g_a, g_p, g_tgt,
                        (hipStream_t)stream, (t->flags & KGE_FLAG_EXACT) != 0);
@@ -2494,7 +2596,7 @@ int kge_score_spo_bwd(const kge_tables* t, kge_index s, kge_index p, kge_index o
                       const float* gout, const float* scores, float* g_s, float* g_p, float* g_o,
                       void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true, /*transh_ok=*/true);
+  int rc = check_tables(t, true, /*transh_ok=*/true, /*rescal_ok=*/true);
   if (rc) return rc;
   if (t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
   if (n < 0 || (n > 0 && (!gout || !g_s || !g_p || !g_o))) return KGE_ERR_INVALID_ARG;
@@ -2504,6 +2606,9 @@ int kge_score_spo_bwd(const kge_tables* t, kge_index s, kge_index p, kge_index o
   if (t->scorer == KGE_TRANSH)
     return run_transh_spo_bwd(t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, gout, false, g_s,
                               t->dim, g_p, t->rel_dim, g_o, t->dim, (hipStream_t)stream);
+  if (t->scorer == KGE_RESCAL)
+    return run_rescal_spo_bwd(ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, gout, false, g_s, t->dim, g_p,
+                              t->rel_dim, g_o, t->dim, (hipStream_t)stream);
   return run_spo_bwd(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
                      (int)t->rel_dim, n, gout, scores, g_s, g_p, g_o, (hipStream_t)stream);
 }
@@ -2512,7 +2617,7 @@ int kge_score_spo_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
                             const float* gout, const float* scores, float* grad_ent, int64_t grad_ent_ld,
                             float* grad_rel, int64_t grad_rel_ld, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true, /*transh_ok=*/true);
+  int rc = check_tables(t, true, /*transh_ok=*/true, /*rescal_ok=*/true);
   if (rc) return rc;
   if (t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
   if (n < 0 || (n > 0 && (!gout || !grad_ent || !grad_rel))) return KGE_ERR_INVALID_ARG;
@@ -2522,6 +2627,9 @@ int kge_score_spo_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
   if (t->scorer == KGE_TRANSH)
     return run_transh_spo_bwd(t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, gout, true, grad_ent,
                               grad_ent_ld, grad_rel, grad_rel_ld, grad_ent, grad_ent_ld, (hipStream_t)stream);
+  if (t->scorer == KGE_RESCAL)
+    return run_rescal_spo_bwd(ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, gout, true, grad_ent, grad_ent_ld,
+                              grad_rel, grad_rel_ld, grad_ent, grad_ent_ld, (hipStream_t)stream);
   return run_spo_bwd_accum(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
                            (int)t->rel_dim, n, gout, scores, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld,
                            (hipStream_t)stream);
@@ -2533,7 +2641,7 @@ int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
                             int64_t lds, float* grad_ent, int64_t grad_ent_ld, float* grad_rel,
                             int64_t grad_rel_ld, void* stream) {
   KGE_RANGE();
-  int rc = check_tables(t, true, /*transh_ok=*/true);
+  int rc = check_tables(t, true, /*transh_ok=*/true, /*rescal_ok=*/true);
   if (rc) return rc;
   if (t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
   if (n < 0 || num_neg < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
@@ -2547,6 +2655,9 @@ int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
     return run_transh_neg_bwd_accum(t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, slot, neg,
                                     neg_itype, neg_ld, num_neg, gout, ldg, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld,
                                     (hipStream_t)stream);
+  if (t->scorer == KGE_RESCAL)
+    return run_rescal_neg_bwd_accum(ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, slot, neg, neg_itype, neg_ld,
+                                    num_neg, gout, ldg, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, (hipStream_t)stream);
   return run_neg_bwd_accum(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
                            (int)t->rel_dim, n, slot, neg, neg_itype, neg_ld, num_neg, gout, ldg, scores,
                            lds, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, (hipStream_t)stream);

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT_QUERY, I32, I64, PO_,
-                   SCORERS, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
+                   RESCAL_MAX_DIM, SCORERS, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
 
 __all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "shared_samples",
            "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "neg_sample", "kvsall_collate", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
@@ -88,7 +88,7 @@ def _workspace(tc, n, device, enable=True, stream=None):
     """(ptr, bytes) of the per-(device, stream) scratch buffer the bf16 path uses to build the
     query vectors once (kge_score_workspace_bytes); (None, 0) when the call needs none.
     Stream-ordered reuse: one buffer per stream, grown on demand through torch's allocator."""
-    if not enable:
+    if not enable and tc.scorer != _lib.RESCAL:  # (RESCAL builds its queries in the workspace: never optional)
         return None, 0
     nk = (tc.dtype, tc.scorer, tc.dim, n, tc.flags & FLAG_SPLIT_QUERY)  # (split queries: about twice the bytes)
     need = _WS_NEED.get(nk)
@@ -352,6 +352,26 @@ def score_sp_po(t: Tables, s, p, o, entity_subset=None, flags=None) -> torch.Ten
                                         ws, wsb, st)
         if rc:
             _lib.check(rc, "kge_score_sp_po")
+    return out
+
+
+def rescal_queries(t: Tables, direction: str, a, p, out=None) -> torch.Tensor:
+    """[n, d] dense RESCAL queries (kge_rescal_queries): q_i = M_{p_i}^T ent[a_i] (direction "sp_") or M_{p_i} ent[a_i]
+    ("_po") -- the rows kge_score_sp / kge_score_po contract with the targets, in the same bits."""
+    if direction not in ("sp_", "_po"):
+        raise ValueError("kge_amd: rescal_queries: direction is 'sp_' or '_po'")
+    keep = []
+    ai, pi = _index(a, t.device, keep), _index(p, t.device, keep)
+    n = _same_len(keep[:2], "rescal_queries")
+    d = t.ent.shape[1]
+    if out is None:
+        out = _empty((n, d), t.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape != (n, d) or out.stride(1) != 1 or out.device != t.device:
+        raise ValueError("kge_amd: rescal_queries: out must be a float32 [n, d] tensor with unit inner stride")
+    with _on_device(t.device):
+        _lib.check(_lib.lib().kge_rescal_queries(ctypes.byref(t.c()), SP_ if direction == "sp_" else PO_, ai, pi, n,
+                                                 out.data_ptr(), out.stride(0) if n > 1 else d, _stream(t.device)),
+                   "kge_rescal_queries")
     return out
 
 
@@ -723,9 +743,10 @@ def score_neg_bwd_accum(t: Tables, s, p, o, slot: int, neg: torch.Tensor, gout, 
     sc = None
     if scores is not None:
         sc = scores if (scores.dim() == 2 and scores.stride(1) == 1) else scores.contiguous().view(n, K)
-    if t.scorer == _lib.TRANSH and NEG_BWD_SORTED:
-        raise ValueError("kge_amd: NEG_BWD_SORTED (the sorted negative-sampling backward) has no TransH kernel")
-    if n * K > 0 and t.scorer != _lib.TRANSH and _neg_bwd_sorted(n, K, t.num_ent):
+    if t.scorer in (_lib.TRANSH, _lib.RESCAL) and NEG_BWD_SORTED:
+        raise ValueError("kge_amd: NEG_BWD_SORTED (the sorted negative-sampling backward) has no {} kernel".format(
+            "TransH" if t.scorer == _lib.TRANSH else "RESCAL"))
+    if n * K > 0 and t.scorer not in (_lib.TRANSH, _lib.RESCAL) and _neg_bwd_sorted(n, K, t.num_ent):
         flat = neg if neg.is_contiguous() else neg.contiguous()
         # counting sort by entity id: histogram + exclusive prefix sums (torch: plumbing), then one cursor bump per sample
         # (kge_neg_order twice around a cumsum -- torch.bincount would wait for the host: it reads the largest id back)

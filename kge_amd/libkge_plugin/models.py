@@ -4,6 +4,9 @@ from torch import Tensor
 
 from kge import Config, Dataset
 from kge.model.kge_model import KgeModel, RelationalScorer
+from kge.model.rescal import Rescal as _RefRescal
+from kge.model.rescal import RescalScorer as _RefRescalScorer
+from kge.model.rescal import rescal_set_relation_embedder_dim
 from kge.model.rotate import RotatE as _RefRotatE
 from kge.model.transe import TransE as _RefTransE
 from kge.model.transh import TransH as _RefTransH
@@ -74,6 +77,15 @@ class HipTransHScorer(_RefTransHScorer):
     def __init__(self, config: Config, dataset: Dataset, configuration_key=None):
         super().__init__(config, dataset, configuration_key)
         self._norm = float(self._norm)
+
+
+class HipRescalScorer(_RefRescalScorer):
+    """The scorer of hip_rescal.  Dense embeddings (embedder dropout in training mode, `job.device: cpu`, other
+    embedders) are scored by the reference's own score_emb (rescal.py:14-52: bmm + mm) -- the library has no RESCAL
+    kernel behind kge_score_emb; the index-level calls of HipRescal never come here."""
+
+    name = "rescal"
+    _norm = 1.0  # (the tables' l_norm: ignored by the RESCAL kernels)
 
 
 class _FusedScoring:
@@ -552,6 +564,47 @@ class HipTransH(_FusedScoring, _RefTransH):
     def set_touched_rows(self, pair):
         if pair is not None:
             raise ValueError("hip_transh: touched_rows is not supported")
+        self._touched_rows = None
+
+    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
+        return None  # (no kge_score_neg_shared kernel: the job calls the sampler's own score)
+
+    def _rank_tables(self):
+        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
+
+    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
+        with torch.no_grad():
+            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
+            return topk_composed(scores, k, filters, keep)
+
+
+class HipRescal(_FusedScoring, _RefRescal):
+    """`model: hip_rescal`: kge/model/rescal.py with score_spo / score_sp / score_po / score_sp_po and the negative-
+    sampling blocks on the fused RESCAL kernels (csrc/rescal.hip: the gathered mat-vec q = M_p^T s / M_p o, then the
+    float32 contraction of ComplEx / DistMult).  The constructor repeats rescal.py:58-75 with the HIP scorer.  float32
+    tables, entity dim <= 256.  Entry points without a RESCAL kernel are never taken: predict_o / predict_s compose
+    score_sp / score_po with topk_composed, shared negative samples go back to the sampler's own score, the evaluation
+    job counts on the stored score matrix, and the options that select such a kernel are refused by name."""
+
+    def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
+        self._init_configuration(config, configuration_key)
+        rescal_set_relation_embedder_dim(config, dataset, self.configuration_key + ".relation_embedder")
+        _init(self, HipRescalScorer, config, dataset, self.configuration_key, init_for_load_only)
+
+    def _fused(self) -> bool:
+        w = self._w()[0]
+        return super()._fused() and w.dtype == torch.float32 and w.shape[1] <= engine.RESCAL_MAX_DIM
+
+    def __setattr__(self, name, value):
+        # hip_1vsAll / hip_KvsAll switch their fused losses on by setting these attributes on the model
+        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
+            raise ValueError("hip_rescal: {} is not supported (no RESCAL kernel behind the fused losses)".format(
+                name.lstrip("_")))
+        super().__setattr__(name, value)
+
+    def set_touched_rows(self, pair):
+        if pair is not None:
+            raise ValueError("hip_rescal: touched_rows is not supported")
         self._touched_rows = None
 
     def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):

@@ -144,6 +144,38 @@ class TransHScorer(RelationalScorer):
         return out.reshape(n, -1)
 
 
+class RescalScorer(RelationalScorer):
+    """kge/model/rescal.py:14-52 on torch operations: the path of dense embeddings (dropout in training mode, CPU
+    parameters).  A relation row is the mixing matrix M, row-major d x d; the index-level calls of the Rescal model run
+    the fused kernels (csrc/rescal.hip); kge_score_emb has no RESCAL kernel."""
+
+    name = "rescal"
+
+    def score_emb(self, s_emb: Tensor, p_emb: Tensor, o_emb: Tensor, combine: str) -> Tensor:
+        n, d = p_emb.size(0), s_emb.size(-1)
+        mix = p_emb.view(-1, d, d)
+        if combine == "spo":
+            assert s_emb.size(0) == n and o_emb.size(0) == n
+            out = (s_emb.unsqueeze(1).bmm(mix).view(n, d) * o_emb).sum(dim=-1)
+        elif combine == "sp_":
+            out = s_emb.unsqueeze(1).bmm(mix).view(n, d).mm(o_emb.transpose(0, 1))
+        elif combine == "_po":
+            out = mix.bmm(o_emb.unsqueeze(2)).view(n, d).mm(s_emb.transpose(0, 1))
+        elif combine == "s_o":  # the reference's generic fallback (kge_model.py:202-209) on the spo form above
+            ns = s_emb.size(0)
+            assert o_emb.size(0) == ns
+            return self.score_emb(s_emb.repeat_interleave(n, 0), p_emb.repeat((ns, 1)), o_emb.repeat_interleave(n, 0),
+                                  "spo").view(ns, -1)
+        else:
+            raise ValueError('cannot handle combine="{}"'.format(combine))
+        return out.view(n, -1)
+
+
+# scorers whose predictions, shared samples and evaluation take the composed paths (no kge_topk / kge_score_neg_shared /
+# fused-loss kernel behind them)
+_COMPOSED_ONLY = ("transh", "rescal")
+
+
 class KgeModel(torch.nn.Module):
     """Index-level API of kge/model/kge_model.py:587-789 on the fused kernels."""
 
@@ -174,6 +206,14 @@ class KgeModel(torch.nn.Module):
                                  "score_po)")
             if float(l_norm) not in (1.0, 2.0):
                 raise ValueError("TransH: l_norm must be 1 or 2 (got {})".format(l_norm))
+        if self.scorer_cls is RescalScorer:
+            rel_dim = dim * dim  # M_p: rescal.yaml's relation_embedder.dim: -1 (rescal.py:78-95)
+            for opt, on in (("fused_dist_loss", fused_dist_loss), ("fused_f32_loss", fused_f32_loss)):
+                if on:  # no RESCAL kernel behind the fused losses
+                    raise ValueError("Rescal: {} is not supported (the losses are composed from score_sp / "
+                                     "score_po)".format(opt))
+            if dim > engine.RESCAL_MAX_DIM:
+                raise ValueError("Rescal: dim must be at most {} (got {})".format(engine.RESCAL_MAX_DIM, dim))
         if self.scorer_cls in (RotatEScorer, ComplExScorer) and dim % 2:
             raise ValueError("{} requires embeddings of even dimensionality (got {})".format(
                 type(self).__name__, dim))
@@ -193,8 +233,8 @@ class KgeModel(torch.nn.Module):
         score_spo, score_neg and score_neg_blocks hand it to their autograd nodes, whose backward then accumulates the
         entity gradient into the persistent `grad`, marks the rows in `bitmap` and leaves the table's `.grad` None
         (DESIGN.md section 25).  Shared samples (score_neg_shared) keep the dense gradient: do not mix them with it."""
-        if pair is not None and self.scorer_cls is TransHScorer:
-            raise ValueError("TransH: touched_rows is not supported")
+        if pair is not None and self.scorer_cls in (TransHScorer, RescalScorer):
+            raise ValueError("{}: touched_rows is not supported".format(type(self).__name__))
         self._touched_rows = pair
 
     # -- accessors (kge_model.py:649-661)
@@ -250,7 +290,9 @@ class KgeModel(torch.nn.Module):
         """[n, K]: score of triple i with slot (0 = s, 2 = o) replaced by the shared sample (unique, drop, repeat) --
         NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score (kge/util/sampler.py:428-463, 537-578);
         equals score_neg on engine.shared_samples(unique, drop, repeat, n)."""
-        if self._fused() and slot in (0, 2) and self._scorer.name != "transh" and \
+        if self.scorer_cls is RescalScorer:  # no kge_score_neg_shared kernel, and none composed in its place
+            raise ValueError("Rescal: shared negative samples (score_neg_shared) are not supported; use score_neg")
+        if self._fused() and slot in (0, 2) and self._scorer.name not in _COMPOSED_ONLY and \
                 neg_shared_fusable(self._entity_embedder.weight, s.numel()):
             return _ScoreNegShared.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
                                          self._relation_embedder.weight, s, p, o, int(slot), unique, drop, repeat)
@@ -297,9 +339,9 @@ class KgeModel(torch.nn.Module):
         with torch.no_grad():
             dev = self._entity_embedder.weight.device
             filters = predict_filters(filter_index, direction, a, p, dev)
-            if self._fused() and dev.type == "cuda" and self._scorer.name != "transh":
+            if self._fused() and dev.type == "cuda" and self._scorer.name not in _COMPOSED_ONLY:
                 return engine.topk(self.tables(), direction, a, p, k, filters, keep)
-            # CPU parameters, dropout in training mode, TransH (no kge_topk kernel): the same rule on the composed scores
+            # CPU parameters, dropout in training mode, TransH / RESCAL (no kge_topk kernel): the same rule on the composed scores
             scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
             return topk_composed(scores, k, filters, keep)
 
@@ -553,7 +595,13 @@ class TransH(KgeModel):
     scorer_cls = TransHScorer
 
 
-MODELS = {"complex": ComplEx, "distmult": DistMult, "transe": TransE, "rotate": RotatE, "transh": TransH}
+class Rescal(KgeModel):
+    """kge/model/rescal.py:55-95: relation rows are d x d mixing matrices (width dim * dim); float32, dim <= 256."""
+    scorer_cls = RescalScorer
+
+
+MODELS = {"complex": ComplEx, "distmult": DistMult, "transe": TransE, "rotate": RotatE, "transh": TransH,
+          "rescal": Rescal}
 
 
 def create(model: str, num_entities: int, num_relations: int, dim: int, **kw) -> KgeModel:
