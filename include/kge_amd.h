@@ -195,6 +195,55 @@ typedef struct kge_index {
  * takes kge_tables returns KGE_ERR_UNSUPPORTED for a RESCAL table and launches nothing (its *_bytes query returns 0). */
 #define KGE_RESCAL_MAX_DIM 256
 
+/* ---- Relational Tucker3 (kge/model/relational_tucker3.py, kge/model/embedder/tucker3_relation_embedder.py;
+ * csrc/tucker3.hip, csrc/tucker3_device.hpp) ---------------------------------------------------------------------------
+ * relational_tucker3 is RESCAL whose mixing matrices are projected from a small base table: with base rows B [num_rel,
+ * base_dim] and the projection weight W [dim * dim, base_dim] (torch.nn.Linear(base_dim, dim * dim, bias=False).weight),
+ *   M_p = (B[p] @ W^T).view(dim, dim),    out[i][j] = sum_{k < base_dim} B[idx_i][k] * W[j][k],   j < dim * dim.
+ * The projected rows are a KGE_RESCAL relation table (rel_dim == dim * dim): there is no scorer of its own.
+ * Canonical arithmetic: ONE fused multiply-add chain per element, ascending k, from +0 --
+ *   acc = +0;  acc = fma(B[idx_i][k], W[j][k], acc)  for k = 0 .. base_dim - 1
+ * -- exactly base_dim operations (no zero padding).  An element of `out` is a pure function of its B row and its W row:
+ * the same bits whatever n, num_rel, the row's position in the call, the index type / stride / range form, the pitch or
+ * 16-byte alignment of any operand, and the launch.
+ * Gate: dtype != KGE_F32, dim > KGE_RESCAL_MAX_DIM or base_dim > KGE_TUCKER3_MAX_BASE_DIM: KGE_ERR_UNSUPPORTED before
+ * any launch (the *_bytes queries return 0); every base_dim >= 1 up to the cap works.  NULL tables, non-positive sizes,
+ * base_ld < base_dim, proj_ld < base_dim, output pitches below their widths: KGE_ERR_INVALID_ARG. */
+#define KGE_TUCKER3_MAX_BASE_DIM 1024
+
+typedef struct kge_tucker3 {
+  const void* base;           /* B [num_rel, base_dim], row-major                 */
+  const void* proj;           /* W [dim * dim, base_dim], row-major               */
+  int32_t dtype;              /* kge_dtype of both: KGE_F32                       */
+  int32_t reserved_;          /* 0                                                */
+  int64_t num_rel;
+  int64_t dim;                /* entity embedding size d                          */
+  int64_t base_dim;           /* d_r                                              */
+  int64_t base_ld;            /* leading dimensions in elements                   */
+  int64_t proj_ld;
+} kge_tucker3;
+
+/* out[i * out_ld + j] as above, i < n, out_ld >= dim * dim.  idx: a kge_index over base rows; ptr == NULL is the
+ * contiguous range start, start + 1, ..., start + n - 1 (0 <= start, start + n <= num_rel): "all relations" is the range
+ * 0 .. num_rel.  kge_tucker3_project_bytes: n * dim * dim floats (0 for a gated table).  n == 0: KGE_OK, nothing is
+ * launched. */
+int64_t kge_tucker3_project_bytes(const kge_tucker3* t, int64_t n);
+int kge_tucker3_project(const kge_tucker3* t, kge_index idx, int64_t n, float* out, int64_t out_ld, void* stream);
+
+/* Backward of the projection from g_out [n, dim * dim] (g_ld >= dim * dim):
+ *   g_brows [n, base_dim]        = g_out * W           (row i belongs to base row idx_i: the caller scatters it)
+ *   g_w     [dim * dim, base_dim] = g_out^T * B[idx]
+ * on the float32 matrix cores (the gradient products of kge_score_pairs_bwd), plain stores, no float atomics: two runs
+ * give the same bits.  The bits depend on the shape and, per output, on whether it is dense (ld == base_dim) and 16-byte
+ * aligned (the split-K form of the product is taken only then); any pitch and alignment is accepted.  Either output may
+ * be NULL (not computed).  The library allocates nothing: split-K partials and
+ * the gathered base rows go to `workspace` (kge_tucker3_project_bwd_workspace_bytes(t, n); no zeroing needed); NULL or
+ * too small with n > 0: KGE_ERR_WORKSPACE. */
+int64_t kge_tucker3_project_bwd_workspace_bytes(const kge_tucker3* t, int64_t n);
+int kge_tucker3_project_bwd(const kge_tucker3* t, kge_index idx, int64_t n, const float* g_out, int64_t g_ld,
+                            float* g_brows, int64_t g_brows_ld, float* g_w, int64_t g_w_ld, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* ---- library ---------------------------------------------------------- */
 int kge_abi_version(void);
 const char* kge_status_string(int status);

@@ -112,6 +112,13 @@ class KgeKvsallTyped(ctypes.Structure):
 KVSALL_COLLATE_MAX_N = 1 << 20  # KGE_KVSALL_COLLATE_MAX_N
 TOPK_MAX = 128  # KGE_TOPK_MAX
 RESCAL_MAX_DIM = 256  # KGE_RESCAL_MAX_DIM
+TUCKER3_MAX_BASE_DIM = 1024  # KGE_TUCKER3_MAX_BASE_DIM
+
+
+class KgeTucker3(ctypes.Structure):
+    _fields_ = [("base", c_vp), ("proj", c_vp), ("dtype", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+                ("num_rel", c_i64), ("dim", c_i64), ("base_dim", c_i64), ("base_ld", c_i64), ("proj_ld", c_i64)]
+
 
 # every symbol include/kge_amd.h declares: name -> (restype, argtypes)
 _PT = ctypes.POINTER(KgeTables)
@@ -126,6 +133,11 @@ PROTOTYPES = {
     "kge_score_sp_po": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_rescal_queries_bytes": (c_i64, [_PT, c_i64]),
     "kge_rescal_queries": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
+    "kge_tucker3_project_bytes": (c_i64, [ctypes.POINTER(KgeTucker3), c_i64]),
+    "kge_tucker3_project": (ctypes.c_int, [ctypes.POINTER(KgeTucker3), KgeIndex, c_i64, c_vp, c_i64, c_vp]),
+    "kge_tucker3_project_bwd_workspace_bytes": (c_i64, [ctypes.POINTER(KgeTucker3), c_i64]),
+    "kge_tucker3_project_bwd": (ctypes.c_int, [ctypes.POINTER(KgeTucker3), KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                               c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_queries_bytes": (c_i64, [_PT, ctypes.c_int, c_i64]),
     "kge_build_queries": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
     "kge_score_queries": (ctypes.c_int, [_PT, ctypes.c_int, c_vp, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_i64,

@@ -7,6 +7,13 @@
 #include <cstdlib>
 
 namespace kge {
+// tucker3.hip
+int run_tucker3_project(const float* Bm, long long ldb, const Index& idx, const float* W, long long ldw, int d, int dr,
+                        long long n, float* out, long long ldo, hipStream_t st);
+long long tucker3_bwd_workspace_bytes(int d, int dr, long long n);
+int run_tucker3_project_bwd(const float* Bm, long long ldb, const Index& idx, const float* W, long long ldw, int d, int dr,
+                            long long n, const float* gout, long long ldg, float* g_brows, long long g_brows_ld,
+                            float* g_w, long long g_w_ld, void* ws, long long ws_bytes, hipStream_t st);
 // rescal.hip
 int run_rescal_queries(const Operand& A, const Operand* A2, const Operand& R, int dir, int d, long long n, float* q,
                        float* q2, long long q_ld, float* ones, hipStream_t st);
@@ -699,6 +706,72 @@ int kge_rescal_queries(const kge_tables* t, int dir, kge_index a, kge_index p, i
   if ((rc = check_index(a, false)) || (rc = check_index(p, false))) return rc;
   return run_rescal_queries(ent_op(t, a), nullptr, rel_op(t, p), dir, (int)t->dim, n, q, nullptr, q_ld, nullptr,
                             (hipStream_t)stream);
+}
+
+// ---- Relational Tucker3 (tucker3.hip): the gate of the four entries, and the base-row index (a range or a vector) ------
+static int check_tucker3(const kge_tucker3* t, bool need_ptrs) {
+  if (!t) return KGE_ERR_INVALID_ARG;
+  if (t->dtype != KGE_F32 && t->dtype != KGE_BF16) return KGE_ERR_INVALID_ARG;
+  if (t->num_rel <= 0 || t->dim <= 0 || t->base_dim <= 0 || t->dim > (1 << 20)) return KGE_ERR_INVALID_ARG;
+  if (t->base_ld < t->base_dim || t->proj_ld < t->base_dim) return KGE_ERR_INVALID_ARG;
+  if (need_ptrs && (!t->base || !t->proj)) return KGE_ERR_INVALID_ARG;
+  if (t->dtype != KGE_F32 || t->dim > KGE_RESCAL_MAX_DIM || t->base_dim > KGE_TUCKER3_MAX_BASE_DIM)
+    return KGE_ERR_UNSUPPORTED;
+  return KGE_OK;
+}
+
+// ptr == NULL: rows start .. start + n - 1 of the base table (`*Bm` moves there, the kernel reads no index)
+static int tucker3_index(const kge_tucker3* t, const kge_index& ix, int64_t n, const float** Bm, Index* out) {
+  *Bm = (const float*)t->base;
+  if (!ix.ptr) {
+    if (ix.start < 0 || (int64_t)ix.start + n > t->num_rel) return KGE_ERR_INVALID_ARG;
+    *Bm += (int64_t)ix.start * t->base_ld;
+    *out = Index{nullptr, 1, KGE_I64};
+    return KGE_OK;
+  }
+  if (ix.start != 0 || (ix.itype != KGE_I32 && ix.itype != KGE_I64) || ix.stride < 1) return KGE_ERR_INVALID_ARG;
+  *out = make_index(ix);
+  return KGE_OK;
+}
+
+int64_t kge_tucker3_project_bytes(const kge_tucker3* t, int64_t n) {
+  if (n <= 0 || check_tucker3(t, false) != KGE_OK) return 0;
+  return n * t->dim * t->dim * (int64_t)sizeof(float);
+}
+
+int kge_tucker3_project(const kge_tucker3* t, kge_index idx, int64_t n, float* out, int64_t out_ld, void* stream) {
+  KGE_RANGE();
+  int rc = check_tucker3(t, true);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !out) || out_ld < t->dim * t->dim) return KGE_ERR_INVALID_ARG;
+  const float* Bm;
+  Index ix;
+  if ((rc = tucker3_index(t, idx, n, &Bm, &ix))) return rc;
+  if (n == 0) return KGE_OK;
+  return run_tucker3_project(Bm, t->base_ld, ix, (const float*)t->proj, t->proj_ld, (int)t->dim, (int)t->base_dim, n, out,
+                             out_ld, (hipStream_t)stream);
+}
+
+int64_t kge_tucker3_project_bwd_workspace_bytes(const kge_tucker3* t, int64_t n) {
+  if (n <= 0 || check_tucker3(t, false) != KGE_OK) return 0;
+  return tucker3_bwd_workspace_bytes((int)t->dim, (int)t->base_dim, n);
+}
+
+int kge_tucker3_project_bwd(const kge_tucker3* t, kge_index idx, int64_t n, const float* g_out, int64_t g_ld,
+                            float* g_brows, int64_t g_brows_ld, float* g_w, int64_t g_w_ld, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  int rc = check_tucker3(t, true);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !g_out) || g_ld < t->dim * t->dim) return KGE_ERR_INVALID_ARG;
+  if ((g_brows && g_brows_ld < t->base_dim) || (g_w && g_w_ld < t->base_dim)) return KGE_ERR_INVALID_ARG;
+  const float* Bm;
+  Index ix;
+  if ((rc = tucker3_index(t, idx, n, &Bm, &ix))) return rc;
+  if (n == 0 || (!g_brows && !g_w)) return KGE_OK;
+  return run_tucker3_project_bwd(Bm, t->base_ld, ix, (const float*)t->proj, t->proj_ld, (int)t->dim, (int)t->base_dim, n,
+                                 g_out, g_ld, g_brows, g_brows_ld, g_w, g_w_ld, workspace, workspace_bytes,
+                                 (hipStream_t)stream);
 }
 
 int kge_build_queries(const kge_tables* t, int combine, kge_index s, kge_index p, kge_index o, int64_t n,

@@ -12,13 +12,14 @@ Function <-> reference map (paths relative to the reference tree):
   rank_counts                                      EntityRankingJob._filter_and_rank  kge/job/eval_entity_ranking.py:533-596
 """
 import ctypes
+import math
 import os
 
 import torch
 
 from . import _lib
 from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT_QUERY, I32, I64, PO_,
-                   RESCAL_MAX_DIM, SCORERS, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
+                   RESCAL_MAX_DIM, SCORERS, TUCKER3_MAX_BASE_DIM, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
 
 __all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "shared_samples",
            "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "neg_sample", "kvsall_collate", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
@@ -373,6 +374,80 @@ def rescal_queries(t: Tables, direction: str, a, p, out=None) -> torch.Tensor:
                                                  out.data_ptr(), out.stride(0) if n > 1 else d, _stream(t.device)),
                    "kge_rescal_queries")
     return out
+
+
+def _tucker3(B: torch.Tensor, W: torch.Tensor, what: str):
+    """(kge_tucker3 descriptor, d) of a base table B [R, d_r] and a projection weight W [d^2, d_r]."""
+    _require_gpu(B, what + ": the base table")
+    if W.device != B.device:
+        raise RuntimeError(f"kge_amd: {what}: base table on {B.device}, projection weight on {W.device}")
+    if B.dim() != 2 or W.dim() != 2 or B.shape[1] != W.shape[1] or B.stride(1) != 1 or W.stride(1) != 1:
+        raise ValueError(f"kge_amd: {what}: B is [R, d_r] and W is [d^2, d_r], both with unit inner stride")
+    d = int(round(math.sqrt(W.shape[0])))
+    if d * d != W.shape[0] or B.shape[0] < 1:
+        raise ValueError(f"kge_amd: {what}: the projection weight has d^2 rows (got {W.shape[0]})")
+    if B.dtype != W.dtype:
+        raise TypeError(f"kge_amd: {what}: B and W must have the same dtype")
+    dr = B.shape[1]
+    tc = _lib.KgeTucker3(B.data_ptr(), W.data_ptr(), _dtype_code(B), 0, B.shape[0], d, dr,
+                         B.stride(0) if B.shape[0] > 1 else dr, W.stride(0) if W.shape[0] > 1 else dr)
+    return tc, d
+
+
+def _tucker3_index(idx, R, device, keep):
+    """None = all R rows, a step-1 `range` = that run of base rows (kge_index.start: no index is read), else a vector."""
+    if idx is None:
+        idx = range(0, R)
+    if isinstance(idx, range):
+        if idx.step != 1 or idx.start < 0 or idx.stop > R or idx.stop < idx.start:
+            raise ValueError(f"kge_amd: a base-row range must be a step-1 range inside [0, {R}); got {idx}")
+        return KgeIndex(None, I64, idx.start, 1), len(idx)
+    ki = _index(idx, device, keep)
+    return ki, keep[-1].numel()
+
+
+def tucker3_project(B: torch.Tensor, W: torch.Tensor, idx=None, out=None) -> torch.Tensor:
+    """[n, d^2] projected mixing matrices (kge_tucker3_project): out[i] = B[idx_i] @ W^T, the rows of a RESCAL relation
+    table -- Tucker3RelationEmbedder.embed.  idx None: all rows of B; a `range`; or an int32 / int64 vector."""
+    tc, d = _tucker3(B, W, "tucker3_project")
+    keep = []
+    ki, n = _tucker3_index(idx, B.shape[0], B.device, keep)
+    if out is None:
+        out = _empty((n, d * d), B.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape != (n, d * d) or out.stride(1) != 1 or \
+            out.device != B.device:
+        raise ValueError("kge_amd: tucker3_project: out must be a float32 [n, d^2] tensor with unit inner stride")
+    with _on_device(B.device):
+        _lib.check(_lib.lib().kge_tucker3_project(ctypes.byref(tc), ki, n, out.data_ptr(),
+                                                  out.stride(0) if n > 1 else d * d, _stream(B.device)),
+                   "kge_tucker3_project")
+    return out
+
+
+def tucker3_project_bwd(B: torch.Tensor, W: torch.Tensor, idx, g_out: torch.Tensor, want_rows: bool = True,
+                        want_w: bool = True):
+    """(g_Brows [n, d_r] = g_out @ W, g_W [d^2, d_r] = g_out^T @ B[idx]) from g_out [n, d^2] (kge_tucker3_project_bwd);
+    an output not wanted is None.  Row i of g_Brows belongs to base row idx_i: the caller scatters it (index_add_)."""
+    tc, d = _tucker3(B, W, "tucker3_project_bwd")
+    keep = []
+    ki, n = _tucker3_index(idx, B.shape[0], B.device, keep)
+    if g_out.dtype != torch.float32 or g_out.dim() != 2 or g_out.shape != (n, d * d) or g_out.device != B.device:
+        raise ValueError("kge_amd: tucker3_project_bwd: g_out must be a float32 [n, d^2] tensor on the tables' device")
+    if g_out.stride(1) != 1 or (n > 1 and g_out.stride(0) < d * d):
+        g_out = g_out.contiguous()
+    dr = B.shape[1]
+    g_rows = _empty((n, dr), B.device) if want_rows else None
+    g_w = _empty((d * d, dr), B.device) if want_w else None
+    with _on_device(B.device):
+        L = _lib.lib()
+        need = L.kge_tucker3_project_bwd_workspace_bytes(ctypes.byref(tc), n)
+        ws = _empty((max(need, 16),), B.device, torch.uint8)
+        _lib.check(L.kge_tucker3_project_bwd(ctypes.byref(tc), ki, n, g_out.data_ptr(),
+                                             g_out.stride(0) if n > 1 else d * d,
+                                             g_rows.data_ptr() if want_rows else None, dr,
+                                             g_w.data_ptr() if want_w else None, dr, ws.data_ptr(), ws.numel(),
+                                             _stream(B.device)), "kge_tucker3_project_bwd")
+    return g_rows, g_w
 
 
 def score_pitch(m: int) -> int:

@@ -7,6 +7,7 @@ from kge.model.kge_model import KgeModel, RelationalScorer
 from kge.model.rescal import Rescal as _RefRescal
 from kge.model.rescal import RescalScorer as _RefRescalScorer
 from kge.model.rescal import rescal_set_relation_embedder_dim
+from kge.model.relational_tucker3 import RelationalTucker3 as _RefRelationalTucker3
 from kge.model.rotate import RotatE as _RefRotatE
 from kge.model.transe import TransE as _RefTransE
 from kge.model.transh import TransH as _RefTransH
@@ -16,8 +17,8 @@ from kge.model.transh import transh_set_relation_embedder_dim
 from .. import engine
 from ..model import (BF16Shadow, _FusedBCEDist, _FusedBCEF32, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32,
                      _FusedKLDist, _FusedKLF32, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
-                     bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable, predict_filters,
-                     topk_composed)
+                     Tucker3Routes, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable,
+                     predict_filters, topk_composed)
 
 
 class _HipScorer(RelationalScorer):
@@ -617,6 +618,130 @@ class HipRescal(_FusedScoring, _RefRescal):
         with torch.no_grad():
             scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
             return topk_composed(scores, k, filters, keep)
+
+
+class HipRelationalTucker3(Tucker3Routes, _FusedScoring, _RefRelationalTucker3):
+    """`model: hip_relational_tucker3`: kge/model/relational_tucker3.py -- RESCAL whose mixing matrices are projected
+    from a base relation table, M_p = (B[p] @ W^T).view(d, d) -- with the projection on kge_tucker3_project
+    (csrc/tucker3.hip) and everything behind it on the RESCAL kernels of hip_rescal over (entity table, projected rows).
+    The constructor repeats relational_tucker3.py:19-38 with the HIP scorer; the embedders are the reference's own
+    classes (checkpoints and `penalty` are the reference's).  With a recorded gradient the relation rows come by the
+    routes of kge_amd.model.Tucker3Routes ("all" when R <= n, else "batch"); without one the projected table is cached
+    until a parameter changes, unless it exceeds `projected_table_max_bytes` (then the batch's rows are projected).  Entry points without a RESCAL kernel are never taken, as for hip_rescal."""
+
+    def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
+        from kge.misc import round_to_points
+        self._init_configuration(config, configuration_key)
+        ent_emb_dim = self.get_option("entity_embedder.dim")
+        round_ent_emb_dim_to = self.get_option("entity_embedder.round_dim_to")
+        if len(round_ent_emb_dim_to) > 0:
+            ent_emb_dim = round_to_points(round_ent_emb_dim_to, ent_emb_dim)
+        config.set(self.configuration_key + ".entity_embedder.dim", ent_emb_dim, log=True)
+        rescal_set_relation_embedder_dim(config, dataset, self.configuration_key + ".relation_embedder")
+        _init(self, HipRescalScorer, config, dataset, self.configuration_key, init_for_load_only)
+        try:  # (hip_relational_tucker3.yaml; absent under a wrapper's key: the default)
+            self.projected_table_max_bytes = int(self.get_option("projected_table_max_bytes"))
+        except KeyError:
+            pass
+
+    def _bw(self):
+        pe = self.get_p_embedder()
+        return pe.base_embedder._embeddings.weight, pe.projection.weight
+
+    def _fused(self) -> bool:
+        from kge.model import LookupEmbedder, Tucker3RelationEmbedder
+        se, oe, pe = self.get_s_embedder(), self.get_o_embedder(), self.get_p_embedder()
+        if se is not oe or type(se) is not LookupEmbedder or type(pe) is not Tucker3RelationEmbedder or \
+                type(pe.base_embedder) is not LookupEmbedder:
+            return False
+        ent = se._embeddings.weight
+        B, W = self._bw()
+        if not ent.is_cuda or any(x.dtype != torch.float32 for x in (ent, B, W)):
+            return False
+        if ent.shape[1] > engine.RESCAL_MAX_DIM or B.shape[1] > engine.TUCKER3_MAX_BASE_DIM:
+            return False
+        if pe.base_embedder.normalize_p > 0:
+            return False
+        return not (self.training and (se.dropout.p > 0 or pe.base_embedder.dropout.p > 0 or pe.dropout > 0))
+
+    def _w(self):
+        """(entity table, projected relation table [R, d^2]): what the RESCAL paths of _FusedScoring take."""
+        return self.get_s_embedder()._embeddings.weight, self.projected_table()
+
+    def __setattr__(self, name, value):
+        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
+            raise ValueError("hip_relational_tucker3: {} is not supported (no RESCAL kernel behind the fused "
+                             "losses)".format(name.lstrip("_")))
+        super().__setattr__(name, value)
+
+    def set_touched_rows(self, pair):
+        if pair is not None:
+            raise ValueError("hip_relational_tucker3: touched_rows is not supported")
+        self._touched_rows = None
+
+    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
+        return None  # (no kge_score_neg_shared kernel: the job calls the sampler's own score)
+
+    def _rank_tables(self):
+        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
+
+    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
+        with torch.no_grad():
+            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
+            return topk_composed(scores, k, filters, keep)
+
+    def predict_o(self, s: Tensor, p: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        dev = self.get_s_embedder()._embeddings.weight.device
+        return self._predict("sp_", s, p, k, predict_filters(filter_index, "sp_", s, p, dev), keep)
+
+    def predict_s(self, p: Tensor, o: Tensor, k: int, filter_index=None, keep: Tensor = None):
+        dev = self.get_s_embedder()._embeddings.weight.device
+        return self._predict("_po", o, p, k, predict_filters(filter_index, "_po", o, p, dev), keep)
+
+    # -- with a recorded gradient: the routes (without one, _FusedScoring's calls on `_w()`: the cached table)
+    def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
+        if not self._fused():
+            return super().score_spo(s, p, o, direction)
+        rel, p2, rows = self._rel(p)
+        return _ScoreSPO.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, None)
+
+    def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor):
+        if not self._fused() or slot not in (0, 2):
+            return None
+        rel, p2, rows = self._rel(p)
+        return _ScoreNeg.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, int(slot), neg,
+                               None)
+
+    def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None):
+        if not self._fused():
+            return None
+        rel, p2, rows = self._rel(p)
+        return _ScoreNegBlocks.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, neg_s,
+                                     neg_o, None)
+
+    def _table_call(self, p: Tensor) -> bool:
+        """_FusedScoring's calls on `_w()` (the cached table, range targets, padded rows): no fused gather, or no gradient
+        recorded and the "all" route (the table within `projected_table_max_bytes`)"""
+        return not self._fused() or (not torch.is_grad_enabled() and self.route(p.numel()) == "all")
+
+    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
+        if self._table_call(p):
+            return super().score_sp(s, p, o)
+        rel, p2, rows = self._rel(p)
+        return _ScorePairs.apply("rescal", 1.0, "sp", self.get_s_embedder()._embeddings.weight, rel, s, p2, o, None,
+                                 self._padded(), rows)
+
+    def score_po(self, p: Tensor, o: Tensor, s: Tensor = None) -> Tensor:
+        if self._table_call(p):
+            return super().score_po(p, o, s)
+        rel, p2, rows = self._rel(p)
+        return _ScorePairs.apply("rescal", 1.0, "po", self.get_s_embedder()._embeddings.weight, rel, o, p2, s, None,
+                                 self._padded(), rows)
+
+    def score_sp_po(self, s: Tensor, p: Tensor, o: Tensor, entity_subset: Tensor = None) -> Tensor:
+        if self._table_call(p):
+            return super().score_sp_po(s, p, o, entity_subset)
+        return torch.cat((self.score_sp(s, p, entity_subset), self.score_po(p, o, entity_subset)), dim=1)
 
 
 class HipRotatE(_FusedScoring, _RefRotatE):

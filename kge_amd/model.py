@@ -223,10 +223,12 @@ class KgeModel(torch.nn.Module):
             relation_args.setdefault("initialize_args", {"a": -math.pi, "b": math.pi})
         self._entity_embedder = LookupEmbedder(num_entities, dim, dtype=dtype, device=device,
                                                **(entity_args or {}))
-        self._relation_embedder = LookupEmbedder(num_relations, rel_dim, dtype=dtype, device=device,
-                                                 **relation_args)
+        self._relation_embedder = self._make_relation_embedder(num_relations, rel_dim, dtype, device, relation_args)
         self._scorer = self.scorer_cls(l_norm)
         self._touched_rows = None  # set_touched_rows
+
+    def _make_relation_embedder(self, num_relations, rel_dim, dtype, device, relation_args):
+        return LookupEmbedder(num_relations, rel_dim, dtype=dtype, device=device, **relation_args)
 
     def set_touched_rows(self, pair):
         """`pair` = kge_amd.optim.Adagrad.enable_touched_rows(entity table) -> (grad, bitmap), or None to switch it off:
@@ -600,8 +602,199 @@ class Rescal(KgeModel):
     scorer_cls = RescalScorer
 
 
+class Tucker3RelationEmbedder(torch.nn.Module):
+    """kge/model/embedder/tucker3_relation_embedder.py (a ProjectionEmbedder, projection_embedder.py:6-46): a base
+    lookup table B [R, d_r] and `projection`, a bias-free Linear(d_r, d^2) with weight W [d^2, d_r]; the embedding of
+    relation p is the mixing matrix M_p = (B[p] @ W^T).view(d, d).  embed / embed_all are the torch path (dense
+    embeddings: dropout in training mode, CPU parameters); the index-level calls of RelationalTucker3 run
+    kge_tucker3_project."""
+
+    def __init__(self, vocab_size: int, dim: int, base_dim: int = 100, dropout: float = 0.0, base_args=None,
+                 dtype=torch.float32, device=None):
+        super().__init__()
+        self.vocab_size, self.dim = vocab_size, dim
+        self.base_embedder = LookupEmbedder(vocab_size, base_dim, dtype=dtype, device=device, **(base_args or {}))
+        self.projection = torch.nn.Linear(base_dim, dim, bias=False, device=device, dtype=dtype)
+        torch.nn.init.normal_(self.projection.weight.data)  # projection_embedder.yaml: initialize: normal_
+        self.dropout = torch.nn.Dropout(max(0.0, dropout))  # on the mixing matrices (tucker3_relation_embedder.yaml)
+
+    def _embed(self, base_rows: Tensor) -> Tensor:
+        out = torch.nn.functional.linear(base_rows, self.projection.weight)
+        return self.dropout(out) if self.dropout.p > 0 else out
+
+    def embed(self, indexes: Tensor) -> Tensor:
+        return self._embed(self.base_embedder.embed(indexes))
+
+    def embed_all(self) -> Tensor:
+        return self._embed(self.base_embedder.embed_all())
+
+    @property
+    def weight(self) -> Tensor:
+        """The projected table [R, d^2] on torch operations (what generic code reads as 'the relation table')."""
+        return torch.nn.functional.linear(self.base_embedder.weight, self.projection.weight)
+
+    def fused_ok(self) -> bool:
+        return self.base_embedder.fused_ok() and not (self.training and self.dropout.p > 0)
+
+
+class _Tucker3Project(torch.autograd.Function):
+    """[n, d^2] = B[idx] @ W^T from kge_tucker3_project; backward = kge_tucker3_project_bwd (the two float32 gradient
+    products, no float atomics) and the scatter of the row gradients into B's (index_add_; the identity for all rows)."""
+
+    @staticmethod
+    def forward(ctx, B, W, idx):
+        ctx.save_for_backward(B, W)
+        ctx.idx = idx
+        return engine.tucker3_project(B.detach(), W.detach(), idx)
+
+    @staticmethod
+    def backward(ctx, gout):
+        B, W = ctx.saved_tensors
+        g_rows, g_w = engine.tucker3_project_bwd(B.detach(), W.detach(), ctx.idx, gout, ctx.needs_input_grad[0],
+                                                 ctx.needs_input_grad[1])
+        g_b = g_rows
+        if g_rows is not None and ctx.idx is not None:
+            g_b = torch.zeros_like(B)
+            _scatter_rows(g_b, ctx.idx, g_rows)
+        return g_b, g_w, None
+
+
+def tucker3_project(B: Tensor, W: Tensor, idx=None) -> Tensor:
+    """The projected rows of a Tucker3 relation embedder: the HIP kernel for float32 parameters on a GPU; CPU
+    parameters take torch's linear (the reference's own operation).  Anything else on a GPU is an error."""
+    if B.is_cuda:
+        if B.dtype != torch.float32 or W.dtype != torch.float32:
+            raise ValueError("RelationalTucker3: the projection kernel takes float32 parameters (got {})".format(B.dtype))
+        return _Tucker3Project.apply(B, W, idx)
+    return torch.nn.functional.linear(B if idx is None else B[idx.reshape(-1).long()], W)
+
+
+class Tucker3Routes:
+    """How a Tucker3 model hands its relation rows to the RESCAL paths (mixed into RelationalTucker3 here and into the
+    plugin's HipRelationalTucker3, which says where B and W live: `_bw()`).  Two routes:
+      "all"    project rows 0 .. R and pass p through; when R <= n, and always without a recorded gradient (the
+               projected table is then cached until B or W changes) unless it exceeds projected_table_max_bytes;
+      "batch"  project the batch's rows and pass p' = arange(n)."""
+    project = "auto"
+    projected_table_max_bytes = 1 << 30
+    projections = 0  # projections of the whole table without a recorded gradient (the cache's misses)
+    _proj_key, _proj_table = None, None
+
+    def _bw(self):
+        raise NotImplementedError
+
+    def route(self, n: int, project: str = None) -> str:
+        mode = project or self.project
+        if mode not in ("auto", "all", "batch"):
+            raise ValueError("RelationalTucker3: project is 'auto', 'all' or 'batch' (got {!r})".format(mode))
+        if mode != "auto":
+            return mode
+        B, W = self._bw()
+        if not torch.is_grad_enabled():
+            table_bytes = B.shape[0] * W.shape[0] * B.element_size()
+            return "all" if table_bytes <= self.projected_table_max_bytes else "batch"
+        return "all" if B.shape[0] <= n else "batch"
+
+    def projected_table(self) -> Tensor:
+        """[R, d^2].  Without a recorded gradient: cached on the versions of B and W (the BF16Shadow pattern) -- an
+        evaluation projects once, not once per batch and chunk.  With one: projected anew, nothing is cached."""
+        B, W = self._bw()
+        if torch.is_grad_enabled():
+            return tucker3_project(B, W, None)
+        key = (B._version, W._version, B.data_ptr(), W.data_ptr(), B.device, B.dtype)
+        if key != self._proj_key:
+            self._proj_table, self._proj_key = tucker3_project(B, W, None), key
+            self.projections += 1
+        return self._proj_table
+
+    def _rel(self, p: Tensor, project: str = None):
+        """(relation table, relation index, rows) the RESCAL paths take for the batch's relations p; rows: the table
+        holds one row per query and the index is arange(n) (_ScorePairs' `rel_rows`)."""
+        n = p.numel()
+        if self.route(n, project) == "all":
+            return self.projected_table(), p, False
+        B, W = self._bw()
+        return tucker3_project(B, W, p.reshape(-1)), torch.arange(n, device=B.device), True
+
+
+class RelationalTucker3(Tucker3Routes, KgeModel):
+    """kge/model/relational_tucker3.py: RESCAL whose mixing matrices are projected from a base relation table,
+    M_p = (B[p] @ W^T).view(d, d) (Tucker3RelationEmbedder).  The projection is kge_tucker3_project; everything behind
+    it is the RESCAL kernels on the projected rows (the routes: Tucker3Routes).
+    `project` ("auto" | "all" | "batch", here or per call) forces a route."""
+    scorer_cls = RescalScorer
+
+    def __init__(self, num_entities: int, num_relations: int, dim: int, rel_base_dim: int = 100, project: str = "auto",
+                 projected_table_max_bytes: int = 1 << 30, **kw):
+        if project not in ("auto", "all", "batch"):
+            raise ValueError("RelationalTucker3: project is 'auto', 'all' or 'batch' (got {!r})".format(project))
+        if not 1 <= int(rel_base_dim) <= engine.TUCKER3_MAX_BASE_DIM:
+            raise ValueError("RelationalTucker3: rel_base_dim must be in [1, {}] (got {})".format(
+                engine.TUCKER3_MAX_BASE_DIM, rel_base_dim))
+        object.__setattr__(self, "_rel_base_dim", int(rel_base_dim))
+        super().__init__(num_entities, num_relations, dim, **kw)
+        self.project, self.projected_table_max_bytes = project, int(projected_table_max_bytes)
+
+    def _make_relation_embedder(self, num_relations, rel_dim, dtype, device, relation_args):
+        args = dict(relation_args)
+        return Tucker3RelationEmbedder(num_relations, rel_dim, self._rel_base_dim, dropout=args.pop("dropout", 0.0),
+                                       base_args=args, dtype=dtype, device=device)
+
+    def _bw(self):
+        return self._relation_embedder.base_embedder.weight, self._relation_embedder.projection.weight
+
+    def tables(self, flags: int = 0) -> engine.Tables:
+        return engine.Tables("rescal", self._entity_embedder.weight.detach(), self.projected_table().detach(), 1.0, flags)
+
+    # -- scoring: the RESCAL autograd nodes over (ent, projected rows)
+    def score_spo(self, s, p, o, direction=None, project=None):
+        if not self._fused():
+            return super().score_spo(s, p, o, direction)
+        rel, p2, rows = self._rel(p, project)
+        return _ScoreSPO.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, None)
+
+    def score_neg(self, s, p, o, slot, neg, project=None):
+        if not (self._fused() and slot in (0, 2)):
+            return super().score_neg(s, p, o, slot, neg)
+        rel, p2, rows = self._rel(p, project)
+        return _ScoreNeg.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, int(slot), neg, None)
+
+    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
+        raise ValueError("RelationalTucker3: shared negative samples (score_neg_shared) are not supported; use "
+                         "score_neg")
+
+    def score_neg_blocks(self, s, p, o, neg_s=None, neg_o=None, project=None):
+        ent = self._entity_embedder.weight
+        if self._fused() and ent.is_cuda and ent.dtype == torch.float32:
+            rel, p2, rows = self._rel(p, project)
+            return _ScoreNegBlocks.apply("rescal", 1.0, ent, rel, s, p2, o, neg_s, neg_o, None)
+        return super().score_neg_blocks(s, p, o, neg_s, neg_o)
+
+    def score_sp(self, s, p, o=None, project=None):
+        if not self._fused():
+            return super().score_sp(s, p, o)
+        rel, p2, rows = self._rel(p, project)
+        return _ScorePairs.apply("rescal", 1.0, "sp", self._entity_embedder.weight, rel, s, p2, o, None,
+                                 self.padded_scores and not torch.is_grad_enabled(), rows)
+
+    def score_po(self, p, o, s=None, project=None):
+        if not self._fused():
+            return super().score_po(p, o, s)
+        rel, p2, rows = self._rel(p, project)
+        return _ScorePairs.apply("rescal", 1.0, "po", self._entity_embedder.weight, rel, o, p2, s, None,
+                                 self.padded_scores and not torch.is_grad_enabled(), rows)
+
+    def score_sp_po(self, s, p, o, entity_subset=None, project=None):
+        if self._fused() and not torch.is_grad_enabled():
+            rel, p2, rows = self._rel(p, project)
+            return engine.score_sp_po(engine.Tables("rescal", self._entity_embedder.weight.detach(), rel, 1.0), s, p2, o,
+                                      entity_subset)
+        return torch.cat((self.score_sp(s, p, entity_subset, project=project),
+                          self.score_po(p, o, entity_subset, project=project)), dim=1)
+
+
 MODELS = {"complex": ComplEx, "distmult": DistMult, "transe": TransE, "rotate": RotatE, "transh": TransH,
-          "rescal": Rescal}
+          "rescal": Rescal, "relational_tucker3": RelationalTucker3}
 
 
 def create(model: str, num_entities: int, num_relations: int, dim: int, **kw) -> KgeModel:
@@ -904,7 +1097,10 @@ class BF16Shadow:
 
 class _ScorePairs(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, name, l_norm, direction, ent, rel, a, p, targets, fwd_tables=None, padded=False):
+    def forward(ctx, name, l_norm, direction, ent, rel, a, p, targets, fwd_tables=None, padded=False, rel_rows=False):
+        # rel_rows: `rel` holds one row per query and p is arange(n) (RelationalTucker3's "batch" route) -- the per-row
+        # relation gradient of the backward IS the gradient of `rel`
+        ctx.rel_rows = bool(rel_rows)
         t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
         tf = t if fwd_tables is None else fwd_tables  # mixed precision: bf16 copies, forward only
         # padded (the models' `padded_scores` option, honoured where no gradient is recorded): the scores as the [:, :m]
@@ -924,15 +1120,20 @@ class _ScorePairs(torch.autograd.Function):
         # tables, gout rounded to bf16, f32 accumulation) -- autocast semantics
         g_a, g_p, g_t = engine.score_pairs_bwd(ctx.tf if ctx.tf is not None else ctx.t, ctx.direction, a, p,
                                                targets, gout, scores)
-        gr = torch.zeros_like(ctx.t.rel)
-        _scatter_rows(gr, p, g_p)
+        if ctx.rel_rows:
+            if g_p.shape != ctx.t.rel.shape:
+                raise RuntimeError("kge_amd: rel_rows needs one relation row per query")
+            gr = g_p  # (no d^2-wide zero fill and index_add_)
+        else:
+            gr = torch.zeros_like(ctx.t.rel)
+            _scatter_rows(gr, p, g_p)
         if targets is None:
             ge = g_t  # [E, d], fresh: the dense target gradient IS the table gradient, plus the query rows
         else:
             ge = torch.zeros_like(ctx.t.ent)
             _scatter_rows(ge, targets, g_t)
         _scatter_rows(ge, a, g_a)
-        return None, None, None, ge, gr, None, None, None, None, None
+        return None, None, None, ge, gr, None, None, None, None, None, None
 
 
 class _FusedCE(torch.autograd.Function):
