@@ -1379,11 +1379,14 @@ int kge_score_neg_bwd_accum_sorted(const kge_tables* t, kge_index s, kge_index p
  * kge/job/train_negative_sampling.py:142-163): gradients of sum_{i,c} gout[i*ldg + c] * out[i, c] ACCUMULATED into
  * the dense table gradients like kge_score_neg_bwd_accum.  gout is folded over the repeat columns and the drop rule
  * into one weight per (positive, physical row); a positive's relation / fixed entity row gradients are summed in
- * registers over a tile of rows, a physical row's gradient over a tile of positives: one atomic row flush per
- * (owner, tile), none per occurrence.  `scores` = the forward output (row pitch lds; needed for TransE / RotatE with
- * l_norm != 1, may be NULL otherwise).  workspace: kge_score_neg_shared_workspace_bytes(t, n, num_unique) bytes of
- * device scratch, 16-byte aligned (too small: KGE_ERR_WORKSPACE).  f32 tables, dim <= 1024; anything else
- * KGE_ERR_UNSUPPORTED. */
+ * registers over a tile of 64 / NC physical rows, a physical row's gradient over a tile of 32 / NC positives (NC = 1,
+ * 2, 4, 8 coordinate pairs per lane for ceil(dim / 2) <= 64, 128, 256, 512): one atomic row flush per (owner, tile),
+ * none per occurrence.  `scores` = the forward output (row pitch lds; needed for TransE / RotatE with l_norm != 1 --
+ * NULL there: KGE_ERR_INVALID_ARG --, may be NULL otherwise).  workspace: kge_score_neg_shared_workspace_bytes(t, n,
+ * num_unique) bytes of device scratch, 16-byte aligned (sized for num_unique + 1 physical rows, with or without drop
+ * indexes; less than the call needs: KGE_ERR_WORKSPACE).  f32 tables, dim <= 1024 (odd dims included); bf16 tables and
+ * dim > 1024: KGE_ERR_UNSUPPORTED, gradients untouched.  n == 0 or num_unique + num_repeat == 0: KGE_OK, nothing is
+ * touched.  Rows of grad_ent / grad_rel that only weightless pairs reach get +0.f added. */
 int64_t kge_score_neg_shared_workspace_bytes(const kge_tables* t, int64_t n, int64_t num_unique);
 int kge_score_neg_shared_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
                                    const void* unique, int32_t unique_itype, int64_t num_unique, const int64_t* drop,

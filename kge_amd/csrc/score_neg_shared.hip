@@ -23,7 +23,9 @@
 //           registers over a tile of physical rows staged in LDS, one atomic flush per (positive, tile);
 //   ROLE 1  a wave owns a physical row: its gradient summed in registers over a tile of positives (their two rows
 //           staged in LDS), one atomic flush per (row, tile).
-// No atomic per (positive, sample) occurrence: ~n U / 64 + U n / 32 row flushes instead of n K.
+// Tiles are 64 / NC physical rows (ROLE 0) and 32 / NC positives (ROLE 1), NC = 1, 2, 4, 8 coordinate pairs per lane
+// for ceil(d / 2) <= 64, 128, 256, 512: the staged rows fill at most SNB_SM = 8192 floats.
+// No atomic per (positive, sample) occurrence: ~NC (n U / 64 + U n / 32) row flushes instead of n K.
 #include "bwd_device.hpp"
 #include "spo_device.hpp"
 

@@ -1,7 +1,10 @@
 """kge_score_neg_shared / kge_score_neg_shared_bwd_accum on the GPU: scores of shared negative samples (unique ids,
 drop indexes, repeat columns; kge/util/sampler.py:383-585) bit-identical to the C oracle's score_neg on the
 materialised samples, nothing written outside the [n, K] block, and the table gradients of kge_amd.model's
-score_neg_shared against torch autograd through the reference's op sequence on the expanded triples."""
+score_neg_shared against torch autograd through the reference's op sequence on the expanded triples (float32, one
+max-abs number per table, d in {33, 40, 200, 1024}: 1, 1, 2 and 8 coordinate pairs per lane of the backward kernel --
+NC = 4, d = 257 .. 512, is not among them).  The backward entry itself is held elementwise to a derived bound against
+float64 at every NC and at its tile and owner edges in tests/test_gpu_neg_shared_bwd.py."""
 import itertools
 
 import numpy as np
@@ -193,8 +196,9 @@ def test_gradients_match_torch_autograd(name, l_norm, d):
 @pytest.mark.parametrize("name,l_norm", SCORERS)
 @pytest.mark.parametrize("d", [200, 1024])
 def test_gradients_with_several_coordinate_pairs_per_lane(name, l_norm, d):
-    """d = 200 and d = 1024: two and eight coordinate pairs per lane in the backward kernel (its tiles are 64 / NC rows
-    and 32 / NC positives), past one tile of either with n = 19 positives and 70 (+ 1) rows."""
+    """d = 200 and d = 1024: two and eight coordinate pairs per lane in the backward kernel (NC; its tiles are 64 / NC
+    physical rows and 32 / NC positives: 32 and 16 at d = 200, 8 and 4 at d = 1024), past one tile of either with n = 19
+    positives and 70 (+ 1) rows."""
     _check_gradients(name, l_norm, d, n=19, uc=70, nrep=9)
 
 
