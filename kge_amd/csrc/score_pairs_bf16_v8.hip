@@ -38,6 +38,15 @@
 // so that both partial scores of a (row, target) sit in ONE lane (elements r and r + 4): score = hi + lo, one add,
 // eight stores per unit -- the bits of pairs_bf16_v6_kernel<SPLIT>.  Fragment buffers: the layout of
 // v4_build_queries (bf16_queries.hpp), unchanged.
+//
+// MS (split queries only): the shape of the matrix instruction.  0 = v_mfma_f32_32x32x16_bf16 as above.
+// 1 = v_mfma_f32_16x16x32_bf16: the wave's 32 operand rows x 32 targets are 2 x 2 tiles of 16 x 16 -- row tile 0 the
+// q_hi rows of the wave's 16 real rows, row tile 1 their q_lo rows, column tile c the targets 2 t + c (t = lane & 15) --
+// four chains of 16 steps of 32 K each; step j = the K-blocks 2 j, 2 j + 1 of the 32x32x16 chain, lane group g = lane >> 4
+// on the 16-byte slot 4 j + g of the table row: the same products in the same order, 8 at a time.  A lane then holds
+// both partial scores of two adjacent targets of four rows: four buffer_store_dwordx2 per unit, each four whole
+// 128-byte lines.  The chip holds a higher clock on this shape (same cycles per flop); everything around the chains --
+// work list, ring, barrier slot, counted waits, pieces -- is the 32x32x16 kernel's, one LDS read per 32-cycle slot.
 #include "common.hpp"
 #include "bf16_queries.hpp"
 #include <atomic>
@@ -71,8 +80,15 @@ struct V8Args {
   KGE_STALL(__LINE__ + 7000); \
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(D), "v"(VO), "s"(P) : "memory", "m0")
 
-template <int SCORER, int SPLIT, int AUX, int VAR = 0>
+// accumulators of a unit: MS = 1: [row tile: q_hi / q_lo][column tile]
+struct V8Acc16 {
+  f32x4 a[2][2];
+};
+
+template <int SCORER, int SPLIT, int AUX, int VAR = 0, int MS = 0>
 __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
+  static_assert(MS == 0 || (MS == 1 && SPLIT), "16x16x32 chains: split queries only");
+  constexpr bool M16 = MS != 0;
   constexpr int HH = 256;
   constexpr int NKB = 2 * HH / 16;        // 32 K-blocks of 16
   constexpr int ROWB = 4 * HH;            // 1 KiB per table row = one DMA piece
@@ -80,7 +96,7 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
   constexpr int NBUF = 4;
   constexpr int SMEM = NBUF * UNITB;      // 128 KiB
   constexpr int RW = SPLIT ? 16 : 32;     // real query rows per wave
-  constexpr int NST = SPLIT ? 8 : 16;     // stores per unit and wave, in slots 0, 2, ..
+  constexpr int NST = M16 ? 4 : SPLIT ? 8 : 16;  // stores per unit and wave, in slots 0, 2, ..
   // LDS reads in flight per wave.  Split queries: 4 -- the 16 registers eight cost were six spilled VGPRs in this
   // instantiation (scratch reloads, each behind a compiler-made s_waitcnt vmcnt(0), at every pair boundary of a kernel
   // whose table stream is ordered by counted waits); four slots of >= 32 cycles still cover the LDS latency, as in
@@ -93,9 +109,17 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
   // (steady state: 28 / 19 plain / split).  The chain behind the cold one waits for unit 2, requested in slots 1 - 13 of
   // the cold chain, behind which 9 / 1 stores + 6 fragment loads + 4 pieces + 7 stores = 26 / 18 operations follow: two
   // less than the steady count serves every chain (the two extra operations waited for are a unit old)
-  constexpr int VMN_STEADY = (NST > 15 ? 1 : 0) + NST + 4 + V8_PB / 2;
-  constexpr int VMN = VMN_STEADY - 2;
-  static_assert(VMN <= (NST > 15 ? 9 : 1) + (NKB - FR0 - 14) + 4 + V8_PB / 2, "the chain behind the cold chain");
+  // MS = 1: four stores, all in front of the barrier slot: 4 + 4 pieces + 4 = 12 in the steady state, and behind unit 2's
+  // last piece in the cold chain 6 fragment loads + 4 pieces + 4 stores = 14: the steady count serves every chain.
+  constexpr int NST_LO = NST < V8_PB / 2 ? NST : V8_PB / 2;  // stores in the slots in front of the barrier's
+  constexpr int VMN_STEADY = (NST > 15 ? 1 : 0) + NST + 4 + NST_LO;
+  constexpr int VMN = M16 ? VMN_STEADY : VMN_STEADY - 2;
+  static_assert(VMN == (M16 ? 12 : SPLIT ? 17 : 26), "counted wait of the unit barrier");
+  static_assert(VMN <= (NST - NST_LO) + (NKB - FR0 - 14) + 4 + NST_LO, "the chain behind the cold chain");
+  // the cold chain's own wait: unit 1 was requested right behind R0; since then the stores and the 14 fragment loads of
+  // the slots in front of the barrier's and unit 2's pieces of slots 1 - 13
+  constexpr int VMN_COLD = NST_LO + V8_PB + 4;
+  static_assert(VMN_COLD == (M16 ? 22 : 25), "counted wait of the cold chain");
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
   if (a.n < 0) smem[threadIdx.x] = 0;  // (never: keeps the allocation -- only asm names the array)
 
@@ -143,6 +167,14 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
 
   if (g1 > g0) {
     stamp();  // 0: start
+#ifdef KGE_V8_PROBES
+    // PROBE build only (tools/v8_clock_probe.py): shader-clock and 100 MHz real-time stamps around the workgroup's
+    // chains -> the clock the chip holds inside this kernel.  Slots 48 - 51 of the debug buffer: nothing reads them.
+    if (a.dbg != nullptr && tid == 0) {
+      a.dbg[(long long)blockIdx.x * 64 + 48] = __builtin_readcyclecounter();
+      a.dbg[(long long)blockIdx.x * 64 + 49] = wall_clock64();
+    }
+#endif
     // ---------------- the table stream: this wave's four rows of every unit ----------------
     const unsigned char* const tgb = (const unsigned char*)a.TG.base;
     const long long tld2 = a.TG.ld * 2;
@@ -182,8 +214,20 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
     bf16x8 afr[NKB];
     unsigned int bp[8];  // read addresses of the current ring buffer; moved on by one buffer per chain
     // target fragment kb of row fi: the 16-byte slot 2 kb + fh, stored at slot ^ (fi & 15)
+    // MS = 1: read e = 2 j + c is step j of column tile c: row 2 t + c, slot 4 j + g (t = lane & 15, g = lane >> 4).
+    // Banks: a ds_read_b128 is served in four groups of 16 lanes, each 8 lanes of g and 8 of g ^ 1 whose t are all
+    // different: the 16-byte bank slot ((4 j + g) ^ (2 t + c)) & 15 has the parity of g ^ c and is one-to-one in t
+    // within a g: sixteen different slots, conflict-free as before
+    const int mt = lane & 15, mg = lane >> 4;
 #pragma unroll
-    for (int t = 0; t < 8; ++t) bp[t] = (unsigned int)(fi * ROWB + (((2 * t + fh) ^ (fi & 15)) << 4));
+    for (int t = 0; t < 8; ++t) {
+      if constexpr (M16) {
+        const int row = 2 * mt + (t & 1);
+        bp[t] = (unsigned int)(row * ROWB + (((4 * (t >> 1) + mg) ^ (row & 15)) << 4));
+      } else {
+        bp[t] = (unsigned int)(fi * ROWB + (((2 * t + fh) ^ (fi & 15)) << 4));
+      }
+    }
     bf16x8 bq[PF];
     auto bread = [&](bf16x8& dst, auto kc) __attribute__((always_inline)) {
       constexpr int kb = decltype(kc)::value;
@@ -197,36 +241,75 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
     // The row part of a store's address travels in the per-lane offset (gfx9 bounds-checks the VGPR offset only): rows
     // >= n fall outside the descriptor and are dropped by the hardware, the unit's column goes in the scalar offset.
     const unsigned int ldo4 = (unsigned int)(a.ldo * 4);
-    const unsigned int svo = (unsigned int)(((long long)(4 * fh) * a.ldo + fi) * 4);
+    // MS = 1: acc.a[part][c][r] = partial score(real row 4 g + r, target 2 t + c): store r = the lane's two adjacent
+    // targets of row 4 g + r, 16 lanes x 8 bytes = one 128-byte line per row, four rows per instruction
+    using Acc = std::conditional_t<M16, V8Acc16, f32x16>;
+    const unsigned int svo =
+        M16 ? (unsigned int)(((long long)(4 * mg) * a.ldo + 2 * mt) * 4) : (unsigned int)(((long long)(4 * fh) * a.ldo + fi) * 4);
     __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, 0, 0x00020000);
-    auto store_q = [&](const f32x16& acc, auto qc, unsigned int vo, unsigned int colb) __attribute__((always_inline)) {
+    auto store_q = [&](const Acc& acc, auto qc, unsigned int vo, unsigned int colb) __attribute__((always_inline)) {
       constexpr int q = decltype(qc)::value;  // q-th store of the unit
-      constexpr int r = SPLIT ? (q & 3) + 8 * (q >> 2) : q;
-      constexpr int rowc = SPLIT ? 8 * (r >> 3) + (r & 3) : 8 * (r >> 2) + (r & 3);
-      const unsigned int vr = vo + (unsigned int)rowc * ldo4;
-      float v = acc[r];  // (a copy first: __builtin_bit_cast straight on the vector element stored element 0 every time)
-      if constexpr (SPLIT) {
-        const float lo = acc[r + 4];
-        v = v + lo;  // score = (sum q_hi t) + (sum q_lo t)
-      }
-      if constexpr (VAR & 1) {  // PROBE: the score computed, the store instruction left out
-        asm volatile("" : : "v"(v), "v"(vr));
+      if constexpr (M16) {
+        const unsigned int vr = vo + (unsigned int)q * ldo4;
+        const float h0 = acc.a[0][0][q], l0 = acc.a[1][0][q], h1 = acc.a[0][1][q], l1 = acc.a[1][1][q];
+        float v0 = h0 + l0, v1 = h1 + l1;  // score = (sum q_hi t) + (sum q_lo t)
+        asm("" : "+v"(v0));  // (two v_add_f32, not a v_pk_add_f32 with its register pairing and copies)
+        if constexpr (VAR & 1) {
+          asm volatile("" : : "v"(v0), "v"(v1), "v"(vr));
+        } else {
+          const u32x2 v = {__builtin_bit_cast(unsigned int, v0), __builtin_bit_cast(unsigned int, v1)};
+          __builtin_amdgcn_raw_buffer_store_b64(v, srs, vr, colb, AUX);
+        }
       } else {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), srs, vr, colb, AUX);
+        constexpr int r = SPLIT ? (q & 3) + 8 * (q >> 2) : q;
+        constexpr int rowc = SPLIT ? 8 * (r >> 3) + (r & 3) : 8 * (r >> 2) + (r & 3);
+        const unsigned int vr = vo + (unsigned int)rowc * ldo4;
+        float v = acc[r];  // (a copy first: __builtin_bit_cast straight on the vector element stored element 0 every time)
+        if constexpr (SPLIT) {
+          const float lo = acc[r + 4];
+          v = v + lo;  // score = (sum q_hi t) + (sum q_lo t)
+        }
+        if constexpr (VAR & 1) {  // PROBE: the score computed, the store instruction left out
+          asm volatile("" : : "v"(v), "v"(vr));
+        } else {
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), srs, vr, colb, AUX);
+        }
       }
     };
     // per-lane offset of the unit at slice position `cu`: out of range for the columns >= m of the ragged last unit
+    // (MS = 1: for the lane's PAIR of columns unless both are < m; m odd leaves one lane with a single column: `lone`)
     auto unit_vo = [&](int cu, unsigned int& colb) __attribute__((always_inline)) -> unsigned int {
       const long long col0 = (long long)(u_lo + cu) * V8_UT;
       colb = (unsigned int)(col0 * 4);
+      if constexpr (M16) return (col0 + V8_UT <= m || col0 + 2 * mt + 1 < m) ? svo : V8_DROP;
       return (col0 + V8_UT <= m || col0 + fi < m) ? svo : V8_DROP;
     };
+    // The flush of a pair's last unit.  MS = 1: the table's ragged last unit is the last unit of its slice, so only a
+    // flush ever stores it -- the lane whose first column is the table's last one (m odd) stores it alone here, behind
+    // the pair stores (more vector-memory operations than the counted waits assume: they wait longer, never shorter)
+    auto flush_unit = [&](const Acc& acc, int cuu, unsigned int vo, unsigned int colb) __attribute__((always_inline)) {
+      v4_static_for<0, NST>([&](auto qc) __attribute__((always_inline)) { store_q(acc, qc, vo, colb); });
+      if constexpr (M16 && !(VAR & 1)) {
+        const long long col0 = (long long)(u_lo + cuu) * V8_UT;
+        if (col0 + V8_UT > m && (m & 1)) {
+          const unsigned int lvo = (col0 + 2 * mt + 1 == m) ? svo : V8_DROP;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float h0 = acc.a[0][0][q], l0 = acc.a[1][0][q];
+            const float v0 = h0 + l0;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v0), srs, lvo + (unsigned int)q * ldo4, colb, AUX);
+          }
+        }
+      }
+    };
 
-    f32x16 acc0, acc1;
+    Acc acc0, acc1;
     // chain of the unit in ring buffer ks & 3 into `acc`; `prev` (offset vo, column colb) is stored on the way.
     // `cold` (the workgroup's very first chain): the ring holds units 0 and 1 only and the fragments K-blocks < FR0 --
     // unit 2 is requested in slots 1, 5, 9, 13, K-block FR0 + j in slot j (FR0 slots ahead of its MFMA); `frag` loads it
-    auto chain = [&](int ks, f32x16& acc, const f32x16& prev, unsigned int vo, unsigned int colb, auto cold, auto&& frag)
+    // MS = 1: slot kb = step kb >> 1 of column tile kb & 1: ONE LDS read as before, two 16-cycle matrix instructions (the
+    // q_hi and the q_lo row tile on the same targets; an accumulator is next touched four instructions later)
+    auto chain = [&](int ks, Acc& acc, const Acc& prev, unsigned int vo, unsigned int colb, auto cold, auto&& frag)
         __attribute__((always_inline)) {
       constexpr bool COLD = decltype(cold)::value;
       // the next ring buffer: + one unit, or back to the first one (unsigned wrap-around)
@@ -236,13 +319,22 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
         constexpr int kb = decltype(kc)::value;
         asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(PF - 1) : "memory");
         if constexpr (kb == V8_PB) {
-          // this wave's pieces of unit ks + 1 have landed (cold: requested right behind R0; since then 7 stores, 14
-          // fragment loads and unit 2's pieces of slots 1 - 13)
-          asm volatile("s_waitcnt vmcnt(%0)" ::"i"(COLD ? 25 : VMN) : "memory");
+          // this wave's pieces of unit ks + 1 have landed (cold: VMN_COLD)
+          asm volatile("s_waitcnt vmcnt(%0)" ::"i"(COLD ? VMN_COLD : VMN) : "memory");
           KGE_BARRIER();  // P(ks)
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (kb == 0) {
+        if constexpr (M16) {
+          constexpr int sj = kb >> 1, sc = kb & 1;
+          if constexpr (sj == 0) {
+            const f32x4 zero = {0, 0, 0, 0};
+            acc.a[0][sc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[0], bq[kb % PF], zero, 0, 0, 0);
+            acc.a[1][sc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[1], bq[kb % PF], zero, 0, 0, 0);
+          } else {
+            acc.a[0][sc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[2 * sj], bq[kb % PF], acc.a[0][sc], 0, 0, 0);
+            acc.a[1][sc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[2 * sj + 1], bq[kb % PF], acc.a[1][sc], 0, 0, 0);
+          }
+        } else if constexpr (kb == 0) {
           const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bq[0], zero, 0, 0, 0);
         } else {
@@ -293,7 +385,14 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
       unsigned int flo;
       const unsigned char* fb;
       int frange;
-      if constexpr (SPLIT) {
+      if constexpr (M16) {
+        // entry e of afr = step e >> 1 of row tile e & 1 (q_hi / q_lo): real row rr = 16 (w & 3) + t of the group's 64,
+        // lane group g = K elements 8 g .. 8 g + 7 of the step = K-block 2 (e >> 1) + (g >> 1), half g & 1
+        const int rr = 16 * (wave & 3) + mt;
+        flo = (unsigned int)(((((rr >> 5) * NKB) + (mg >> 1)) * 64 + (rr & 31) + 32 * (mg & 1)) * 16);
+        fb = gbase;
+        frange = 4 * NKB * 1024;
+      } else if constexpr (SPLIT) {
         // operand row fi = 16 a + 8 part + jj of wave w: real row 16 (w & 3) + 8 a + jj of the group's 64, whose q_hi
         // sits in block (row >> 5), its q_lo in block 2 + (row >> 5)
         const int part = (fi >> 3) & 1, rr = 16 * (wave & 3) + 8 * (fi >> 4) + (fi & 7);
@@ -309,7 +408,8 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
       auto load_fragments = [&](auto lo, auto hi) __attribute__((always_inline)) {
         v4_static_for<decltype(lo)::value, decltype(hi)::value>([&](auto kc) __attribute__((always_inline)) {
           constexpr int kb = decltype(kc)::value;
-          afr[kb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(frs, flo + kb * 1024, 0, 16 /* sc1 */));
+          constexpr int fo = M16 ? (kb & 1) * (2 * NKB * 1024) + (kb >> 1) * 2048 : kb * 1024;
+          afr[kb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(frs, flo + fo, 0, 16 /* sc1 */));
         });
       };
       using C0 = std::integral_constant<int, 0>;
@@ -350,9 +450,9 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
         chain(ks, acc1, acc0, pvo, pcolb, Warm{}, nofrag);
         pvo = unit_vo(cu + i, pcolb);
         ++ks;
-        v4_static_for<0, NST>([&](auto qc) __attribute__((always_inline)) { store_q(acc1, qc, pvo, pcolb); });
+        flush_unit(acc1, cu + i, pvo, pcolb);
       } else {
-        v4_static_for<0, NST>([&](auto qc) __attribute__((always_inline)) { store_q(acc0, qc, pvo, pcolb); });
+        flush_unit(acc0, cu + cnt - 1, pvo, pcolb);
       }
       g += cnt;
       pair += pstep;
@@ -366,6 +466,12 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
     else
       asm volatile("" : : "v"(bq[0]), "v"(bq[1]), "v"(bq[2]), "v"(bq[3]));
     stamp_at(34);  // last store issued
+#ifdef KGE_V8_PROBES
+    if (a.dbg != nullptr && tid == 0) {
+      a.dbg[(long long)blockIdx.x * 64 + 50] = __builtin_readcyclecounter();
+      a.dbg[(long long)blockIdx.x * 64 + 51] = wall_clock64();
+    }
+#endif
   }
   // the NEXT group's query fragments: a slice per workgroup, behind its last unit
   if (a.nx.qf != nullptr)
@@ -411,19 +517,36 @@ static int launch_v8(V8Args& a, int sc1, hipStream_t st) {
   // batches -- the stores cost 13 %, the rest of the distance to the bare matrix pipe is not theirs)
   if constexpr (SCORER == KGE_COMPLEX && SPLIT == 1) {
     if (sw(SW_V8_VAR) == 1) {
-      hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, 2, 1>), grid, block, 0, st, a);
+      if (sw(SW_V8_MFMA32) == 1)
+        hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, 2, 1>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, 2, 1, 1>), grid, block, 0, st, a);
       return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
     }
   }
 #endif
+  // split queries: the chains on v_mfma_f32_16x16x32_bf16; V8_MFMA32 = 1 keeps the 32x32x16 instantiation
+  // (the same bits: tests/test_gpu_v8_mfma_shape.py)
+  const int ms = SPLIT && sw(SW_V8_MFMA32) != 1 ? 1 : 0;
+#define KGE_V8_GO(AUXV)                                                                               \
+  do {                                                                                                \
+    if constexpr (SPLIT) {                                                                            \
+      if (ms == 1) {                                                                                  \
+        hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, AUXV, 0, 1>), grid, block, 0, st, a); \
+        break;                                                                                        \
+      }                                                                                               \
+    }                                                                                                 \
+    hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, AUXV>), grid, block, 0, st, a);           \
+  } while (0)
   if (sc1 == 1)
-    hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, 16>), grid, block, 0, st, a);
+    KGE_V8_GO(16);
   else if (sc1 == 2)
-    hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, 2>), grid, block, 0, st, a);
+    KGE_V8_GO(2);
   else if (sc1 == 3)
-    hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, 18>), grid, block, 0, st, a);
+    KGE_V8_GO(18);
   else
-    hipLaunchKernelGGL((pairs_bf16_v8_kernel<SCORER, SPLIT, 0>), grid, block, 0, st, a);
+    KGE_V8_GO(0);
+#undef KGE_V8_GO
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 
