@@ -244,6 +244,77 @@ int kge_tucker3_project_bwd(const kge_tucker3* t, kge_index idx, int64_t n, cons
                             float* g_brows, int64_t g_brows_ld, float* g_w, int64_t g_w_ld, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/* ---- ConvE (kge/model/conve.py:9-101; csrc/conve.hip, csrc/conve_device.hpp) -------------------------------------------
+ * ConvE puts a small network between the (s, p) rows and the contraction with the entity table (conve.py:75-93).  In
+ * eval mode that network is a fixed function of two rows; kge_conve_queries runs it and writes AUGMENTED query rows
+ *   q' = [1.0f | x],   d + 1 floats,   x = the network's output for (s, p),   d = h * w,
+ * so that score(s, p, o) = q' . ent[o] over the WHOLE entity row of d + 1 floats: the 1.0f meets the bias column (column 0
+ * of an entity row).  There is no ConvE scorer and nothing ConvE in kge_tables: the contraction is the float32 DistMult
+ * arithmetic through kge_score_emb(KGE_DISTMULT, KGE_SP_ / KGE_SPO, q', rows of ones, entity rows) and its backward
+ * kge_score_emb_bwd.  The reference adds the bias AFTER the product (conve.py:99); the augmented form is the same real
+ * number with a different rounding, inside the float64 bound of the score -- not bit-equal to the reference's order.
+ * Eval-mode semantics only (running statistics, no dropout), in this order; Ho = 2 h - fs + 2 pad + 1,
+ * Wo = w - fs + 2 pad + 1, F = 32 * Ho * Wo:
+ *   1 gather    ent[s][1:] and rel[p][1:] as two h x w images stacked to 2 h x w, the subject on top (conve.py:82-84)
+ *   2 conv      32 channels, fs x fs, stride 1, zero padding: ONE fma chain per output, taps in ascending (ky, kx),
+ *               from conv_b[c] or +0; a tap in the padding enters no fma                       (conve.py:85)
+ *   3 bn1       (v - bn1_mean[c]) * rsq,  rsq = 1 / sqrt(bn1_var[c] + bn1_eps): one add, one correctly rounded sqrt,
+ *               one correctly rounded division; no affine                                      (conve.py:86)
+ *   4 ReLU      v > 0 ? v : +0                                                                 (conve.py:87)
+ *   5 flatten   channel-major: feature c * Ho * Wo + y * Wo + x                                (conve.py:89)
+ *   6 proj      x_j = sum_k feature_k proj_w[j][k] + proj_b[j].  Summation order: 32 channel partials P_c, each one fma
+ *               chain from +0 over the channel's positions k = y * Wo + x in groups of eight -- within group g the order
+ *               is 8g, 8g+4, 8g+1, 8g+5, 8g+2, 8g+6, 8g+3, 8g+7 (the chain of v_mfma_f32_32x32x2_f32; positions past
+ *               Ho * Wo in the last group are zeros on both sides) -- then (((P_0 + P_1) + P_2) + ... + P_31) + proj_b[j]
+ *               by plain additions in a fixed order; no float atomics: two runs give the same bits   (conve.py:90)
+ *   7 bn2       as 3 with bn2_mean[j], bn2_var[j], bn2_eps                                     (conve.py:92)
+ *   8 ReLU                                                                                     (conve.py:93)
+ *   9 write     q[i][1 + j] = the result, q[i][0] = 1.0f; nothing else of q is touched (q_ld > d + 1: a pitched q)
+ * A query row is a pure function of its two table rows and the network: the same bits whatever n, the row's position in
+ * the call, the index type or stride, the pitches, 16-byte alignment and the launch geometry.
+ * Gate, before any launch (kge_conve_workspace_bytes returns 0):
+ *   KGE_ERR_INVALID_ARG   NULL net or pointers (conv_b only with has_conv_bias), h, w < 1, padding < 0, proj_ld < F,
+ *                         ent_ld / rel_ld / q_ld < d + 1, n < 0, NULL q or tables with n > 0, a malformed index
+ *   KGE_ERR_UNSUPPORTED   filter_size outside 1..5, padding > 2 (stride is 1 by construction), Ho < 1, Wo < 1,
+ *                         h * w > KGE_CONVE_MAX_DIM, or a channel slice that does not fit the LDS plan: the kernel holds
+ *                         32 rows x (Ho * Wo rounded up to a multiple of 8, + 1) floats, and that row length must be at
+ *                         most KGE_CONVE_MAX_SLICE floats (128 KiB)
+ *   KGE_ERR_WORKSPACE     workspace NULL or below kge_conve_workspace_bytes(net, n) = 32 * n * d floats (the channel
+ *                         partials; no zeroing needed, every float of it is written before it is read)
+ * n == 0: KGE_OK, nothing is launched.  Every KGE_ERR_INVALID_ARG condition, the call's own arguments included, is
+ * reported in front of KGE_ERR_UNSUPPORTED.  A slice above 48 KiB asks the runtime for its LDS once per device; a
+ * runtime that refuses what the gate allows is KGE_ERR_LAUNCH. */
+#define KGE_CONVE_MAX_DIM 1024
+#define KGE_CONVE_MAX_SLICE 1024
+
+typedef struct kge_conve_net {
+  int32_t h;                  /* image height and width of one embedding: d = h * w (conve.py:17-42)  */
+  int32_t w;
+  int32_t filter_size;        /* fs                                                                   */
+  int32_t padding;            /* pad                                                                  */
+  int32_t has_conv_bias;      /* 0: conv_b is not read and may be NULL                                */
+  int32_t reserved_;          /* 0                                                                    */
+  const float* conv_w;        /* convolution.weight [32, 1, fs, fs], contiguous                       */
+  const float* conv_b;        /* convolution.bias [32] or NULL                                        */
+  const float* bn1_mean;      /* bn1.running_mean [32]                                                */
+  const float* bn1_var;       /* bn1.running_var [32]                                                 */
+  const float* proj_w;        /* projection.weight [d, F], row-major, pitch proj_ld                   */
+  int64_t proj_ld;
+  const float* proj_b;        /* projection.bias [d]                                                  */
+  const float* bn2_mean;      /* bn2.running_mean [d]                                                 */
+  const float* bn2_var;       /* bn2.running_var [d]                                                  */
+  float bn1_eps;
+  float bn2_eps;
+} kge_conve_net;
+
+/* q[i * q_ld + :] = [1.0f | network(ent[s_i], rel[p_i])], i < n, q_ld >= d + 1 ("ConvE" above: conve.py:75-93).
+ * ent / rel: float32 tables whose rows hold d + 1 floats (column 0 of an entity row is its bias; column 0 of a relation
+ * row is never read), pitches ent_ld / rel_ld in floats. */
+int64_t kge_conve_workspace_bytes(const kge_conve_net* net, int64_t n);
+int kge_conve_queries(const kge_conve_net* net, const float* ent, int64_t ent_ld, const float* rel, int64_t rel_ld,
+                      kge_index s, kge_index p, int64_t n, float* q, int64_t q_ld, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* ---- library ---------------------------------------------------------- */
 int kge_abi_version(void);
 const char* kge_status_string(int status);

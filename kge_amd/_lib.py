@@ -120,6 +120,18 @@ class KgeTucker3(ctypes.Structure):
                 ("num_rel", c_i64), ("dim", c_i64), ("base_dim", c_i64), ("base_ld", c_i64), ("proj_ld", c_i64)]
 
 
+CONVE_MAX_DIM = 1024  # KGE_CONVE_MAX_DIM
+CONVE_MAX_SLICE = 1024  # KGE_CONVE_MAX_SLICE
+
+
+class KgeConveNet(ctypes.Structure):
+    _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("filter_size", ctypes.c_int32),
+                ("padding", ctypes.c_int32), ("has_conv_bias", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+                ("conv_w", c_vp), ("conv_b", c_vp), ("bn1_mean", c_vp), ("bn1_var", c_vp), ("proj_w", c_vp),
+                ("proj_ld", c_i64), ("proj_b", c_vp), ("bn2_mean", c_vp), ("bn2_var", c_vp),
+                ("bn1_eps", ctypes.c_float), ("bn2_eps", ctypes.c_float)]
+
+
 # every symbol include/kge_amd.h declares: name -> (restype, argtypes)
 _PT = ctypes.POINTER(KgeTables)
 PROTOTYPES = {
@@ -138,6 +150,9 @@ PROTOTYPES = {
     "kge_tucker3_project_bwd_workspace_bytes": (c_i64, [ctypes.POINTER(KgeTucker3), c_i64]),
     "kge_tucker3_project_bwd": (ctypes.c_int, [ctypes.POINTER(KgeTucker3), KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64,
                                                c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kge_conve_workspace_bytes": (c_i64, [ctypes.POINTER(KgeConveNet), c_i64]),
+    "kge_conve_queries": (ctypes.c_int, [ctypes.POINTER(KgeConveNet), c_vp, c_i64, c_vp, c_i64, KgeIndex, KgeIndex, c_i64,
+                                         c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_queries_bytes": (c_i64, [_PT, ctypes.c_int, c_i64]),
     "kge_build_queries": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
     "kge_score_queries": (ctypes.c_int, [_PT, ctypes.c_int, c_vp, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_i64,

@@ -14,6 +14,11 @@ long long tucker3_bwd_workspace_bytes(int d, int dr, long long n);
 int run_tucker3_project_bwd(const float* Bm, long long ldb, const Index& idx, const float* W, long long ldw, int d, int dr,
                             long long n, const float* gout, long long ldg, float* g_brows, long long g_brows_ld,
                             float* g_w, long long g_w_ld, void* ws, long long ws_bytes, hipStream_t st);
+// conve.hip
+bool conve_lds_ok(long long hw);
+long long conve_workspace_bytes(int d, long long n);
+int run_conve_queries(const kge_conve_net* cn, const float* ent, long long ent_ld, const float* rel, long long rel_ld,
+                      const Index& s, const Index& p, long long n, float* q, long long q_ld, float* ws, hipStream_t st);
 // rescal.hip
 int run_rescal_queries(const Operand& A, const Operand* A2, const Operand& R, int dir, int d, long long n, float* q,
                        float* q2, long long q_ld, float* ones, hipStream_t st);
@@ -772,6 +777,60 @@ int kge_tucker3_project_bwd(const kge_tucker3* t, kge_index idx, int64_t n, cons
   return run_tucker3_project_bwd(Bm, t->base_ld, ix, (const float*)t->proj, t->proj_ld, (int)t->dim, (int)t->base_dim, n,
                                  g_out, g_ld, g_brows, g_brows_ld, g_w, g_w_ld, workspace, workspace_bytes,
                                  (hipStream_t)stream);
+}
+
+// ---- ConvE (conve.hip): the gate of the two entries ("ConvE" in include/kge_amd.h states the rule) ----------------------
+// ONE pass: every KGE_ERR_INVALID_ARG condition is looked at before any KGE_ERR_UNSUPPORTED one
+static int check_conve(const kge_conve_net* c, bool need_ptrs) {
+  if (!c) return KGE_ERR_INVALID_ARG;
+  if (c->h < 1 || c->w < 1 || c->padding < 0) return KGE_ERR_INVALID_ARG;
+  if (need_ptrs && (!c->conv_w || !c->bn1_mean || !c->bn1_var || !c->proj_w || !c->proj_b || !c->bn2_mean ||
+                    !c->bn2_var || (c->has_conv_bias && !c->conv_b)))
+    return KGE_ERR_INVALID_ARG;
+  const int64_t Ho = 2 * (int64_t)c->h - c->filter_size + 2 * (int64_t)c->padding + 1;
+  const int64_t Wo = (int64_t)c->w - c->filter_size + 2 * (int64_t)c->padding + 1;
+  if (Ho >= 1 && Wo >= 1 && c->proj_ld < 32 * Ho * Wo) return KGE_ERR_INVALID_ARG;  // (a pitch below the width F)
+  if (c->filter_size < 1 || c->filter_size > 5 || c->padding > 2) return KGE_ERR_UNSUPPORTED;
+  if ((int64_t)c->h * c->w > KGE_CONVE_MAX_DIM) return KGE_ERR_UNSUPPORTED;
+  if (Ho < 1 || Wo < 1 || !conve_lds_ok(Ho * Wo)) return KGE_ERR_UNSUPPORTED;
+  return KGE_OK;
+}
+
+int64_t kge_conve_workspace_bytes(const kge_conve_net* net, int64_t n) {
+  if (n <= 0 || check_conve(net, false) != KGE_OK) return 0;
+  return conve_workspace_bytes(net->h * net->w, n);
+}
+
+// ptr == NULL: rows start .. start + n - 1 of the table (`*base` moves there, the kernel reads no index)
+static int conve_index(const kge_index& ix, const float** base, int64_t ld, Index* out) {
+  if (!ix.ptr) {
+    if (ix.start < 0) return KGE_ERR_INVALID_ARG;
+    *base += (int64_t)ix.start * ld;
+    *out = Index{nullptr, 1, KGE_I64};
+    return KGE_OK;
+  }
+  if (ix.start != 0 || (ix.itype != KGE_I32 && ix.itype != KGE_I64) || ix.stride < 1) return KGE_ERR_INVALID_ARG;
+  *out = make_index(ix);
+  return KGE_OK;
+}
+
+int kge_conve_queries(const kge_conve_net* net, const float* ent, int64_t ent_ld, const float* rel, int64_t rel_ld,
+                      kge_index s, kge_index p, int64_t n, float* q, int64_t q_ld, void* workspace,
+                      int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  const int gate = check_conve(net, true);
+  if (gate == KGE_ERR_INVALID_ARG) return gate;
+  // the call's own arguments: also KGE_ERR_INVALID_ARG, in front of an unsupported shape
+  const int64_t d = (int64_t)net->h * net->w;
+  if (n < 0 || (n > 0 && (!q || !ent || !rel)) || ent_ld < d + 1 || rel_ld < d + 1 || q_ld < d + 1)
+    return KGE_ERR_INVALID_ARG;
+  Index si, pi;
+  int rc;
+  if ((rc = conve_index(s, &ent, ent_ld, &si)) || (rc = conve_index(p, &rel, rel_ld, &pi))) return rc;
+  if (gate) return gate;
+  if (n == 0) return KGE_OK;
+  if (!workspace || workspace_bytes < conve_workspace_bytes((int)d, n)) return KGE_ERR_WORKSPACE;
+  return run_conve_queries(net, ent, ent_ld, rel, rel_ld, si, pi, n, q, q_ld, (float*)workspace, (hipStream_t)stream);
 }
 
 int kge_build_queries(const kge_tables* t, int combine, kge_index s, kge_index p, kge_index o, int64_t n,

@@ -376,6 +376,88 @@ def rescal_queries(t: Tables, direction: str, a, p, out=None) -> torch.Tensor:
     return out
 
 
+class ConveNet:
+    """The float32 tensors of ConvE's network (kge/model/conve.py:53-72) as kge_conve_queries reads them: convolution
+    weight [32, 1, fs, fs] and bias [32] or None, the running statistics of bn1 [32] and bn2 [d], projection weight
+    [d, F] and bias [d]; h x w is the image of one embedding (d = h * w)."""
+
+    def __init__(self, h: int, w: int, filter_size: int, padding: int, conv_w, conv_b, bn1_mean, bn1_var, bn1_eps: float,
+                 proj_w, proj_b, bn2_mean, bn2_var, bn2_eps: float):
+        self.h, self.w, self.filter_size, self.padding = int(h), int(w), int(filter_size), int(padding)
+        self.conv_w, self.conv_b, self.bn1_mean, self.bn1_var = conv_w, conv_b, bn1_mean, bn1_var
+        self.proj_w, self.proj_b, self.bn2_mean, self.bn2_var = proj_w, proj_b, bn2_mean, bn2_var
+        self.bn1_eps, self.bn2_eps = float(bn1_eps), float(bn2_eps)
+
+    @property
+    def dim(self) -> int:
+        return self.h * self.w
+
+    @property
+    def features(self) -> int:
+        return 32 * (2 * self.h - self.filter_size + 2 * self.padding + 1) * \
+            (self.w - self.filter_size + 2 * self.padding + 1)
+
+
+def conve_gate(h: int, w: int, filter_size: int, padding: int) -> bool:
+    """Does kge_conve_queries take this shape (the gate of include/kge_amd.h, asked of the library itself)."""
+    Ho, Wo = 2 * h - filter_size + 2 * padding + 1, w - filter_size + 2 * padding + 1
+    c = _lib.KgeConveNet(h=h, w=w, filter_size=filter_size, padding=padding, proj_ld=max(32 * Ho * Wo, 1))
+    return _lib.lib().kge_conve_workspace_bytes(ctypes.byref(c), 1) > 0
+
+
+def conve_queries(net: ConveNet, ent: torch.Tensor, rel: torch.Tensor, s, p, out=None) -> torch.Tensor:
+    """[n, d + 1] augmented ConvE queries q' = [1 | network(ent[s], rel[p])] (kge_conve_queries; eval-mode semantics):
+    score(s, p, o) = q' . ent[o].  ent / rel: float32 tables of d + 1 columns.  out: a float32 [n, >= d + 1] tensor with
+    unit inner stride whose first d + 1 columns are written (a zero-padded pitch stays zero)."""
+    _require_gpu(ent, "entity table")
+    _require_gpu(rel, "relation table")
+    d = net.dim
+    names = ("conv_w", "bn1_mean", "bn1_var", "proj_w", "proj_b", "bn2_mean", "bn2_var") + \
+        (("conv_b",) if net.conv_b is not None else ())
+    for name in names:
+        x = getattr(net, name)
+        if x.device != ent.device or x.dtype != torch.float32:
+            raise ValueError(f"kge_amd: conve_queries: {name} must be a float32 tensor on {ent.device}")
+    for x, what in ((ent, "entity"), (rel, "relation")):
+        if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] != d + 1 or x.device != ent.device:
+            raise ValueError(f"kge_amd: conve_queries: the {what} table must be float32 [rows, d + 1] with unit inner "
+                             "stride")
+    F = net.features
+    cw = net.conv_w if net.conv_w.is_contiguous() else net.conv_w.contiguous()
+    pw = net.proj_w if net.proj_w.stride(1) == 1 else net.proj_w.contiguous()
+    if cw.numel() != 32 * net.filter_size ** 2 or tuple(pw.shape) != (d, F):
+        raise ValueError("kge_amd: conve_queries: convolution weight [32, 1, fs, fs] and projection weight [d, F] expected")
+    vecs = [getattr(net, k).contiguous() for k in ("bn1_mean", "bn1_var", "proj_b", "bn2_mean", "bn2_var")]
+    cb = None if net.conv_b is None else net.conv_b.contiguous()
+    if s is None or p is None:
+        raise ValueError("kge_amd: conve_queries: s and p are index vectors (None is not taken)")
+    keep = [cw, pw, cb] + vecs
+    ixs = []
+    si, pi = _index(s, ent.device, ixs), _index(p, ent.device, ixs)
+    n = _same_len(ixs, "conve_queries")
+    keep += ixs
+    if out is None:
+        out = _empty((n, d + 1), ent.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n or out.shape[1] < d + 1 or \
+            out.stride(1) != 1 or out.device != ent.device:
+        raise ValueError("kge_amd: conve_queries: out must be a float32 [n, >= d + 1] tensor with unit inner stride")
+    c = _lib.KgeConveNet(net.h, net.w, net.filter_size, net.padding, 0 if cb is None else 1, 0, cw.data_ptr(),
+                         None if cb is None else cb.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), pw.data_ptr(),
+                         pw.stride(0) if d > 1 else F, vecs[2].data_ptr(), vecs[3].data_ptr(), vecs[4].data_ptr(),
+                         net.bn1_eps, net.bn2_eps)
+    with _on_device(ent.device):
+        L = _lib.lib()
+        need = L.kge_conve_workspace_bytes(ctypes.byref(c), n)
+        if n > 0 and need <= 0:
+            _lib.check(_lib.KGE_ERR_UNSUPPORTED, "kge_conve_queries (the shape is outside the gate)")
+        ws = _empty((max(need, 16),), ent.device, torch.uint8)
+        _lib.check(L.kge_conve_queries(ctypes.byref(c), ent.data_ptr(), ent.stride(0) if ent.shape[0] > 1 else d + 1,
+                                       rel.data_ptr(), rel.stride(0) if rel.shape[0] > 1 else d + 1, si, pi, n,
+                                       out.data_ptr(), out.stride(0) if n > 1 else out.shape[1], ws.data_ptr(), ws.numel(),
+                                       _stream(ent.device)), "kge_conve_queries")
+    return out
+
+
 def _tucker3(B: torch.Tensor, W: torch.Tensor, what: str):
     """(kge_tucker3 descriptor, d) of a base table B [R, d_r] and a projection weight W [d^2, d_r]."""
     _require_gpu(B, what + ": the base table")

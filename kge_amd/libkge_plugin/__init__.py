@@ -4,7 +4,7 @@ Usage inside an unmodified LibKGE installation (config-default.yaml:137, README.
 
     modules: [kge.job, kge.model, kge.model.embedder, kge_amd.libkge_plugin]
     model: hip_complex            # or hip_distmult / hip_transe / hip_rotate / hip_transh / hip_rescal /
-    #                               hip_relational_tucker3
+    #                               hip_relational_tucker3 / hip_conve (under reciprocal relations)
     #   (or model: hip_reciprocal_relations_model with hip_reciprocal_relations_model.base_model.type: hip_complex)
     # optional: eval.type: hip_entity_ranking
     # optional: train.type: hip_1vsAll / hip_KvsAll  (kl / bce loss fused into the scoring kernel)
@@ -32,7 +32,7 @@ try:
 except ImportError as e:  # pragma: no cover
     raise ImportError("kge_amd.libkge_plugin needs LibKGE (`kge`) to be importable") from e
 
-from .models import (HipComplEx, HipComplExScorer, HipDistMult, HipDistMultScorer,  # noqa: F401
+from .models import (HipComplEx, HipComplExScorer, HipConvE, HipConvEScorer, HipDistMult, HipDistMultScorer,  # noqa: F401
                      HipReciprocalRelationsModel, HipRelationalTucker3, HipRescal, HipRescalScorer, HipRotatE,
                      HipRotatEScorer, HipTransE, HipTransEScorer, HipTransH, HipTransHScorer)
 from .eval_job import HipEntityRankingJob  # noqa: F401

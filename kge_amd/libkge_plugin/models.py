@@ -4,6 +4,8 @@ from torch import Tensor
 
 from kge import Config, Dataset
 from kge.model.kge_model import KgeModel, RelationalScorer
+from kge.model.conve import ConvE as _RefConvE
+from kge.model.conve import ConvEScorer as _RefConvEScorer
 from kge.model.rescal import Rescal as _RefRescal
 from kge.model.rescal import RescalScorer as _RefRescalScorer
 from kge.model.rescal import rescal_set_relation_embedder_dim
@@ -17,7 +19,7 @@ from kge.model.transh import transh_set_relation_embedder_dim
 from .. import engine
 from ..model import (BF16Shadow, _FusedBCEDist, _FusedBCEF32, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32,
                      _FusedKLDist, _FusedKLF32, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
-                     Tucker3Routes, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable,
+                     ConveNetOps, ConveRoutes, Tucker3Routes, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable,
                      predict_filters, topk_composed)
 
 
@@ -742,6 +744,118 @@ class HipRelationalTucker3(Tucker3Routes, _FusedScoring, _RefRelationalTucker3):
         if self._table_call(p):
             return super().score_sp_po(s, p, o, entity_subset)
         return torch.cat((self.score_sp(s, p, entity_subset), self.score_po(p, o, entity_subset)), dim=1)
+
+
+class HipConvEScorer(ConveNetOps, _RefConvEScorer):
+    """The scorer of hip_conve: the reference's constructor (conve.py:14-73: its modules, its shape rule, the names of
+    its state_dict) with score_emb restated (kge_amd.model.ConveNetOps) so that on a GPU in float32 the contraction and
+    its backward are the DistMult kernels over q' = [1 | x]; on CPU it is the reference's arithmetic in torch."""
+
+    name = "conve"
+    _norm = 1.0
+
+
+class HipConvE(ConveRoutes, _FusedScoring, _RefConvE):
+    """`model: hip_conve`: kge/model/conve.py with score_sp and score_spo(direction="o") on the two routes of
+    kge_amd.model.ConveRoutes -- kge_conve_queries + the float32 DistMult contraction in eval mode without a recorded
+    gradient, torch operations with autograd otherwise.  The constructor repeats conve.py:107-135 (the +1 dimension
+    hack) with the HIP scorer.  Use it as hip_reciprocal_relations_model.base_model.type: score_po, score_sp_po and the
+    other directions raise the reference's errors.  Options without a ConvE kernel are refused by name."""
+
+    def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
+        self._init_configuration(config, configuration_key)
+        for key in ("entity_embedder.dim", "relation_embedder.dim"):  # HACK to add bias terms to embeddings
+            self.set_option(key, self.get_option(key) + 1)
+        _init(self, HipConvEScorer(config, dataset, self.configuration_key), config, dataset, self.configuration_key,
+              init_for_load_only)
+        for key in ("entity_embedder.dim", "relation_embedder.dim"):  # UNDO hack
+            self.set_option(key, self.get_option(key) - 1)
+        self._init_routes()
+        try:
+            self.padded_table_max_bytes = int(self.get_option("padded_table_max_bytes"))
+        except KeyError:
+            pass
+
+    def _fused(self) -> bool:
+        ent, rel = self._w()
+        return super()._fused() and ent.dtype == torch.float32 and rel.dtype == torch.float32
+
+    def _conve_parts(self):
+        ent, rel = self._w()
+        return ent, rel, self._scorer, self._fused()
+
+    def _torch_scores(self, s, p, o, combine):
+        se, pe = self.get_s_embedder().embed(s), self.get_p_embedder().embed(p)
+        if o is None:
+            oe = self.get_o_embedder().embed_all()
+        elif isinstance(o, range):
+            oe = self.get_o_embedder().embed_all()[o.start:o.stop]
+        else:
+            oe = self.get_o_embedder().embed(o)
+        return self._scorer.score_emb(se, pe, oe, combine)
+
+    def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
+        if direction != "o":
+            raise ValueError("ConvE can only score objects")
+        if not self._fused():
+            return KgeModel.score_spo(self, s, p, o, direction)
+        return self.conve_scores(s, p, o, "spo").view(-1)
+
+    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
+        if not self._fused():
+            return KgeModel.score_sp(self, s, p, o)
+        return self.conve_scores(s, p, self._targets(o) if not torch.is_grad_enabled() else o, "sp_")
+
+    def score_po(self, p: Tensor, o: Tensor, s: Tensor = None) -> Tensor:
+        return KgeModel.score_po(self, p, o, s)  # (the scorer raises: "_po" is not supported)
+
+    def score_sp_po(self, s: Tensor, p: Tensor, o: Tensor, entity_subset: Tensor = None) -> Tensor:
+        return KgeModel.score_sp_po(self, s, p, o, entity_subset)  # (likewise)
+
+    def __setattr__(self, name, value):
+        # hip_1vsAll / hip_KvsAll switch their fused losses on by setting these attributes on the model
+        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
+            raise ValueError("hip_conve: {} is not supported (no ConvE kernel behind the fused losses)".format(
+                name.lstrip("_")))
+        super().__setattr__(name, value)
+
+    def set_touched_rows(self, pair):
+        if pair is not None:
+            raise ValueError("hip_conve: touched_rows is not supported")
+        self._touched_rows = None
+
+    def score_neg(self, s, p, o, slot, neg):
+        raise ValueError("hip_conve: negative-sampling blocks (hip_negative_sampling's score_neg) are not supported; "
+                         "use train.type: negative_sampling")
+
+    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
+        raise ValueError("hip_conve: negative-sampling blocks (negative_sampling.shared through score_neg_shared) are "
+                         "not supported; use train.type: negative_sampling")
+
+    def score_neg_blocks(self, s, p, o, neg_s=None, neg_o=None):
+        raise ValueError("hip_conve: negative-sampling blocks (hip_negative_sampling's score_neg_blocks) are not "
+                         "supported; use train.type: negative_sampling")
+
+    def _ce_tables(self):
+        return None
+
+    def _ce_dist_tables(self):
+        return None
+
+    def _ce_f32_tables(self):
+        return None
+
+    def _dropout_only(self):
+        return None
+
+    def _rank_tables(self):
+        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
+
+    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
+        if direction != "sp_":
+            raise Exception("Combine {} not supported in ConvE's score function".format(direction))
+        with torch.no_grad():
+            return topk_composed(self.score_sp(a, p), k, filters, keep)
 
 
 class HipRotatE(_FusedScoring, _RefRotatE):

@@ -173,7 +173,7 @@ class RescalScorer(RelationalScorer):
 
 # scorers whose predictions, shared samples and evaluation take the composed paths (no kge_topk / kge_score_neg_shared /
 # fused-loss kernel behind them)
-_COMPOSED_ONLY = ("transh", "rescal")
+_COMPOSED_ONLY = ("transh", "rescal", "conve")
 
 
 class KgeModel(torch.nn.Module):
@@ -183,7 +183,7 @@ class KgeModel(torch.nn.Module):
 
     def __init__(self, num_entities: int, num_relations: int, dim: int, l_norm: float = 1.0,
                  dtype=torch.float32, device=None, entity_args=None, relation_args=None,
-                 score_dtype=None, fused_dist_loss: bool = False, fused_f32_loss: bool = False):
+                 score_dtype=None, fused_dist_loss: bool = False, fused_f32_loss: bool = False, scorer_args=None):
         super().__init__()
         # fused_f32_loss=True (ComplEx / DistMult, float32 parameters on a GPU scored in float32, dim % 8 == 0): loss_sp /
         # loss_po / loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_f32_fwd / _bwd), and kl_loss_sp /
@@ -224,8 +224,12 @@ class KgeModel(torch.nn.Module):
         self._entity_embedder = LookupEmbedder(num_entities, dim, dtype=dtype, device=device,
                                                **(entity_args or {}))
         self._relation_embedder = self._make_relation_embedder(num_relations, rel_dim, dtype, device, relation_args)
-        self._scorer = self.scorer_cls(l_norm)
+        self._scorer = self._make_scorer(l_norm, dtype, device, scorer_args)
         self._touched_rows = None  # set_touched_rows
+
+    def _make_scorer(self, l_norm, dtype, device, scorer_args):
+        """`scorer_args`: what a subclass's constructor hands to its scorer (ConvE: the network's options)"""
+        return self.scorer_cls(l_norm)
 
     def _make_relation_embedder(self, num_relations, rel_dim, dtype, device, relation_args):
         return LookupEmbedder(num_relations, rel_dim, dtype=dtype, device=device, **relation_args)
@@ -793,8 +797,240 @@ class RelationalTucker3(Tucker3Routes, KgeModel):
                           self.score_po(p, o, entity_subset, project=project)), dim=1)
 
 
+def conve_image_shape(dim: int, aspect_ratio: float = 2, round_dim: bool = False):
+    """(h, w, d) of conve.py:17-42: h = sqrt(d / aspect_ratio), w = h * aspect_ratio; round_dim rounds h up and d with
+    it, otherwise a d that does not factor raises the reference's error."""
+    height = math.sqrt(dim / aspect_ratio)
+    width = height * aspect_ratio
+    rounded = math.ceil(height)
+    if round_dim and rounded != height:
+        height = rounded
+        width = height * aspect_ratio
+        dim = height * width
+    elif dim % height or dim % width:
+        raise Exception(("Embedding dimension {} incompatible with aspect ratio {}; width ({}) or height ({}) is not "
+                         "integer. Adapt dimension or set conve.round_dim=true").format(dim, aspect_ratio, width, height))
+    return int(height), int(width), int(dim)
+
+
+class ConveNetOps:
+    """The network of conve.py:75-101 over the reference's module names (convolution, bn1, bn2, projection,
+    feature_map_dropout, projection_dropout) and shape attributes (emb_height, emb_width, filter_size, padding) -- mixed
+    into ConvEScorer here and into the plugin's HipConvEScorer, whose modules the reference's constructor builds."""
+
+    def network(self, s_emb: Tensor, p_emb: Tensor) -> Tensor:
+        """x [n, d] of conve.py:81-93"""
+        n = p_emb.size(0)
+        s2 = s_emb[:, 1:].reshape(-1, 1, int(self.emb_height), int(self.emb_width))
+        p2 = p_emb[:, 1:].reshape(-1, 1, int(self.emb_height), int(self.emb_width))
+        out = self.convolution(torch.cat([s2, p2], 2))
+        out = torch.relu(self.bn1(out))
+        out = self.feature_map_dropout(out)
+        out = self.projection(out.view(n, -1))
+        out = self.projection_dropout(out)
+        return torch.relu(self.bn2(out))
+
+    def kernel_net(self) -> "engine.ConveNet":
+        return engine.ConveNet(int(self.emb_height), int(self.emb_width), int(self.filter_size), int(self.padding),
+                               self.convolution.weight.detach(),
+                               None if self.convolution.bias is None else self.convolution.bias.detach(),
+                               self.bn1.running_mean, self.bn1.running_var, self.bn1.eps, self.projection.weight.detach(),
+                               self.projection.bias.detach(), self.bn2.running_mean, self.bn2.running_var, self.bn2.eps)
+
+    def score_emb(self, s_emb: Tensor, p_emb: Tensor, o_emb: Tensor, combine: str) -> Tensor:
+        if combine not in ["sp_", "spo"]:
+            raise Exception("Combine {} not supported in ConvE's score function".format(combine))
+        n = p_emb.size(0)
+        x = self.network(s_emb, p_emb)
+        if x.is_cuda and x.dtype == torch.float32 and o_emb.dtype == torch.float32:
+            q = torch.cat([torch.ones_like(x[:, :1]), x], 1)  # the gradient of column 0 is dropped by the cat
+            out = _ScoreEmb.apply("distmult", combine, 1.0, q, torch.ones_like(q), o_emb)
+        elif combine == "sp_":
+            out = torch.mm(x, o_emb[:, 1:].transpose(1, 0)) + o_emb[:, 0]
+        else:
+            out = (x * o_emb[:, 1:]).sum(-1) + o_emb[:, 0]
+        return out.view(n, -1)
+
+
+class ConvEScorer(ConveNetOps, RelationalScorer):
+    """kge/model/conve.py:9-101 on torch operations with autograd -- the TORCH ROUTE of ConvE: training mode (batch
+    statistics, Dropout2d, Dropout), a recorded gradient, CPU parameters, a shape outside the kernel's gate.  Module names
+    equal the reference's (convolution, bn1, bn2, projection): state_dicts interchange.  Embeddings have d + 1 columns,
+    column 0 of an entity row is its bias.  On a GPU in float32 the contraction (and its backward) is the DistMult
+    kernels' over the augmented query q' = [1 | x] (_ScoreEmb); on CPU it is plain torch."""
+
+    name = "conve"
+
+    def __init__(self, dim: int, aspect_ratio=2, filter_size: int = 3, padding: int = 0, feature_map_dropout: float = 0.2,
+                 projection_dropout: float = 0.3, convolution_bias: bool = True, round_dim: bool = False,
+                 dtype=torch.float32, device=None):
+        super().__init__(1.0)
+        self.emb_height, self.emb_width, self.emb_dim = conve_image_shape(dim, aspect_ratio, round_dim)
+        self.filter_size, self.stride, self.padding = int(filter_size), 1, int(padding)
+        self.feature_map_dropout = torch.nn.Dropout2d(feature_map_dropout)
+        self.projection_dropout = torch.nn.Dropout(projection_dropout)
+        self.convolution = torch.nn.Conv2d(1, 32, (self.filter_size, self.filter_size), stride=1, padding=self.padding,
+                                           bias=bool(convolution_bias), device=device, dtype=dtype)
+        self.bn1 = torch.nn.BatchNorm2d(32, affine=False, device=device, dtype=dtype)
+        self.bn2 = torch.nn.BatchNorm1d(self.emb_dim, affine=False, device=device, dtype=dtype)
+        ho = 2 * self.emb_height - self.filter_size + 2 * self.padding + 1
+        wo = self.emb_width - self.filter_size + 2 * self.padding + 1
+        if ho < 1 or wo < 1:
+            raise ValueError("ConvE: filter_size {} does not fit the {} x {} image".format(
+                filter_size, 2 * self.emb_height, self.emb_width))
+        self.projection = torch.nn.Linear(32 * ho * wo, self.emb_dim, device=device, dtype=dtype)
+
+
+class ConveRoutes:
+    """Which way a ConvE model scores (mixed into ConvE here and into the plugin's HipConvE, which say where the tables
+    and the scorer live: `_conve_parts()`).  Two routes:
+      "kernel"  module in eval mode, no gradient recorded, float32 parameters on a GPU, a shape inside the gate of
+                kge_conve_queries: the query network as ONE canonical arithmetic (engine.conve_queries), then the float32
+                DistMult contraction of q' with the entity rows.  Rows of d + 1 floats miss the vectorised matrix-core
+                path of the pair kernel (d % 8 == 0, 16-byte aligned rows), so the route keeps a copy of the entity
+                table padded with zero columns to a multiple of 8 floats, and a matching zero-padded q'; zeros add
+                exactly nothing to an fma chain.  The copy is cached on the table's version (the BF16Shadow pattern) and
+                left out above padded_table_max_bytes (the plain rows then take the element path: the same scores inside
+                the bound, slower).
+      "torch"   everything else: ConvEScorer.score_emb."""
+    padded_table_max_bytes = 1 << 30
+
+    def _conve_parts(self):
+        """(entity weight, relation weight, scorer, are both embedders pure lookups)"""
+        raise NotImplementedError
+
+    def _init_routes(self):
+        self.routes = {"kernel": 0, "torch": 0}  # calls per route (what the tests assert)
+        self.paddings = 0  # padded copies made (the cache's misses)
+        self._pad_key, self._pad_table, self._pad_ones = None, None, None
+        self._gate = None  # (shape, does kge_conve_queries take it): asked of the library once per shape
+
+    def kernel_route(self) -> bool:
+        ent, rel, sc, pure = self._conve_parts()
+        if self.training or sc.training or not pure or not ent.is_cuda or ent.dtype != torch.float32 or rel.dtype != torch.float32:
+            return False
+        if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad or
+                                        any(x.requires_grad for x in sc.parameters())):
+            return False
+        if int(getattr(sc, "stride", 1)) != 1:  # (the reference's option; the kernel is stride 1 by construction)
+            return False
+        shape = (int(sc.emb_height), int(sc.emb_width), int(sc.filter_size), int(sc.padding))
+        if self._gate is None or self._gate[0] != shape:
+            self._gate = (shape, engine.conve_gate(*shape))
+        return self._gate[1]
+
+    def padded_table(self):
+        """[E, dp] zero-padded copy of the entity table, dp = d + 1 rounded up to 8; None above the byte cap"""
+        ent = self._conve_parts()[0]
+        dp = (ent.shape[1] + 7) // 8 * 8
+        if ent.shape[0] * dp * ent.element_size() > self.padded_table_max_bytes:
+            return None
+        key = (ent._version, ent.data_ptr(), ent.device, tuple(ent.shape))
+        if key != self._pad_key:
+            t = torch.zeros((ent.shape[0], dp), dtype=ent.dtype, device=ent.device)
+            t[:, :ent.shape[1]] = ent.detach()
+            self._pad_table, self._pad_key = t, key
+            self.paddings += 1
+        return self._pad_table
+
+    def _kernel_scores(self, s: Tensor, p: Tensor, o, combine: str) -> Tensor:
+        ent, rel, sc, _ = self._conve_parts()
+        n = s.numel()
+        with torch.no_grad():
+            table = self.padded_table()
+            if table is None:
+                table = ent.detach()
+            dp = table.shape[1]
+            q = torch.zeros((n, dp), dtype=torch.float32, device=ent.device)
+            engine.conve_queries(sc.kernel_net(), ent.detach(), rel.detach(), s, p, out=q)
+            if self._pad_ones is None or self._pad_ones.shape[0] < n or self._pad_ones.shape[1] != dp or \
+                    self._pad_ones.device != ent.device:
+                self._pad_ones = torch.ones((max(n, 64), dp), dtype=torch.float32, device=ent.device)
+            if o is None:
+                rows = table
+            elif isinstance(o, range):  # (a contiguous chunk of the table: the plugin's _targets)
+                rows = table[o.start:o.stop]
+            else:
+                rows = table[o.reshape(-1).long()]
+            return engine.score_emb("distmult", q, self._pad_ones[:n], rows, combine)
+
+    def conve_scores(self, s: Tensor, p: Tensor, o, combine: str) -> Tensor:
+        """combine "sp_": [n, E] (o None) or [n, len(o)]; "spo": [n, 1]"""
+        if self.kernel_route():
+            self.routes["kernel"] += 1
+            return self._kernel_scores(s, p, o, combine)
+        self.routes["torch"] += 1
+        return self._torch_scores(s, p, o, combine)
+
+
+class ConvE(ConveRoutes, KgeModel):
+    """kge/model/conve.py:104-144: embedders of d + 1 columns (the bias hack), score_sp and score_spo(direction="o")
+    only -- use it under reciprocal relations, as the reference says.  The routes: ConveRoutes.  A fused training forward
+    and backward of the network is not here (the follow-up)."""
+    scorer_cls = ConvEScorer
+
+    def __init__(self, num_entities: int, num_relations: int, dim: int, aspect_ratio=2, filter_size: int = 3,
+                 padding: int = 0, feature_map_dropout: float = 0.2, projection_dropout: float = 0.3,
+                 convolution_bias: bool = True, round_dim: bool = False, padded_table_max_bytes: int = 1 << 30, **kw):
+        for opt in ("fused_dist_loss", "fused_f32_loss", "score_dtype"):
+            if kw.get(opt):  # no ConvE kernel behind the fused losses, no bf16 scoring
+                raise ValueError("ConvE: {} is not supported (the losses are composed from score_sp)".format(opt))
+        h, w, d = conve_image_shape(dim, aspect_ratio, round_dim)
+        net_args = dict(dim=d, aspect_ratio=aspect_ratio, filter_size=filter_size, padding=padding,
+                        feature_map_dropout=feature_map_dropout, projection_dropout=projection_dropout,
+                        convolution_bias=convolution_bias, round_dim=False)
+        super().__init__(num_entities, num_relations, d + 1, scorer_args=net_args, **kw)
+        self.padded_table_max_bytes = int(padded_table_max_bytes)
+        self._init_routes()
+
+    def _make_scorer(self, l_norm, dtype, device, scorer_args):
+        return ConvEScorer(dtype=dtype, device=device, **scorer_args)
+
+    def _conve_parts(self):
+        return (self._entity_embedder.weight, self._relation_embedder.weight, self._scorer, self._fused())
+
+    def _torch_scores(self, s, p, o, combine):
+        se, pe = self._entity_embedder.embed(s), self._relation_embedder.embed(p)
+        oe = self._entity_embedder.embed_all() if o is None else self._entity_embedder.embed(o)
+        return self._scorer.score_emb(se, pe, oe, combine)
+
+    def tables(self, flags: int = 0):
+        raise ValueError("ConvE: there are no kge_tables of a ConvE model (its score is not a function of three rows)")
+
+    def set_touched_rows(self, pair):
+        if pair is not None:
+            raise ValueError("ConvE: touched_rows is not supported")
+        self._touched_rows = None
+
+    def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
+        if direction != "o":
+            raise ValueError("ConvE can only score objects")
+        return self.conve_scores(s, p, o, "spo").view(-1)
+
+    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
+        return self.conve_scores(s, p, o, "sp_")
+
+    def score_po(self, p: Tensor, o: Tensor, s: Tensor = None) -> Tensor:
+        raise Exception("Combine {} not supported in ConvE's score function".format("_po"))
+
+    def score_sp_po(self, s: Tensor, p: Tensor, o: Tensor, entity_subset: Tensor = None) -> Tensor:
+        raise Exception("Combine {} not supported in ConvE's score function".format("_po"))
+
+    def score_so(self, s: Tensor, o: Tensor, p: Tensor = None) -> Tensor:
+        raise Exception("Combine {} not supported in ConvE's score function".format("s_o"))
+
+    def score_neg(self, s, p, o, slot, neg):
+        raise ValueError("ConvE: negative-sampling blocks (score_neg) are not supported")
+
+    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
+        raise ValueError("ConvE: negative-sampling blocks (score_neg_shared) are not supported")
+
+    def score_neg_blocks(self, s, p, o, neg_s=None, neg_o=None):
+        raise ValueError("ConvE: negative-sampling blocks (score_neg_blocks) are not supported")
+
+
 MODELS = {"complex": ComplEx, "distmult": DistMult, "transe": TransE, "rotate": RotatE, "transh": TransH,
-          "rescal": Rescal, "relational_tucker3": RelationalTucker3}
+          "rescal": Rescal, "relational_tucker3": RelationalTucker3, "conve": ConvE}
 
 
 def create(model: str, num_entities: int, num_relations: int, dim: int, **kw) -> KgeModel:
