@@ -2037,29 +2037,70 @@ int kge_ce_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index
 
 // ---- the same loss for the distance scorers on float32 tables (ce_dist.hip): train_1vsAll.py:64-81, loss.py:192-207,
 // transe.py:18-34, rotate.py:30-64 ------------------------------------------------------------------------------
+// What the entries of this loss and of its float32 ComplEx / DistMult and KvsAll twins below share: the target operand,
+// ONE argument check and ONE workspace query, each taking the family's table predicate (static: the functions of this
+// block are inside extern "C", where the unnamed namespace alone does not keep a name out of the library's exports).
 namespace {
+static Operand all_ent(const kge_tables* t) {  // every row of the entity table
+  const kge_index all = {nullptr, 0, 0, 1};
+  return ent_op(t, all);
+}
 bool ce_dist_tables_ok(const kge_tables* t) {
   if (t->scorer != KGE_TRANSE && t->scorer != KGE_ROTATE) return false;
   if (t->dtype != KGE_F32) return false;
   return t->l_norm == 1.0f || t->l_norm == 2.0f;
 }
-int ce_dist_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, const kge_index& label,
-                  int64_t n) {
+// what run_pairs_f32 accepts: the layout every gathered row shares with the table it comes from
+bool ce_f32_tables_ok(const kge_tables* t) {
+  if (t->scorer != KGE_COMPLEX && t->scorer != KGE_DISTMULT) return false;
+  if (t->dtype != KGE_F32 || t->rel_dim != t->dim) return false;
+  const kge_index all = {nullptr, 0, 0, 1};
+  return ce_f32_layout_ok((int)t->dim, all_ent(t), rel_op(t, all), all_ent(t));
+}
+// the status codes in the order they are decided: tables, direction, n, the family's tables, the indexes (`label`: the
+// 1vsAll entries), the label CSR (`csr`: the KvsAll entries, both arrays wherever there is a row)
+static int dense_check(const kge_tables* t, bool (*tables_ok)(const kge_tables*), int dir, const kge_index& a,
+                       const kge_index& p, int64_t n, const kge_index* label, bool csr = false,
+                       const int64_t* lbl_rowptr = nullptr, const int64_t* lbl_col = nullptr) {
   int rc = check_tables(t, true);
   if (rc) return rc;
   if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
   if (n < 0) return KGE_ERR_INVALID_ARG;
-  if (!ce_dist_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
-  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n)) || (rc = check_index(label, false, n)))
-    return rc;
+  if (!tables_ok(t)) return KGE_ERR_UNSUPPORTED;
+  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n))) return rc;
+  if (label && (rc = check_index(*label, false, n))) return rc;
+  if (csr && n > 0 && (!lbl_rowptr || !lbl_col)) return KGE_ERR_INVALID_ARG;
   return KGE_OK;
+}
+// its four bindings (names the library has exported so far: kept)
+int ce_dist_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, const kge_index& label,
+                  int64_t n) {
+  return dense_check(t, ce_dist_tables_ok, dir, a, p, n, &label);
+}
+int ce_f32_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, const kge_index& label,
+                 int64_t n) {
+  return dense_check(t, ce_f32_tables_ok, dir, a, p, n, &label);
+}
+int ml_dist_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, int64_t n,
+                  const int64_t* lbl_rowptr, const int64_t* lbl_col) {
+  return dense_check(t, ce_dist_tables_ok, dir, a, p, n, nullptr, true, lbl_rowptr, lbl_col);
+}
+int ml_f32_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, int64_t n,
+                 const int64_t* lbl_rowptr, const int64_t* lbl_col) {
+  return dense_check(t, ce_f32_tables_ok, dir, a, p, n, nullptr, true, lbl_rowptr, lbl_col);
+}
+// 0: these tables, this n or this chunk width (a multiple of `chunk_multiple`) are not taken
+static int64_t dense_workspace_bytes(const kge_tables* t, bool (*tables_ok)(const kge_tables*), int64_t n,
+                                     int64_t chunk_cols, int chunk_multiple,
+                                     long long (*bytes)(long long, long long, int, long long)) {
+  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !tables_ok(t)) return 0;
+  if (chunk_cols < 0 || chunk_cols % chunk_multiple) return 0;
+  return bytes(n, t->num_ent, (int)t->dim, chunk_cols);
 }
 }  // namespace
 
 int64_t kge_ce_dist_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
-  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_dist_tables_ok(t)) return 0;
-  if (chunk_cols < 0 || chunk_cols % 64) return 0;
-  return ce_dist_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+  return dense_workspace_bytes(t, ce_dist_tables_ok, n, chunk_cols, 64, ce_dist_workspace_bytes);
 }
 
 int kge_ce_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label, int64_t n,
@@ -2069,8 +2110,7 @@ int kge_ce_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_
   if (rc) return rc;
   if (n == 0) return KGE_OK;
   if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ce_dist_fwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+  return run_ce_dist_fwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, make_index(label), loss_rows, lse, workspace, workspace_bytes,
                          (hipStream_t)stream);
 }
@@ -2082,39 +2122,15 @@ int kge_ce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_
   const int rc = ce_dist_check(t, dir, a, p, label, n);
   if (rc) return rc;
   if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ce_dist_bwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+  return run_ce_dist_bwd(t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, make_index(label), lse, g_rows, g_scalar, g_a, g_p, g_tgt,
                          workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- the same loss for ComplEx / DistMult on FLOAT32 tables (ce_f32.hip): train_1vsAll.py:64-81, loss.py:192-207,
 // complex.py:30-39, distmult.py:15-21 ------------------------------------------------------------------------------
-namespace {
-// what run_pairs_f32 accepts: the layout every gathered row shares with the table it comes from
-bool ce_f32_tables_ok(const kge_tables* t) {
-  if (t->scorer != KGE_COMPLEX && t->scorer != KGE_DISTMULT) return false;
-  if (t->dtype != KGE_F32 || t->rel_dim != t->dim) return false;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return ce_f32_layout_ok((int)t->dim, ent_op(t, all), rel_op(t, all), ent_op(t, all));
-}
-int ce_f32_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, const kge_index& label,
-                 int64_t n) {
-  int rc = check_tables(t, true);
-  if (rc) return rc;
-  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
-  if (n < 0) return KGE_ERR_INVALID_ARG;
-  if (!ce_f32_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
-  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n)) || (rc = check_index(label, false, n)))
-    return rc;
-  return KGE_OK;
-}
-}  // namespace
-
 int64_t kge_ce_f32_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
-  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_f32_tables_ok(t)) return 0;
-  if (chunk_cols < 0 || chunk_cols % 128) return 0;
-  return ce_f32_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+  return dense_workspace_bytes(t, ce_f32_tables_ok, n, chunk_cols, 128, ce_f32_workspace_bytes);
 }
 
 int kge_ce_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_index label, int64_t n,
@@ -2124,8 +2140,7 @@ int kge_ce_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_i
   if (rc) return rc;
   if (n == 0) return KGE_OK;
   if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ce_f32_fwd(t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+  return run_ce_f32_fwd(t->scorer, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim, n, t->num_ent,
                         make_index(label), loss_rows, lse, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -2136,32 +2151,15 @@ int kge_ce_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, kge_i
   const int rc = ce_f32_check(t, dir, a, p, label, n);
   if (rc) return rc;
   if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ce_f32_bwd(t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+  return run_ce_f32_bwd(t->scorer, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim, n, t->num_ent,
                         make_index(label), lse, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
                         (hipStream_t)stream);
 }
 
 // ---- the KvsAll losses of the distance scorers on float32 tables (ce_dist.hip, the folds FOLD_KL = 1 / FOLD_BCE = 2):
 // train_KvsAll.py:216-294, loss.py:137-159 and :192-213 ----------------------------------------------------------------
-namespace {
-int ml_dist_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, int64_t n,
-                  const int64_t* lbl_rowptr, const int64_t* lbl_col) {
-  int rc = check_tables(t, true);
-  if (rc) return rc;
-  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
-  if (n < 0) return KGE_ERR_INVALID_ARG;
-  if (!ce_dist_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
-  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n))) return rc;
-  if (n > 0 && (!lbl_rowptr || !lbl_col)) return KGE_ERR_INVALID_ARG;
-  return KGE_OK;
-}
-}  // namespace
-
 int64_t kge_multilabel_dist_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
-  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_dist_tables_ok(t)) return 0;
-  if (chunk_cols < 0 || chunk_cols % 64) return 0;
-  return ml_dist_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+  return dense_workspace_bytes(t, ce_dist_tables_ok, n, chunk_cols, 64, ml_dist_workspace_bytes);
 }
 
 int kge_kl_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
@@ -2172,8 +2170,7 @@ int kge_kl_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int6
   if (rc) return rc;
   if (n == 0) return KGE_OK;
   if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_dist_fwd(1, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+  return run_ml_dist_fwd(1, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col,
                          label_weight, 0.0f, loss_rows, lse, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2186,8 +2183,7 @@ int kge_kl_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int6
   const int rc = ml_dist_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
   if (rc) return rc;
   if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_dist_bwd(1, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+  return run_ml_dist_bwd(1, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col,
                          label_weight, 0.0f, lse, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
                          (hipStream_t)stream);
@@ -2201,8 +2197,7 @@ int kge_bce_dist_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int
   if (rc) return rc;
   if (n == 0) return KGE_OK;
   if (!loss_rows) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_dist_fwd(2, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+  return run_ml_dist_fwd(2, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr,
                          offset, loss_rows, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2214,8 +2209,7 @@ int kge_bce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int
   const int rc = ml_dist_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
   if (rc) return rc;
   if (!g_tgt || (n > 0 && (!g_a || !g_p))) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_dist_bwd(2, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim,
+  return run_ml_dist_bwd(2, t->scorer, t->l_norm, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim,
                          (int)t->rel_dim, n, t->num_ent, (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr,
                          offset, nullptr, g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes,
                          (hipStream_t)stream);
@@ -2223,24 +2217,8 @@ int kge_bce_dist_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int
 
 // ---- the KvsAll losses of ComplEx / DistMult on FLOAT32 tables (ce_f32.hip, the folds F3_KL / F3_BCE and the gradient
 // epilogues F3_GRAD_KL / F3_GRAD_BCE): train_KvsAll.py:216-294, loss.py:137-159 and :192-213 ---------------------------
-namespace {
-int ml_f32_check(const kge_tables* t, int dir, const kge_index& a, const kge_index& p, int64_t n,
-                 const int64_t* lbl_rowptr, const int64_t* lbl_col) {
-  int rc = check_tables(t, true);
-  if (rc) return rc;
-  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
-  if (n < 0) return KGE_ERR_INVALID_ARG;
-  if (!ce_f32_tables_ok(t)) return KGE_ERR_UNSUPPORTED;
-  if ((rc = check_index(a, false, n)) || (rc = check_index(p, false, n))) return rc;
-  if (n > 0 && (!lbl_rowptr || !lbl_col)) return KGE_ERR_INVALID_ARG;
-  return KGE_OK;
-}
-}  // namespace
-
 int64_t kge_multilabel_f32_workspace_bytes(const kge_tables* t, int64_t n, int64_t chunk_cols) {
-  if (check_tables(t, false) != KGE_OK || n <= 0 || t->num_ent <= 0 || !ce_f32_tables_ok(t)) return 0;
-  if (chunk_cols < 0 || chunk_cols % 128) return 0;
-  return ml_f32_workspace_bytes(n, t->num_ent, (int)t->dim, chunk_cols);
+  return dense_workspace_bytes(t, ce_f32_tables_ok, n, chunk_cols, 128, ml_f32_workspace_bytes);
 }
 
 int kge_kl_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,
@@ -2251,8 +2229,7 @@ int kge_kl_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64
   if (rc) return rc;
   if (n == 0) return KGE_OK;
   if (!loss_rows || !lse) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_f32_fwd(false, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+  return run_ml_f32_fwd(false, t->scorer, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim, n, t->num_ent,
                         (const long long*)lbl_rowptr, (const long long*)lbl_col, label_weight, 0.0f, loss_rows, lse,
                         workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2265,8 +2242,7 @@ int kge_kl_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64
   const int rc = ml_f32_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
   if (rc) return rc;
   if (!g_tgt || (n > 0 && (!lse || !g_a || !g_p))) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_f32_bwd(false, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+  return run_ml_f32_bwd(false, t->scorer, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim, n, t->num_ent,
                         (const long long*)lbl_rowptr, (const long long*)lbl_col, label_weight, label_bias, 0.0f, lse,
                         g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2279,8 +2255,7 @@ int kge_bce_f32_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int6
   if (rc) return rc;
   if (n == 0) return KGE_OK;
   if (!loss_rows) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_f32_fwd(true, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+  return run_ml_f32_fwd(true, t->scorer, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim, n, t->num_ent,
                         (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr, offset, loss_rows, nullptr,
                         workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -2292,8 +2267,7 @@ int kge_bce_f32_bwd(const kge_tables* t, int dir, kge_index a, kge_index p, int6
   const int rc = ml_f32_check(t, dir, a, p, n, lbl_rowptr, lbl_col);
   if (rc) return rc;
   if (!g_tgt || (n > 0 && (!g_a || !g_p))) return KGE_ERR_INVALID_ARG;
-  const kge_index all = {nullptr, 0, 0, 1};
-  return run_ml_f32_bwd(true, t->scorer, ent_op(t, a), rel_op(t, p), ent_op(t, all), dir, (int)t->dim, n, t->num_ent,
+  return run_ml_f32_bwd(true, t->scorer, ent_op(t, a), rel_op(t, p), all_ent(t), dir, (int)t->dim, n, t->num_ent,
                         (const long long*)lbl_rowptr, (const long long*)lbl_col, nullptr, nullptr, offset, nullptr,
                         g_rows, g_scalar, g_a, g_p, g_tgt, workspace, workspace_bytes, (hipStream_t)stream);
 }

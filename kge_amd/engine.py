@@ -14,6 +14,7 @@ Function <-> reference map (paths relative to the reference tree):
 import ctypes
 import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -2070,430 +2071,269 @@ def ce_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scalar: f
     return g_a, g_p, g_t
 
 
-def ce_dist_supported(t: Tables) -> bool:
-    """Can the fused 1vsAll loss of the distance scorers run on these tables (kge_ce_dist_workspace_bytes > 0):
-    TransE / RotatE, float32, l_norm 1 or 2, on a GPU?"""
+# ---- the dense-row losses on float32 tables, no [n, E] matrix: 1vsAll cross entropy (ce), KvsAll KL (kl) and KvsAll BCE
+# (bce), for two families of tables.  The kernels differ (csrc/ce_dist.hip, csrc/ce_f32.hip); everything above them is
+# written once against a family record, and the public functions bind a body to a family.  A public function's name is
+# its C entry's without "kge_" (ce_dist_fwd -> kge_ce_dist_fwd): the bodies take it as `what` ----------------------------
+class _DenseFamily(NamedTuple):
+    tag: str         # in the workspace keys "ce_<tag>" / "ml_<tag>" (distinct per device and stream)
+    scorers: tuple   # the scorers it takes, on float32 tables
+    extra: object    # its further table rule: Tables -> None, or the sentence that refuses them
+    chunk: int       # chunk_cols is a multiple of it
+    ws_bytes: dict   # loss group ("ce": 1vsAll; "ml": KvsAll kl and bce) -> the group's workspace-bytes symbol
+    kl_bias: bool    # does its kge_kl_*_bwd take label_bias?
+    only: str        # error text: what it takes ...
+    elsewhere: str   # ... and where other tables go ({0} / {1}: the group's bf16 and dist functions, _ELSEWHERE)
+    layout: str      # error text where the library's workspace query declines the tables
+
+
+_ELSEWHERE = {"ce": ("ce_fwd / ce_bwd", "ce_dist_fwd / ce_dist_bwd"),
+              "ml": ("kl_fwd / bce_fwd", "kl_dist_fwd / bce_dist_fwd")}
+
+_DIST = _DenseFamily(  # TransE / RotatE (kge_ce_dist_*, kge_kl_dist_*, kge_bce_dist_*)
+    tag="dist", scorers=(_lib.TRANSE, _lib.ROTATE), chunk=64, kl_bias=False,
+    extra=lambda t: None if t.l_norm in (1.0, 2.0) else
+    f"TransE / RotatE on float32 tables take l_norm 1 or 2, got {t.l_norm}",
+    ws_bytes={"ce": "kge_ce_dist_workspace_bytes", "ml": "kge_multilabel_dist_workspace_bytes"},
+    only="TransE / RotatE on float32 tables with l_norm 1 or 2 only", elsewhere="ComplEx / DistMult on bf16 tables: {0}",
+    layout="float32 TransE / RotatE tables with l_norm 1 or 2 only")
+
+_F32 = _DenseFamily(  # ComplEx / DistMult (kge_ce_f32_*, kge_kl_f32_*, kge_bce_f32_*)
+    tag="f32", scorers=(_lib.COMPLEX, _lib.DISTMULT), chunk=128, kl_bias=True,
+    extra=lambda t: f"the dimension must be a multiple of 8, got {t.ent.shape[1]}" if t.ent.shape[1] % 8 else None,
+    ws_bytes={"ce": "kge_ce_f32_workspace_bytes", "ml": "kge_multilabel_f32_workspace_bytes"},
+    only="ComplEx / DistMult on float32 tables only", elsewhere="bf16 tables: {0}; TransE / RotatE: {1}",
+    layout="float32 ComplEx / DistMult tables, dim % 8 == 0, 16-byte aligned rows only")
+
+
+def _ptr(x):
+    return None if x is None else x.data_ptr()
+
+
+def _dense_supported(fam, group, t: Tables) -> bool:
+    """Can the family's losses of this group run on these tables (its workspace query > 0), on a GPU?"""
     if not t.ent.is_cuda:
         return False
-    return _lib.lib().kge_ce_dist_workspace_bytes(ctypes.byref(t.c()), 1, 0) > 0
+    return getattr(_lib.lib(), fam.ws_bytes[group])(ctypes.byref(t.c()), 1, 0) > 0
 
 
-def _ce_dist_args(t: Tables, a, p, label, chunk_cols, what):
-    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths."""
+def _dense_args(fam, group, what, t: Tables, ixs, chunk_cols, csr=None, per_row=()):
+    """The checks every device takes, before anything is asked of a GPU, in one order for both families: chunk width,
+    tables, index lengths, the label CSR (`csr`: (rowptr, col), or None), the lengths of the `per_row` vectors ((tensor
+    or None, name) pairs), the device.  Returns (a KgeIndex per entry of `ixs`, n, chunk_cols, the CSR as int64 on the
+    device, the per-row vectors as contiguous float32 on the device, the tensors behind the indexes: keep them)."""
     chunk_cols = int(chunk_cols)
-    if chunk_cols < 0 or chunk_cols % 64:
-        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 64, got {chunk_cols}")
-    if t.scorer not in (_lib.TRANSE, _lib.ROTATE) or t.ent.dtype != torch.float32 or t.l_norm not in (1.0, 2.0):
-        raise RuntimeError(f"kge_amd: {what}: TransE / RotatE on float32 tables with l_norm 1 or 2 only "
-                           "(ComplEx / DistMult on bf16 tables: ce_fwd / ce_bwd)")
+    if chunk_cols < 0 or chunk_cols % fam.chunk:
+        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of {fam.chunk}, "
+                         f"got {chunk_cols}")
+    if t.scorer not in fam.scorers or t.ent.dtype != torch.float32 or t.rel.dtype != torch.float32:
+        raise RuntimeError(f"kge_amd: {what}: {fam.only} ({fam.elsewhere.format(*_ELSEWHERE[group])})")
+    why = fam.extra(t)
+    if why:
+        raise RuntimeError(f"kge_amd: {what}: {why}")
     keep = []
-    ixs = tuple(_index(x, t.device, keep) for x in (a, p, label))
-    n = _same_len(keep[:3], what)
+    ixs = tuple(_index(x, t.device, keep) for x in ixs)
+    n = _same_len(keep, what)
+    if csr is not None:
+        rowptr, col = csr
+        if not torch.is_tensor(rowptr) or not torch.is_tensor(col) or rowptr.dim() != 1 or col.dim() != 1:
+            raise ValueError(f"kge_amd: {what}: the labels are a CSR of two 1-d tensors (rowptr [n + 1], col [nnz])")
+        if rowptr.is_floating_point() or col.is_floating_point():
+            raise TypeError(f"kge_amd: {what}: the label CSR holds integers")
+        if rowptr.numel() != n + 1:
+            raise ValueError(f"kge_amd: {what}: label rowptr has {rowptr.numel()} entries for {n} rows")
+    for x, name in per_row:
+        if x is not None and x.numel() != n:
+            raise ValueError(f"kge_amd: {what}: {name} has {x.numel()} entries for {n} rows (one entry per row)")
     _require_gpu(t.ent, "entity table")
-    return ixs, n, chunk_cols, keep
+    rows = tuple(None if x is None else _f32c(x, t.device) for x, _ in per_row)
+    return ixs, n, chunk_cols, csr and _csr64(*csr, t.device), rows, keep
 
 
-def _ce_dist_workspace(tc, n, chunk_cols, device, st):
-    """(ptr, bytes): the per-(device, stream) scratch of kge_ce_dist_fwd / _bwd; `bytes` is exactly what the chunk width
-    asks for (the backward derives its chunk width from it), the buffer may be larger."""
-    need = _lib.lib().kge_ce_dist_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
+def _dense_workspace(fam, group, tc, n, chunk_cols, device, st):
+    """(ptr, bytes): the per-(device, stream) scratch of a family's loss group; `bytes` is exactly what the chunk width
+    asks for (the backward derives its chunk width from it), the buffer may be larger.  The multi-label backward leaves
+    the label bits zero and nothing else needs a value: no initialisation."""
+    need = getattr(_lib.lib(), fam.ws_bytes[group])(ctypes.byref(tc), n, chunk_cols)
     if need <= 0:
-        raise RuntimeError("kge_ce_dist_fwd/kge_ce_dist_bwd: float32 TransE / RotatE tables with l_norm 1 or 2 only")
-    key = (device.index, st, "ce_dist")
+        raise RuntimeError(f"{fam.ws_bytes[group]}: {fam.layout}")
+    key = (device.index, st, group + "_" + fam.tag)
     buf = _WORKSPACES.get(key)
     if buf is None or buf.numel() < need:
         buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
     return buf.data_ptr(), need
+
+
+def _dense_launch(fam, group, what, t: Tables, direction, n, chunk_cols, *args):
+    """kge_<what>(tables, direction, *args, workspace, its bytes, stream) on t's device and torch's current stream."""
+    with _on_device(t.device):
+        tc = t.c()
+        st = _stream_handle(t.device)
+        ws, wsb = _dense_workspace(fam, group, tc, n, chunk_cols, t.device, st)
+        _lib.check(getattr(_lib.lib(), "kge_" + what)(ctypes.byref(tc), SP_ if direction == "sp" else PO_, *args,
+                                                      ws, wsb, st), "kge_" + what)
+
+
+def _dense_bwd(fam, group, what, t: Tables, direction, n, chunk_cols, g_rows, g_scalar, *args):
+    """The end the three backwards share, kge_<what>(.., *args, g_rows, g_scalar, g_a, g_p, g_entities, ..): (g_a [n, d],
+    g_p [n, d_r], g_entities [E, d]).  An empty batch asks nothing of the library; its entity gradient is zero."""
+    d, dr = t.ent.shape[1], t.rel.shape[1]
+    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
+    if n == 0:
+        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
+    g_t = _empty((t.num_ent, d), t.device)
+    _dense_launch(fam, group, what, t, direction, n, chunk_cols, *args, _ptr(g_rows), float(g_scalar), g_a.data_ptr(),
+                  g_p.data_ptr(), g_t.data_ptr())
+    return g_a, g_p, g_t
+
+
+def _ce_rows_fwd(fam, what, t, direction, a, p, label, chunk_cols):
+    """ce_fwd on a family's float32 tables: (loss_rows [n], lse [n]) of score_sp ('sp': a = s, label = o) / score_po
+    ('po': a = o, label = s) against all entities, no [n, E] matrix."""
+    ixs, n, chunk_cols, _, _, keep = _dense_args(fam, "ce", what, t, (a, p, label), chunk_cols)
+    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
+    if n:
+        _dense_launch(fam, "ce", what, t, direction, n, chunk_cols, *ixs, n, loss_rows.data_ptr(), lse.data_ptr())
+    return loss_rows, lse
+
+
+def _ce_rows_bwd(fam, what, t, direction, a, p, label, lse, g_rows, g_scalar, chunk_cols):
+    """Backward of _ce_rows_fwd: gradients of sum_i g_i * loss_rows[i] w.r.t. the gathered query rows and all entity
+    rows: (g_a [n, d], g_p [n, d_r], g_entities [E, d]).  chunk_cols: entity columns per chunk of the backward (a
+    multiple of the family's `chunk`; 0 = the library's default, a chunk of at most 32 MB)."""
+    ixs, n, chunk_cols, _, (lse, gr), keep = _dense_args(fam, "ce", what, t, (a, p, label), chunk_cols, None,
+                                                         ((lse, "lse"), (g_rows, "g_rows")))
+    return _dense_bwd(fam, "ce", what, t, direction, n, chunk_cols, gr, g_scalar, *ixs, n, lse.data_ptr())
+
+
+def _kl_rows_fwd(fam, what, t, direction, a, p, lbl_rowptr, lbl_col, label_weight, chunk_cols):
+    """kl_fwd on a family's float32 tables: (loss_rows [n], lse [n]) of score_sp ('sp': a = s) / score_po ('po': a = o)
+    against all entities with the rows' labels as an int64 CSR (ids in any order), no [n, E] matrix.  label_weight [n]:
+    loss_rows[i] = lse[i] - label_weight[i] * (sum of row i's label scores)."""
+    ixs, n, chunk_cols, (rp, cl), (lw,), keep = _dense_args(fam, "ml", what, t, (a, p), chunk_cols, (lbl_rowptr, lbl_col),
+                                                            ((label_weight, "label_weight"),))
+    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
+    if n:
+        _dense_launch(fam, "ml", what, t, direction, n, chunk_cols, *ixs, n, rp.data_ptr(), cl.data_ptr(), _ptr(lw),
+                      loss_rows.data_ptr(), lse.data_ptr())
+    return loss_rows, lse
+
+
+def _kl_rows_bwd(fam, what, t, direction, a, p, lbl_rowptr, lbl_col, lse, g_rows, g_scalar, label_weight, label_bias,
+                 chunk_cols):
+    """Backward of _kl_rows_fwd: (g_a [n, d], g_p [n, d_r], g_entities [E, d]).  label_bias [n], where the family's
+    entry takes one (`kl_bias`): b_i is subtracted at every column (the uniform term of smoothed labels: the gradient
+    of loss_rows[i] - b_i sum_j score_ij).  chunk_cols: as in _ce_rows_bwd."""
+    ixs, n, chunk_cols, (rp, cl), (lse, gr, lw, lb), keep = _dense_args(
+        fam, "ml", what, t, (a, p), chunk_cols, (lbl_rowptr, lbl_col),
+        ((lse, "lse"), (g_rows, "g_rows"), (label_weight, "label_weight"), (label_bias, "label_bias")))
+    bias = (_ptr(lb),) if fam.kl_bias else ()
+    return _dense_bwd(fam, "ml", what, t, direction, n, chunk_cols, gr, g_scalar, *ixs, n, rp.data_ptr(), cl.data_ptr(),
+                      _ptr(lw), *bias, lse.data_ptr())
+
+
+def _bce_rows_fwd(fam, what, t, direction, a, p, lbl_rowptr, lbl_col, offset, chunk_cols):
+    """bce_fwd on a family's float32 tables: loss_rows [n], the sum over ALL entities of BCEWithLogits(score + offset,
+    multi-hot labels), the labels an int64 CSR as in _kl_rows_fwd, no [n, E] matrix."""
+    ixs, n, chunk_cols, (rp, cl), _, keep = _dense_args(fam, "ml", what, t, (a, p), chunk_cols, (lbl_rowptr, lbl_col))
+    loss_rows = _empty((n,), t.device)
+    if n:
+        _dense_launch(fam, "ml", what, t, direction, n, chunk_cols, *ixs, n, rp.data_ptr(), cl.data_ptr(), float(offset),
+                      loss_rows.data_ptr())
+    return loss_rows
+
+
+def _bce_rows_bwd(fam, what, t, direction, a, p, lbl_rowptr, lbl_col, offset, g_rows, g_scalar, chunk_cols):
+    """Backward of _bce_rows_fwd: (g_a [n, d], g_p [n, d_r], g_entities [E, d])."""
+    ixs, n, chunk_cols, (rp, cl), (gr,), keep = _dense_args(fam, "ml", what, t, (a, p), chunk_cols, (lbl_rowptr, lbl_col),
+                                                            ((g_rows, "g_rows"),))
+    return _dense_bwd(fam, "ml", what, t, direction, n, chunk_cols, gr, g_scalar, *ixs, n, rp.data_ptr(), cl.data_ptr(),
+                      float(offset))
+
+
+# the bindings: TransE / RotatE with l_norm 1 or 2 (chunk_cols a multiple of 64) ...
+def ce_dist_supported(t: Tables) -> bool:
+    """_dense_supported: the 1vsAll loss of TransE / RotatE (kge_ce_dist_workspace_bytes > 0)."""
+    return _dense_supported(_DIST, "ce", t)
 
 
 def ce_dist_fwd(t: Tables, direction: str, a, p, label, chunk_cols: int = 0):
-    """ce_fwd for TransE / RotatE on float32 tables (kge_ce_dist_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
-    a = s, label = o) / score_po ('po': a = o, label = s) against all entities, no [n, E] matrix."""
-    (ai, pi, li), n, chunk_cols, keep = _ce_dist_args(t, a, p, label, chunk_cols, "ce_dist_fwd")
-    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
-    if n == 0:
-        return loss_rows, lse
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ce_dist_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_ce_dist_fwd(ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n,
-                                              loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_ce_dist_fwd")
-    return loss_rows, lse
+    """_ce_rows_fwd for TransE / RotatE (kge_ce_dist_fwd)."""
+    return _ce_rows_fwd(_DIST, "ce_dist_fwd", t, direction, a, p, label, chunk_cols)
 
 
 def ce_dist_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scalar: float = 1.0, chunk_cols: int = 0):
-    """Backward of ce_dist_fwd (kge_ce_dist_bwd): gradients of sum_i g_i * loss_rows[i] w.r.t. the gathered query rows
-    and all entity rows: (g_a [n, d], g_p [n, d_r], g_entities [E, d]).  chunk_cols: entity columns per chunk of the
-    backward (a multiple of 64; 0 = the library's default, a score chunk of at most 32 MB)."""
-    (ai, pi, li), n, chunk_cols, keep = _ce_dist_args(t, a, p, label, chunk_cols, "ce_dist_bwd")
-    d, dr = t.ent.shape[1], t.rel.shape[1]
-    lse = _f32c(lse, t.device)
-    gr = None if g_rows is None else _f32c(g_rows, t.device)
-    if lse.numel() != n or (gr is not None and gr.numel() != n):
-        raise ValueError("kge_amd: ce_dist_bwd: lse and g_rows must have one entry per row")
-    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
-    if n == 0:
-        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
-    g_t = _empty((t.num_ent, d), t.device)
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ce_dist_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_ce_dist_bwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n, lse.data_ptr(),
-            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(),
-            g_t.data_ptr(), ws, wsb, st), "kge_ce_dist_bwd")
-    return g_a, g_p, g_t
-
-
-def ce_f32_supported(t: Tables) -> bool:
-    """Can the fused 1vsAll loss of float32 ComplEx / DistMult tables run (kge_ce_f32_workspace_bytes > 0): float32,
-    dim % 8 == 0, 16-byte aligned rows, on a GPU?"""
-    if not t.ent.is_cuda:
-        return False
-    return _lib.lib().kge_ce_f32_workspace_bytes(ctypes.byref(t.c()), 1, 0) > 0
-
-
-def _ce_f32_args(t: Tables, a, p, label, chunk_cols, what, per_row=()):
-    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths, the
-    lengths of the `per_row` vectors (None: not given)."""
-    chunk_cols = int(chunk_cols)
-    if chunk_cols < 0 or chunk_cols % 128:
-        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 128, got {chunk_cols}")
-    if t.scorer not in (_lib.COMPLEX, _lib.DISTMULT) or t.ent.dtype != torch.float32 or t.rel.dtype != torch.float32:
-        raise RuntimeError(f"kge_amd: {what}: ComplEx / DistMult on float32 tables only "
-                           "(bf16 tables: ce_fwd / ce_bwd; TransE / RotatE: ce_dist_fwd / ce_dist_bwd)")
-    if t.ent.shape[1] % 8:
-        raise RuntimeError(f"kge_amd: {what}: the dimension must be a multiple of 8, got {t.ent.shape[1]}")
-    keep = []
-    ixs = tuple(_index(x, t.device, keep) for x in (a, p, label))
-    n = _same_len(keep[:3], what)
-    if any(x is not None and x.numel() != n for x in per_row):
-        raise ValueError(f"kge_amd: {what}: lse and g_rows must have one entry per row")
-    _require_gpu(t.ent, "entity table")
-    return ixs, n, chunk_cols, keep
-
-
-def _ce_f32_workspace(tc, n, chunk_cols, device, st):
-    """(ptr, bytes): the per-(device, stream) scratch of kge_ce_f32_fwd / _bwd; `bytes` is exactly what the chunk width
-    asks for (the backward derives its chunk width from it), the buffer may be larger."""
-    need = _lib.lib().kge_ce_f32_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
-    if need <= 0:
-        raise RuntimeError("kge_ce_f32_fwd/kge_ce_f32_bwd: float32 ComplEx / DistMult tables, dim % 8 == 0, "
-                           "16-byte aligned rows only")
-    key = (device.index, st, "ce_f32")
-    buf = _WORKSPACES.get(key)
-    if buf is None or buf.numel() < need:
-        buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
-    return buf.data_ptr(), need
-
-
-def ce_f32_fwd(t: Tables, direction: str, a, p, label, chunk_cols: int = 0):
-    """ce_fwd for ComplEx / DistMult on float32 tables (kge_ce_f32_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
-    a = s, label = o) / score_po ('po': a = o, label = s) against all entities, no [n, E] matrix."""
-    (ai, pi, li), n, chunk_cols, keep = _ce_f32_args(t, a, p, label, chunk_cols, "ce_f32_fwd")
-    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
-    if n == 0:
-        return loss_rows, lse
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ce_f32_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_ce_f32_fwd(ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n,
-                                             loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_ce_f32_fwd")
-    return loss_rows, lse
-
-
-def ce_f32_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scalar: float = 1.0, chunk_cols: int = 0):
-    """Backward of ce_f32_fwd (kge_ce_f32_bwd): gradients of sum_i g_i * loss_rows[i] w.r.t. the gathered query rows
-    and all entity rows: (g_a [n, d], g_p [n, d], g_entities [E, d]).  chunk_cols: entity columns per chunk of the
-    backward (a multiple of 128; 0 = the library's default, a gradient chunk of at most 32 MB)."""
-    (ai, pi, li), n, chunk_cols, keep = _ce_f32_args(t, a, p, label, chunk_cols, "ce_f32_bwd", (lse, g_rows))
-    d, dr = t.ent.shape[1], t.rel.shape[1]
-    lse = _f32c(lse, t.device)
-    gr = None if g_rows is None else _f32c(g_rows, t.device)
-    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
-    if n == 0:
-        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
-    g_t = _empty((t.num_ent, d), t.device)
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ce_f32_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_ce_f32_bwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, li, n, lse.data_ptr(),
-            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(),
-            g_t.data_ptr(), ws, wsb, st), "kge_ce_f32_bwd")
-    return g_a, g_p, g_t
-
-
-# ---- KvsAll losses of the distance scorers (kge_kl_dist_* / kge_bce_dist_*): labels as an int64 CSR per row -------------
-def _ml_dist_args(t: Tables, a, p, lbl_rowptr, lbl_col, chunk_cols, what):
-    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths, the CSR."""
-    chunk_cols = int(chunk_cols)
-    if chunk_cols < 0 or chunk_cols % 64:
-        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 64, got {chunk_cols}")
-    if t.scorer not in (_lib.TRANSE, _lib.ROTATE) or t.ent.dtype != torch.float32 or t.l_norm not in (1.0, 2.0):
-        raise RuntimeError(f"kge_amd: {what}: TransE / RotatE on float32 tables with l_norm 1 or 2 only "
-                           "(ComplEx / DistMult on bf16 tables: kl_fwd / bce_fwd)")
-    keep = []
-    ixs = tuple(_index(x, t.device, keep) for x in (a, p))
-    n = _same_len(keep[:2], what)
-    if not torch.is_tensor(lbl_rowptr) or not torch.is_tensor(lbl_col) or lbl_rowptr.dim() != 1 or lbl_col.dim() != 1:
-        raise ValueError(f"kge_amd: {what}: the labels are a CSR of two 1-d tensors (rowptr [n + 1], col [nnz])")
-    if lbl_rowptr.is_floating_point() or lbl_col.is_floating_point():
-        raise TypeError(f"kge_amd: {what}: the label CSR holds integers")
-    if lbl_rowptr.numel() != n + 1:
-        raise ValueError(f"kge_amd: {what}: label rowptr has {lbl_rowptr.numel()} entries for {n} rows")
-    _require_gpu(t.ent, "entity table")
-    rp, cl = _csr64(lbl_rowptr, lbl_col, t.device)
-    return ixs, n, chunk_cols, rp, cl, keep
-
-
-def _ml_dist_rows(x, n, dev, what, name):
-    if x is None:
-        return None
-    x = _f32c(x, dev)
-    if x.numel() != n:
-        raise ValueError(f"kge_amd: {what}: {name} has {x.numel()} entries for {n} rows")
-    return x
-
-
-def _ml_dist_workspace(tc, n, chunk_cols, device, st):
-    """(ptr, bytes): the per-(device, stream) scratch of kge_kl_dist_* / kge_bce_dist_*; `bytes` is exactly what the
-    chunk width asks for (the backward derives its chunk width from it), the buffer may be larger."""
-    need = _lib.lib().kge_multilabel_dist_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
-    if need <= 0:
-        raise RuntimeError("kge_kl_dist_* / kge_bce_dist_*: float32 TransE / RotatE tables with l_norm 1 or 2 only")
-    key = (device.index, st, "ml_dist")
-    buf = _WORKSPACES.get(key)
-    if buf is None or buf.numel() < need:
-        buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
-    return buf.data_ptr(), need
+    """_ce_rows_bwd for TransE / RotatE (kge_ce_dist_bwd)."""
+    return _ce_rows_bwd(_DIST, "ce_dist_bwd", t, direction, a, p, label, lse, g_rows, g_scalar, chunk_cols)
 
 
 def kl_dist_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, label_weight=None, chunk_cols: int = 0):
-    """kl_fwd for TransE / RotatE on float32 tables (kge_kl_dist_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
-    a = s) / score_po ('po': a = o) against all entities with the rows' labels as an int64 CSR (ids in any order), no
-    [n, E] matrix.  label_weight [n]: loss_rows[i] = lse[i] - label_weight[i] * (sum of row i's label scores)."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_dist_fwd")
-    lw = _ml_dist_rows(label_weight, n, t.device, "kl_dist_fwd", "label_weight")
-    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
-    if n == 0:
-        return loss_rows, lse
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_kl_dist_fwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
-            None if lw is None else lw.data_ptr(), loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_kl_dist_fwd")
-    return loss_rows, lse
+    """_kl_rows_fwd for TransE / RotatE (kge_kl_dist_fwd)."""
+    return _kl_rows_fwd(_DIST, "kl_dist_fwd", t, direction, a, p, lbl_rowptr, lbl_col, label_weight, chunk_cols)
 
 
 def kl_dist_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, lse, g_rows=None, g_scalar: float = 1.0,
                 label_weight=None, chunk_cols: int = 0):
-    """Backward of kl_dist_fwd (kge_kl_dist_bwd): (g_a [n, d], g_p [n, d_r], g_entities [E, d]).  chunk_cols: entity
-    columns per chunk (a multiple of 64; 0 = the library's default, a score chunk of at most 32 MB)."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_dist_bwd")
-    d, dr = t.ent.shape[1], t.rel.shape[1]
-    lse = _ml_dist_rows(lse, n, t.device, "kl_dist_bwd", "lse")
-    gr = _ml_dist_rows(g_rows, n, t.device, "kl_dist_bwd", "g_rows")
-    lw = _ml_dist_rows(label_weight, n, t.device, "kl_dist_bwd", "label_weight")
-    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
-    if n == 0:
-        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
-    g_t = _empty((t.num_ent, d), t.device)
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_kl_dist_bwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
-            None if lw is None else lw.data_ptr(), lse.data_ptr(), None if gr is None else gr.data_ptr(),
-            float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(), ws, wsb, st), "kge_kl_dist_bwd")
-    return g_a, g_p, g_t
+    """_kl_rows_bwd for TransE / RotatE (kge_kl_dist_bwd): no label_bias, these scores are not linear in the target."""
+    return _kl_rows_bwd(_DIST, "kl_dist_bwd", t, direction, a, p, lbl_rowptr, lbl_col, lse, g_rows, g_scalar,
+                        label_weight, None, chunk_cols)
 
 
 def bce_dist_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, chunk_cols: int = 0):
-    """bce_fwd for TransE / RotatE on float32 tables (kge_bce_dist_fwd): loss_rows [n], the sum over ALL entities of
-    BCEWithLogits(score + offset, multi-hot labels), no [n, E] matrix."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_dist_fwd")
-    loss_rows = _empty((n,), t.device)
-    if n == 0:
-        return loss_rows
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_bce_dist_fwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
-            loss_rows.data_ptr(), ws, wsb, st), "kge_bce_dist_fwd")
-    return loss_rows
+    """_bce_rows_fwd for TransE / RotatE (kge_bce_dist_fwd)."""
+    return _bce_rows_fwd(_DIST, "bce_dist_fwd", t, direction, a, p, lbl_rowptr, lbl_col, offset, chunk_cols)
 
 
 def bce_dist_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, g_rows=None,
                  g_scalar: float = 1.0, chunk_cols: int = 0):
-    """Backward of bce_dist_fwd (kge_bce_dist_bwd): (g_a [n, d], g_p [n, d_r], g_entities [E, d])."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_dist_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_dist_bwd")
-    d, dr = t.ent.shape[1], t.rel.shape[1]
-    gr = _ml_dist_rows(g_rows, n, t.device, "bce_dist_bwd", "g_rows")
-    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
-    if n == 0:
-        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
-    g_t = _empty((t.num_ent, d), t.device)
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_dist_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_bce_dist_bwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
-            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(),
-            ws, wsb, st), "kge_bce_dist_bwd")
-    return g_a, g_p, g_t
+    """_bce_rows_bwd for TransE / RotatE (kge_bce_dist_bwd)."""
+    return _bce_rows_bwd(_DIST, "bce_dist_bwd", t, direction, a, p, lbl_rowptr, lbl_col, offset, g_rows, g_scalar,
+                         chunk_cols)
 
 
-# ---- KvsAll losses of ComplEx / DistMult on float32 tables (kge_kl_f32_* / kge_bce_f32_*): the CSR of the distance
-# twins above, the tables and chunk widths of ce_f32_fwd / ce_f32_bwd -----------------------------------------------------
+# ... and ComplEx / DistMult on float32 tables with dim % 8 == 0 and 16-byte aligned rows (chunk_cols a multiple of 128)
+def ce_f32_supported(t: Tables) -> bool:
+    """_dense_supported: the 1vsAll loss of float32 ComplEx / DistMult (kge_ce_f32_workspace_bytes > 0)."""
+    return _dense_supported(_F32, "ce", t)
+
+
 def multilabel_f32_supported(t: Tables) -> bool:
-    """Can the fused KvsAll losses of float32 ComplEx / DistMult tables run (kge_multilabel_f32_workspace_bytes > 0):
-    float32, dim % 8 == 0, 16-byte aligned rows, on a GPU?"""
-    if not t.ent.is_cuda:
-        return False
-    return _lib.lib().kge_multilabel_f32_workspace_bytes(ctypes.byref(t.c()), 1, 0) > 0
+    """_dense_supported: the KvsAll losses of float32 ComplEx / DistMult (kge_multilabel_f32_workspace_bytes > 0)."""
+    return _dense_supported(_F32, "ml", t)
 
 
-def _ml_f32_args(t: Tables, a, p, lbl_rowptr, lbl_col, chunk_cols, what, per_row=()):
-    """The checks every device takes, before anything is asked of a GPU: chunk width, tables, index lengths, the CSR,
-    the lengths of the `per_row` vectors ((tensor or None, name) pairs)."""
-    chunk_cols = int(chunk_cols)
-    if chunk_cols < 0 or chunk_cols % 128:
-        raise ValueError(f"kge_amd: {what}: chunk_cols must be 0 (the library's default) or a multiple of 128, got {chunk_cols}")
-    if t.scorer not in (_lib.COMPLEX, _lib.DISTMULT) or t.ent.dtype != torch.float32 or t.rel.dtype != torch.float32:
-        raise RuntimeError(f"kge_amd: {what}: ComplEx / DistMult on float32 tables only "
-                           "(bf16 tables: kl_fwd / bce_fwd; TransE / RotatE: kl_dist_fwd / bce_dist_fwd)")
-    if t.ent.shape[1] % 8:
-        raise RuntimeError(f"kge_amd: {what}: the dimension must be a multiple of 8, got {t.ent.shape[1]}")
-    keep = []
-    ixs = tuple(_index(x, t.device, keep) for x in (a, p))
-    n = _same_len(keep[:2], what)
-    if not torch.is_tensor(lbl_rowptr) or not torch.is_tensor(lbl_col) or lbl_rowptr.dim() != 1 or lbl_col.dim() != 1:
-        raise ValueError(f"kge_amd: {what}: the labels are a CSR of two 1-d tensors (rowptr [n + 1], col [nnz])")
-    if lbl_rowptr.is_floating_point() or lbl_col.is_floating_point():
-        raise TypeError(f"kge_amd: {what}: the label CSR holds integers")
-    if lbl_rowptr.numel() != n + 1:
-        raise ValueError(f"kge_amd: {what}: label rowptr has {lbl_rowptr.numel()} entries for {n} rows")
-    for x, name in per_row:
-        if x is not None and x.numel() != n:
-            raise ValueError(f"kge_amd: {what}: {name} has {x.numel()} entries for {n} rows")
-    _require_gpu(t.ent, "entity table")
-    rp, cl = _csr64(lbl_rowptr, lbl_col, t.device)
-    return ixs, n, chunk_cols, rp, cl, keep
+def ce_f32_fwd(t: Tables, direction: str, a, p, label, chunk_cols: int = 0):
+    """_ce_rows_fwd for float32 ComplEx / DistMult (kge_ce_f32_fwd)."""
+    return _ce_rows_fwd(_F32, "ce_f32_fwd", t, direction, a, p, label, chunk_cols)
 
 
-def _ml_f32_workspace(tc, n, chunk_cols, device, st):
-    """(ptr, bytes): the per-(device, stream) scratch of kge_kl_f32_* / kge_bce_f32_*; `bytes` is exactly what the
-    chunk width asks for (the backward derives its chunk width from it), the buffer may be larger.  The backward leaves
-    the label bits zero and nothing else needs a value: no initialisation."""
-    need = _lib.lib().kge_multilabel_f32_workspace_bytes(ctypes.byref(tc), n, chunk_cols)
-    if need <= 0:
-        raise RuntimeError("kge_kl_f32_* / kge_bce_f32_*: float32 ComplEx / DistMult tables, dim % 8 == 0, "
-                           "16-byte aligned rows only")
-    key = (device.index, st, "ml_f32")
-    buf = _WORKSPACES.get(key)
-    if buf is None or buf.numel() < need:
-        buf = _WORKSPACES[key] = _empty((need,), device, torch.uint8)
-    return buf.data_ptr(), need
+def ce_f32_bwd(t: Tables, direction: str, a, p, label, lse, g_rows=None, g_scalar: float = 1.0, chunk_cols: int = 0):
+    """_ce_rows_bwd for float32 ComplEx / DistMult (kge_ce_f32_bwd)."""
+    return _ce_rows_bwd(_F32, "ce_f32_bwd", t, direction, a, p, label, lse, g_rows, g_scalar, chunk_cols)
 
 
 def kl_f32_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, label_weight=None, chunk_cols: int = 0):
-    """kl_fwd for ComplEx / DistMult on float32 tables (kge_kl_f32_fwd): (loss_rows [n], lse [n]) of score_sp ('sp':
-    a = s) / score_po ('po': a = o) against all entities with the rows' labels as an int64 CSR (ids in any order), no
-    [n, E] matrix.  label_weight [n]: loss_rows[i] = lse[i] - label_weight[i] * (sum of row i's label scores)."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_f32_fwd",
-                                                         ((label_weight, "label_weight"),))
-    lw = _ml_dist_rows(label_weight, n, t.device, "kl_f32_fwd", "label_weight")
-    loss_rows, lse = _empty((n,), t.device), _empty((n,), t.device)
-    if n == 0:
-        return loss_rows, lse
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_kl_f32_fwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
-            None if lw is None else lw.data_ptr(), loss_rows.data_ptr(), lse.data_ptr(), ws, wsb, st), "kge_kl_f32_fwd")
-    return loss_rows, lse
+    """_kl_rows_fwd for float32 ComplEx / DistMult (kge_kl_f32_fwd)."""
+    return _kl_rows_fwd(_F32, "kl_f32_fwd", t, direction, a, p, lbl_rowptr, lbl_col, label_weight, chunk_cols)
 
 
 def kl_f32_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, lse, g_rows=None, g_scalar: float = 1.0,
                label_weight=None, label_bias=None, chunk_cols: int = 0):
-    """Backward of kl_f32_fwd (kge_kl_f32_bwd): (g_a [n, d], g_p [n, d], g_entities [E, d]).  label_bias [n]: b_i is
-    subtracted at every column (the uniform term of smoothed labels: the gradient of loss_rows[i] - b_i sum_j score_ij).
-    chunk_cols: entity columns per chunk (a multiple of 128; 0 = the library's default, a gradient chunk of at most
-    32 MB)."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(
-        t, a, p, lbl_rowptr, lbl_col, chunk_cols, "kl_f32_bwd",
-        ((lse, "lse"), (g_rows, "g_rows"), (label_weight, "label_weight"), (label_bias, "label_bias")))
-    d, dr = t.ent.shape[1], t.rel.shape[1]
-    lse = _ml_dist_rows(lse, n, t.device, "kl_f32_bwd", "lse")
-    gr = _ml_dist_rows(g_rows, n, t.device, "kl_f32_bwd", "g_rows")
-    lw = _ml_dist_rows(label_weight, n, t.device, "kl_f32_bwd", "label_weight")
-    lb = _ml_dist_rows(label_bias, n, t.device, "kl_f32_bwd", "label_bias")
-    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
-    if n == 0:
-        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
-    g_t = _empty((t.num_ent, d), t.device)
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_kl_f32_bwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(),
-            None if lw is None else lw.data_ptr(), None if lb is None else lb.data_ptr(), lse.data_ptr(),
-            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(),
-            ws, wsb, st), "kge_kl_f32_bwd")
-    return g_a, g_p, g_t
+    """_kl_rows_bwd for float32 ComplEx / DistMult (kge_kl_f32_bwd), label_bias included."""
+    return _kl_rows_bwd(_F32, "kl_f32_bwd", t, direction, a, p, lbl_rowptr, lbl_col, lse, g_rows, g_scalar,
+                        label_weight, label_bias, chunk_cols)
 
 
 def bce_f32_fwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, chunk_cols: int = 0):
-    """bce_fwd for ComplEx / DistMult on float32 tables (kge_bce_f32_fwd): loss_rows [n], the sum over ALL entities of
-    BCEWithLogits(score + offset, multi-hot labels), no [n, E] matrix."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_f32_fwd")
-    loss_rows = _empty((n,), t.device)
-    if n == 0:
-        return loss_rows
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_bce_f32_fwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
-            loss_rows.data_ptr(), ws, wsb, st), "kge_bce_f32_fwd")
-    return loss_rows
+    """_bce_rows_fwd for float32 ComplEx / DistMult (kge_bce_f32_fwd)."""
+    return _bce_rows_fwd(_F32, "bce_f32_fwd", t, direction, a, p, lbl_rowptr, lbl_col, offset, chunk_cols)
 
 
 def bce_f32_bwd(t: Tables, direction: str, a, p, lbl_rowptr, lbl_col, offset: float = 0.0, g_rows=None,
                 g_scalar: float = 1.0, chunk_cols: int = 0):
-    """Backward of bce_f32_fwd (kge_bce_f32_bwd): (g_a [n, d], g_p [n, d], g_entities [E, d])."""
-    (ai, pi), n, chunk_cols, rp, cl, keep = _ml_f32_args(t, a, p, lbl_rowptr, lbl_col, chunk_cols, "bce_f32_bwd",
-                                                         ((g_rows, "g_rows"),))
-    d, dr = t.ent.shape[1], t.rel.shape[1]
-    gr = _ml_dist_rows(g_rows, n, t.device, "bce_f32_bwd", "g_rows")
-    g_a, g_p = _empty((n, d), t.device), _empty((n, dr), t.device)
-    if n == 0:
-        return g_a, g_p, torch.zeros((t.num_ent, d), device=t.device)
-    g_t = _empty((t.num_ent, d), t.device)
-    with _on_device(t.device):
-        tc = t.c()
-        st = _stream_handle(t.device)
-        ws, wsb = _ml_f32_workspace(tc, n, chunk_cols, t.device, st)
-        _lib.check(_lib.lib().kge_bce_f32_bwd(
-            ctypes.byref(tc), SP_ if direction == "sp" else PO_, ai, pi, n, rp.data_ptr(), cl.data_ptr(), float(offset),
-            None if gr is None else gr.data_ptr(), float(g_scalar), g_a.data_ptr(), g_p.data_ptr(), g_t.data_ptr(),
-            ws, wsb, st), "kge_bce_f32_bwd")
-    return g_a, g_p, g_t
+    """_bce_rows_bwd for float32 ComplEx / DistMult (kge_bce_f32_bwd)."""
+    return _bce_rows_bwd(_F32, "bce_f32_bwd", t, direction, a, p, lbl_rowptr, lbl_col, offset, g_rows, g_scalar,
+                         chunk_cols)
 
 
 def ce_emb_fwd(t: Tables, direction: str, a_rows, p_rows, label):

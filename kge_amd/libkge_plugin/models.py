@@ -17,10 +17,9 @@ from kge.model.transh import TransHScorer as _RefTransHScorer
 from kge.model.transh import transh_set_relation_embedder_dim
 
 from .. import engine
-from ..model import (BF16Shadow, _FusedBCEDist, _FusedBCEF32, _FusedCE, _FusedCE2, _FusedCE2Sum, _FusedCEDist, _FusedCEF32,
-                     _FusedKLDist, _FusedKLF32, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared, _ScorePairs, _ScoreSPO,
-                     ConveNetOps, ConveRoutes, Tucker3Routes, bce_fused, ce_fused_dropout, kl_fused, neg_blocks_fusable, neg_shared_fusable,
-                     predict_filters, topk_composed)
+from ..model import (BF16Shadow, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared,
+                     _ScorePairs, _ScoreSPO, ConveNetOps, ConveRoutes, Tucker3Routes, ce_fused_dropout, fused_loss_rows,
+                     neg_blocks_fusable, neg_shared_fusable, predict_filters, topk_composed)
 
 
 class _HipScorer(RelationalScorer):
@@ -321,11 +320,6 @@ class _FusedScoring:
     # label smoothing (kge_kl_dist_* / kge_bce_dist_*); also the bce loss under hip_1vsAll.
     _fused_dist_loss = False
 
-    def _ml_dist_tables(self, label_smoothing):
-        """_ce_dist_tables() for a multi-label loss, None under label smoothing (its uniform term is not linear in the
-        table for a distance scorer: the composed path)."""
-        return self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
-
     def _ce_dist_tables(self):
         """float32 tables for the distance scorers' fused loss, or None (the composed path): the option on, TransE /
         RotatE with l_norm 1 or 2, `_fused()` (plain lookup embedders, no active dropout, parameters on a GPU)."""
@@ -355,33 +349,6 @@ class _FusedScoring:
         t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
         return t if engine.ce_f32_supported(t) else None
 
-    def _loss_one_sided(self, direction, a, p, label):
-        """loss_sp / loss_po where neither _ce_tables() nor _dropout_only() applies: the float32 fused losses, or None."""
-        td = self._ce_dist_tables()
-        if td is not None:
-            return _FusedCEDist.apply(direction, *self._w(), a, p, label, td)
-        tf = self._ce_f32_tables()
-        return None if tf is None else _FusedCEF32.apply(direction, *self._w(), a, p, label, tf)
-
-    def _kl_f32(self, direction, a, p, lbl_rowptr, lbl_col, label_smoothing):
-        """kl_loss_sp / kl_loss_po where neither _ce_tables() nor _ml_dist_tables() applies: the float32 ComplEx /
-        DistMult loss (kl_fused around _FusedKLF32: label smoothing included), or None."""
-        tf = self._ce_f32_tables()
-        if tf is None:
-            return None
-        ent, rel = self._w()
-        return kl_fused(self._scorer.name, self._scorer._norm, direction, ent, rel, a, p, lbl_rowptr, lbl_col,
-                        float(label_smoothing), tf, _FusedKLF32)
-
-    def _bce_f32(self, direction, a, p, lbl_rowptr, lbl_col, offset, label_smoothing):
-        """The same for bce_loss_sp / bce_loss_po (bce_fused around _FusedBCEF32), or None."""
-        tf = self._ce_f32_tables()
-        if tf is None:
-            return None
-        ent, rel = self._w()
-        return bce_fused(self._scorer.name, self._scorer._norm, direction, ent, rel, a, p, lbl_rowptr, lbl_col,
-                         float(offset), float(label_smoothing), tf, _FusedBCEF32)
-
     def _rank_tables(self):
         """The tables HipEntityRankingJob counts on (kge_score_rank_sp_po: scoring + _filter_and_rank counts in one
         kernel) -- the ones score_sp_po scores on under no_grad, so that fused and two-step counts agree bit for bit:
@@ -392,26 +359,27 @@ class _FusedScoring:
         ent, rel = self._w()
         return self._fwd_tables() or engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
 
+    def _fused_rows(self, kind: str, direction: str, a: Tensor, p: Tensor, labels: tuple, eps: float = 0.0, bf16=None):
+        """kge_amd.model.fused_loss_rows on this model's tables ("sp": a = s; "po": a = o): the loss rows, or None if no
+        fused path applies."""
+        scorer = self._scorer  # (one Module.__getattr__, not two)
+        return fused_loss_rows(kind, direction, scorer.name, scorer._norm, self._w, a, p, labels, eps,
+                               bf16 or self._ce_tables, self._ce_dist_tables, self._ce_f32_tables)
+
+    def _ce_rows(self, direction: str, a: Tensor, p: Tensor, label: Tensor):
+        t = self._ce_tables()
+        dp = self._dropout_only() if t is None else None
+        if dp is not None:  # embedder dropout in training: the masks applied here, the fused kernels on dense rows
+            ent, rel = self._w()
+            return ce_fused_dropout(self._scorer.name, self._scorer._norm, direction, ent, rel, a, p, label, dp[0], dp[1])
+        return self._fused_rows("ce", direction, a, p, (label,), bf16=lambda: t)
+
     def loss_sp(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
         """[n] cross entropy of score_sp(s, p) against o; None if the fused path does not apply."""
-        t = self._ce_tables()
-        dp = self._dropout_only() if t is None else None
-        if t is None and dp is None:
-            return self._loss_one_sided("sp", s, p, o)
-        ent, rel = self._w()
-        if dp is not None:  # embedder dropout in training: the masks applied here, the fused kernels on dense rows
-            return ce_fused_dropout(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, o, dp[0], dp[1])
-        return _FusedCE.apply("sp", ent, rel, s, p, o, t)
+        return self._ce_rows("sp", s, p, o)
 
     def loss_po(self, p: Tensor, o: Tensor, s: Tensor) -> Tensor:
-        t = self._ce_tables()
-        dp = self._dropout_only() if t is None else None
-        if t is None and dp is None:
-            return self._loss_one_sided("po", o, p, s)
-        ent, rel = self._w()
-        if dp is not None:  # embedder dropout in training: the masks applied here, the fused kernels on dense rows
-            return ce_fused_dropout(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, s, dp[0], dp[1])
-        return _FusedCE.apply("po", ent, rel, o, p, s, t)
+        return self._ce_rows("po", o, p, s)
 
     def loss_sp_po(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
         """[2n] loss_sp rows then loss_po rows from one pass over the batch; None if not applicable."""
@@ -443,53 +411,21 @@ class _FusedScoring:
         """[n] KL divergence of softmax(score_sp(s, p)) from the rows' normalised (and, with
         `label_smoothing`, smoothed: train_KvsAll.py:260-266) multi-hot labels (int64 CSR); None if the
         fused path does not apply (HipTrainingJobKvsAll; kge_kl_fwd / kge_kl_weighted_fwd)."""
-        t = self._ce_tables()
-        if t is None:
-            td = self._ml_dist_tables(label_smoothing)
-            if td is not None:
-                return _FusedKLDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, None, td)
-            return self._kl_f32("sp", s, p, lbl_rowptr, lbl_col, label_smoothing)
-        ent, rel = self._w()
-        return kl_fused(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, lbl_rowptr, lbl_col,
-                        float(label_smoothing), t)
+        return self._fused_rows("kl", "sp", s, p, (lbl_rowptr, lbl_col), float(label_smoothing))
 
     def kl_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
                    label_smoothing: float = 0.0) -> Tensor:
-        t = self._ce_tables()
-        if t is None:
-            td = self._ml_dist_tables(label_smoothing)
-            if td is not None:
-                return _FusedKLDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, None, td)
-            return self._kl_f32("po", o, p, lbl_rowptr, lbl_col, label_smoothing)
-        ent, rel = self._w()
-        return kl_fused(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, lbl_rowptr, lbl_col,
-                        float(label_smoothing), t)
+        return self._fused_rows("kl", "po", o, p, (lbl_rowptr, lbl_col), float(label_smoothing))
 
     def bce_loss_sp(self, s: Tensor, p: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor, offset: float = 0.0,
                     label_smoothing: float = 0.0):
         """[n] sum over all entities of BCEWithLogits(score_sp(s, p) + offset, (smoothed) multi-hot labels);
         None if the fused path does not apply (kge_bce_fwd)."""
-        t = self._ce_tables()
-        if t is None:
-            td = self._ml_dist_tables(label_smoothing)
-            if td is not None:
-                return _FusedBCEDist.apply("sp", *self._w(), s, p, lbl_rowptr, lbl_col, float(offset), td)
-            return self._bce_f32("sp", s, p, lbl_rowptr, lbl_col, offset, label_smoothing)
-        ent, rel = self._w()
-        return bce_fused(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, lbl_rowptr, lbl_col,
-                         float(offset), float(label_smoothing), t)
+        return self._fused_rows("bce", "sp", s, p, (lbl_rowptr, lbl_col, float(offset)), float(label_smoothing))
 
     def bce_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor, offset: float = 0.0,
                     label_smoothing: float = 0.0):
-        t = self._ce_tables()
-        if t is None:
-            td = self._ml_dist_tables(label_smoothing)
-            if td is not None:
-                return _FusedBCEDist.apply("po", *self._w(), o, p, lbl_rowptr, lbl_col, float(offset), td)
-            return self._bce_f32("po", o, p, lbl_rowptr, lbl_col, offset, label_smoothing)
-        ent, rel = self._w()
-        return bce_fused(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, lbl_rowptr, lbl_col,
-                         float(offset), float(label_smoothing), t)
+        return self._fused_rows("bce", "po", o, p, (lbl_rowptr, lbl_col, float(offset)), float(label_smoothing))
 
     def multilabel_loss_sp_po(self, kind: str, s: Tensor, p_sp: Tensor, rowptr_sp: Tensor, col_sp: Tensor, o: Tensor,
                               p_po: Tensor, rowptr_po: Tensor, col_po: Tensor, offset: float = 0.0,

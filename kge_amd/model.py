@@ -396,19 +396,38 @@ class KgeModel(torch.nn.Module):
         t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach())
         return t if engine.ce_f32_supported(t) else None
 
+    # one method per loss, the direction an argument ("sp": a = s; "po": a = o): the fused rows where a family of
+    # fused_loss_rows applies, else composed from the scores
+    def _weights(self):
+        return self._entity_embedder.weight, self._relation_embedder.weight
+
+    def _fused_rows(self, kind: str, direction: str, a: Tensor, p: Tensor, labels: tuple, eps: float = 0.0):
+        scorer = self._scorer  # (one Module.__getattr__, not two)
+        return fused_loss_rows(kind, direction, scorer.name, scorer._norm, self._weights, a, p, labels, eps,
+                               self._ce_tables, self._ce_dist_tables, self._ce_f32_tables)
+
+    def _scores(self, direction: str, a: Tensor, p: Tensor) -> Tensor:
+        return self.score_sp(a, p) if direction == "sp" else self.score_po(p, a)
+
+    def _ce_rows(self, direction: str, a: Tensor, p: Tensor, label: Tensor) -> Tensor:
+        rows = self._fused_rows("ce", direction, a, p, (label,))
+        if rows is None:
+            rows = torch.nn.functional.cross_entropy(self._scores(direction, a, p), label.long(), reduction="none")
+        return rows
+
+    def _kl_rows(self, direction: str, a: Tensor, p: Tensor, rowptr: Tensor, col: Tensor, eps: float) -> Tensor:
+        rows = self._fused_rows("kl", direction, a, p, (rowptr, col), float(eps))
+        return self._kl_composed(self._scores(direction, a, p), rowptr, col, eps) if rows is None else rows
+
+    def _bce_rows(self, direction: str, a: Tensor, p: Tensor, rowptr: Tensor, col: Tensor, offset: float,
+                  eps: float) -> Tensor:
+        rows = self._fused_rows("bce", direction, a, p, (rowptr, col, float(offset)), float(eps))
+        return self._bce_composed(self._scores(direction, a, p), rowptr, col, offset, eps) if rows is None else rows
+
     def loss_sp(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
         """Per-row cross entropy of score_sp(s, p) against the true objects o ([n]); its sum is the
         reference's `self.loss(scores_sp, triples[:, 2])` with train.loss=kl (loss.py:192-207)."""
-        t = self._ce_tables()
-        if t is not None:
-            return _FusedCE.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, t)
-        td = self._ce_dist_tables()
-        if td is not None:
-            return _FusedCEDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, td)
-        tf = self._ce_f32_tables()
-        if tf is not None:
-            return _FusedCEF32.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, tf)
-        return torch.nn.functional.cross_entropy(self.score_sp(s, p), o.long(), reduction="none")
+        return self._ce_rows("sp", s, p, o)
 
     def loss_sp_po(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
         """[2n]: loss_sp(s, p, o) followed by loss_po(p, o, s) -- both directions of a 1vsAll batch
@@ -432,16 +451,7 @@ class KgeModel(torch.nn.Module):
 
     def loss_po(self, p: Tensor, o: Tensor, s: Tensor) -> Tensor:
         """Per-row cross entropy of score_po(p, o) against the true subjects s."""
-        t = self._ce_tables()
-        if t is not None:
-            return _FusedCE.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p, s, t)
-        td = self._ce_dist_tables()
-        if td is not None:
-            return _FusedCEDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p, s, td)
-        tf = self._ce_f32_tables()
-        if tf is not None:
-            return _FusedCEF32.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p, s, tf)
-        return torch.nn.functional.cross_entropy(self.score_po(p, o), s.long(), reduction="none")
+        return self._ce_rows("po", o, p, s)
 
     # -- KvsAll loss: train_KvsAll.py:274-294 with train.loss=kl
     @staticmethod
@@ -458,40 +468,15 @@ class KgeModel(torch.nn.Module):
         y = torch.nn.functional.normalize(labels, p=1, dim=1)
         return torch.nn.functional.kl_div(torch.log_softmax(scores, dim=1), y, reduction="none").sum(dim=1)
 
-    def _kl_fused(self, direction: str, a: Tensor, p: Tensor, rowptr: Tensor, col: Tensor, eps: float, t,
-                  fused_fn=None) -> Tensor:
-        return kl_fused(self._scorer.name, self._scorer._norm, direction, self._entity_embedder.weight,
-                        self._relation_embedder.weight, a, p, rowptr, col, eps, t, fused_fn)
-
     def kl_loss_sp(self, s: Tensor, p: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
                    label_smoothing: float = 0.0) -> Tensor:
         """Per-row KL divergence of softmax(score_sp(s, p)) from the normalised multi-hot labels
         given as an int64 CSR over the rows (the known objects of each (s, p) query)."""
-        t = self._ce_tables()
-        if t is not None:
-            return self._kl_fused("sp", s, p, lbl_rowptr, lbl_col, float(label_smoothing), t)
-        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
-        if td is not None:
-            return _FusedKLDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p,
-                                      lbl_rowptr, lbl_col, None, td)
-        tf = self._ce_f32_tables()
-        if tf is not None:
-            return self._kl_fused("sp", s, p, lbl_rowptr, lbl_col, float(label_smoothing), tf, _FusedKLF32)
-        return self._kl_composed(self.score_sp(s, p), lbl_rowptr, lbl_col, label_smoothing)
+        return self._kl_rows("sp", s, p, lbl_rowptr, lbl_col, label_smoothing)
 
     def kl_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
                    label_smoothing: float = 0.0) -> Tensor:
-        t = self._ce_tables()
-        if t is not None:
-            return self._kl_fused("po", o, p, lbl_rowptr, lbl_col, float(label_smoothing), t)
-        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
-        if td is not None:
-            return _FusedKLDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p,
-                                      lbl_rowptr, lbl_col, None, td)
-        tf = self._ce_f32_tables()
-        if tf is not None:
-            return self._kl_fused("po", o, p, lbl_rowptr, lbl_col, float(label_smoothing), tf, _FusedKLF32)
-        return self._kl_composed(self.score_po(p, o), lbl_rowptr, lbl_col, label_smoothing)
+        return self._kl_rows("po", o, p, lbl_rowptr, lbl_col, label_smoothing)
 
     def multilabel_loss_sp_po(self, kind: str, s: Tensor, p_sp: Tensor, rowptr_sp: Tensor, col_sp: Tensor, o: Tensor,
                               p_po: Tensor, rowptr_po: Tensor, col_po: Tensor, offset: float = 0.0,
@@ -529,39 +514,11 @@ class KgeModel(torch.nn.Module):
     def bce_loss_sp(self, s: Tensor, p: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor, offset: float = 0.0,
                     label_smoothing: float = 0.0) -> Tensor:
         """Per-row sum over all entities of BCEWithLogits(score_sp(s, p) + offset, multi-hot labels)."""
-        t = self._ce_tables()
-        if t is not None:
-            return bce_fused(self._scorer.name, self._scorer._norm, "sp", self._entity_embedder.weight,
-                             self._relation_embedder.weight, s, p, lbl_rowptr, lbl_col, float(offset),
-                             float(label_smoothing), t)
-        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
-        if td is not None:
-            return _FusedBCEDist.apply("sp", self._entity_embedder.weight, self._relation_embedder.weight, s, p,
-                                       lbl_rowptr, lbl_col, float(offset), td)
-        tf = self._ce_f32_tables()
-        if tf is not None:
-            return bce_fused(self._scorer.name, self._scorer._norm, "sp", self._entity_embedder.weight,
-                             self._relation_embedder.weight, s, p, lbl_rowptr, lbl_col, float(offset),
-                             float(label_smoothing), tf, _FusedBCEF32)
-        return self._bce_composed(self.score_sp(s, p), lbl_rowptr, lbl_col, offset, label_smoothing)
+        return self._bce_rows("sp", s, p, lbl_rowptr, lbl_col, offset, label_smoothing)
 
     def bce_loss_po(self, p: Tensor, o: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor, offset: float = 0.0,
                     label_smoothing: float = 0.0) -> Tensor:
-        t = self._ce_tables()
-        if t is not None:
-            return bce_fused(self._scorer.name, self._scorer._norm, "po", self._entity_embedder.weight,
-                             self._relation_embedder.weight, o, p, lbl_rowptr, lbl_col, float(offset),
-                             float(label_smoothing), t)
-        td = self._ce_dist_tables() if float(label_smoothing) == 0.0 else None
-        if td is not None:
-            return _FusedBCEDist.apply("po", self._entity_embedder.weight, self._relation_embedder.weight, o, p,
-                                       lbl_rowptr, lbl_col, float(offset), td)
-        tf = self._ce_f32_tables()
-        if tf is not None:
-            return bce_fused(self._scorer.name, self._scorer._norm, "po", self._entity_embedder.weight,
-                             self._relation_embedder.weight, o, p, lbl_rowptr, lbl_col, float(offset),
-                             float(label_smoothing), tf, _FusedBCEF32)
-        return self._bce_composed(self.score_po(p, o), lbl_rowptr, lbl_col, offset, label_smoothing)
+        return self._bce_rows("po", o, p, lbl_rowptr, lbl_col, offset, label_smoothing)
 
     def score_so(self, s: Tensor, o: Tensor, p: Tensor = None) -> Tensor:
         se, oe = self._entity_embedder.embed(s), self._entity_embedder.embed(o)
@@ -1372,172 +1329,117 @@ class _ScorePairs(torch.autograd.Function):
         return None, None, None, ge, gr, None, None, None, None, None, None
 
 
-class _FusedCE(torch.autograd.Function):
-    """Per-row 1vsAll cross entropy fused with the sp_/_po scoring (kge_ce_fwd / kge_ce_bwd):
-    `tables16` are the bf16 tables the scores come from (the parameters themselves, or their
-    bf16 copies in mixed precision); gradients go to `ent` / `rel`."""
+class _LossRows(torch.autograd.Function):
+    """What the nine one-sided loss nodes below share: per-row loss fused with the sp_ / _po scoring against all entities
+    -- 1vsAll cross entropy, KvsAll KL, KvsAll BCE (labels as an int64 CSR: rowptr [n + 1], col [nnz], ids in any order)
+    -- on one of three kinds of tables (bf16: `tables16`, the parameters or their bf16 copies in mixed precision;
+    TransE / RotatE on float32; ComplEx / DistMult on float32: `tables`, the parameters themselves, the backward walking
+    the entity columns in chunks of `chunk_cols`, 0 = the library's default).  Gradients go to `ent` / `rel`.  A node's
+    forward names its inputs (its `apply` signature) and hands them to `rows` with its pair of engine functions."""
+
+    @staticmethod
+    def rows(ctx, fwd, bwd, tables, direction, rel, idx, tail=(), **bwd_kw):
+        """The loss rows of fwd(tables, direction, *idx, *tail), which returns them alone or with the rows' lse; the
+        backward calls bwd(tables, direction, *idx, [lse,] g_rows=.., **bwd_kw).  idx[0] / idx[1]: the query rows' entity
+        and relation ids."""
+        out = fwd(tables, direction, *idx, *tail)
+        ctx.call, ctx.rel_shape = (bwd, tables, direction, idx, bwd_kw), rel.shape
+        if isinstance(out, tuple):
+            out, lse = out
+            ctx.save_for_backward(lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        bwd, tables, direction, idx, bwd_kw = ctx.call
+        g_a, g_p, ge = bwd(tables, direction, *idx, *ctx.saved_tensors, g_rows=g_rows.contiguous(), **bwd_kw)
+        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
+        _scatter_rows(gr, idx[1], g_p)
+        _scatter_rows(ge, idx[0], g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
+        return (None, ge, gr) + (None,) * (len(ctx.needs_input_grad) - 3)  # (direction, ent, rel, the other inputs)
+
+
+class _FusedCE(_LossRows):
+    """1vsAll cross entropy on bf16 tables (kge_ce_fwd / kge_ce_bwd)."""
 
     @staticmethod
     def forward(ctx, direction, ent, rel, a, p, label, tables16):
-        loss_rows, lse = engine.ce_fwd(tables16, direction, a, p, label)
-        ctx.t16, ctx.direction, ctx.idx = tables16, direction, (a, p, label)
-        ctx.rel_shape = rel.shape
-        ctx.save_for_backward(lse)
-        return loss_rows
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, p, label = ctx.idx
-        (lse,) = ctx.saved_tensors
-        g_a, g_p, ge = engine.ce_bwd(ctx.t16, ctx.direction, a, p, label, lse, g_rows=g_rows.contiguous())
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
-        return None, ge, gr, None, None, None, None
+        return _LossRows.rows(ctx, engine.ce_fwd, engine.ce_bwd, tables16, direction, rel, (a, p, label))
 
 
-class _FusedCEDist(torch.autograd.Function):
-    """_FusedCE for TransE / RotatE on float32 tables (kge_ce_dist_fwd / kge_ce_dist_bwd): `tables` are the
-    parameters themselves; the backward walks the entity columns in chunks of `chunk_cols` (0: the library's default)."""
+class _FusedCEDist(_LossRows):
+    """_FusedCE for TransE / RotatE on float32 tables (kge_ce_dist_fwd / kge_ce_dist_bwd)."""
 
     @staticmethod
     def forward(ctx, direction, ent, rel, a, p, label, tables, chunk_cols=0):
-        loss_rows, lse = engine.ce_dist_fwd(tables, direction, a, p, label, chunk_cols)
-        ctx.t, ctx.direction, ctx.idx, ctx.chunk_cols = tables, direction, (a, p, label), chunk_cols
-        ctx.rel_shape = rel.shape
-        ctx.save_for_backward(lse)
-        return loss_rows
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, p, label = ctx.idx
-        (lse,) = ctx.saved_tensors
-        g_a, g_p, ge = engine.ce_dist_bwd(ctx.t, ctx.direction, a, p, label, lse, g_rows=g_rows.contiguous(),
-                                          chunk_cols=ctx.chunk_cols)
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
-        return None, ge, gr, None, None, None, None, None
+        return _LossRows.rows(ctx, engine.ce_dist_fwd, engine.ce_dist_bwd, tables, direction, rel, (a, p, label),
+                              (chunk_cols,), chunk_cols=chunk_cols)
 
 
-class _FusedCEF32(torch.autograd.Function):
-    """_FusedCE for ComplEx / DistMult on FLOAT32 tables (kge_ce_f32_fwd / kge_ce_f32_bwd): `tables` are the parameters
-    themselves; the backward walks the entity columns in chunks of `chunk_cols` (0: the library's default)."""
+class _FusedCEF32(_LossRows):
+    """_FusedCE for ComplEx / DistMult on FLOAT32 tables (kge_ce_f32_fwd / kge_ce_f32_bwd)."""
 
     @staticmethod
     def forward(ctx, direction, ent, rel, a, p, label, tables, chunk_cols=0):
-        loss_rows, lse = engine.ce_f32_fwd(tables, direction, a, p, label, chunk_cols)
-        ctx.t, ctx.direction, ctx.idx, ctx.chunk_cols = tables, direction, (a, p, label), chunk_cols
-        ctx.rel_shape = rel.shape
-        ctx.save_for_backward(lse)
-        return loss_rows
+        return _LossRows.rows(ctx, engine.ce_f32_fwd, engine.ce_f32_bwd, tables, direction, rel, (a, p, label),
+                              (chunk_cols,), chunk_cols=chunk_cols)
+
+
+class _FusedKL(_LossRows):
+    """KvsAll KL loss on bf16 tables (kge_kl_fwd / kge_kl_bwd).  label_weight / label_bias [n] or None: the two terms of
+    smoothed labels (kl_fused composes label smoothing around this node or _FusedKLF32; label_bias, the uniform term,
+    is taken inside the gradient kernel -- these scores are linear in the target row)."""
 
     @staticmethod
-    def backward(ctx, g_rows):
-        a, p, label = ctx.idx
-        (lse,) = ctx.saved_tensors
-        g_a, g_p, ge = engine.ce_f32_bwd(ctx.t, ctx.direction, a, p, label, lse, g_rows=g_rows.contiguous(),
-                                         chunk_cols=ctx.chunk_cols)
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
-        return None, ge, gr, None, None, None, None, None
+    def forward(ctx, direction, ent, rel, a, p, rowptr, col, label_weight, label_bias, tables16):
+        return _LossRows.rows(ctx, engine.kl_fwd, engine.kl_bwd, tables16, direction, rel, (a, p, rowptr, col),
+                              (label_weight,), label_weight=label_weight, label_bias=label_bias)
 
 
-class _FusedKLDist(torch.autograd.Function):
-    """_FusedKL for TransE / RotatE on float32 tables (kge_kl_dist_fwd / kge_kl_dist_bwd): `tables` are the parameters
-    themselves, labels an int64 CSR (rowptr [n + 1], col [nnz]; ids in any order); no label-smoothing bias.  The
-    backward walks the entity columns in chunks of `chunk_cols` (0: the library's default)."""
+class _FusedKLDist(_LossRows):
+    """_FusedKL for TransE / RotatE on float32 tables (kge_kl_dist_fwd / kge_kl_dist_bwd); no label-smoothing bias."""
 
     @staticmethod
     def forward(ctx, direction, ent, rel, a, p, rowptr, col, label_weight, tables, chunk_cols=0):
-        loss_rows, lse = engine.kl_dist_fwd(tables, direction, a, p, rowptr, col, label_weight, chunk_cols)
-        ctx.t, ctx.direction, ctx.idx, ctx.chunk_cols = tables, direction, (a, p, rowptr, col, label_weight), chunk_cols
-        ctx.rel_shape = rel.shape
-        ctx.save_for_backward(lse)
-        return loss_rows
+        return _LossRows.rows(ctx, engine.kl_dist_fwd, engine.kl_dist_bwd, tables, direction, rel, (a, p, rowptr, col),
+                              (label_weight, chunk_cols), label_weight=label_weight, chunk_cols=chunk_cols)
+
+
+class _FusedKLF32(_LossRows):
+    """_FusedKL for ComplEx / DistMult on FLOAT32 tables (kge_kl_f32_fwd / kge_kl_f32_bwd); _FusedKL's signature."""
 
     @staticmethod
-    def backward(ctx, g_rows):
-        a, p, rowptr, col, label_weight = ctx.idx
-        (lse,) = ctx.saved_tensors
-        g_a, g_p, ge = engine.kl_dist_bwd(ctx.t, ctx.direction, a, p, rowptr, col, lse, g_rows=g_rows.contiguous(),
-                                          label_weight=label_weight, chunk_cols=ctx.chunk_cols)
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
-        return None, ge, gr, None, None, None, None, None, None, None
+    def forward(ctx, direction, ent, rel, a, p, rowptr, col, label_weight, label_bias, tables, chunk_cols=0):
+        return _LossRows.rows(ctx, engine.kl_f32_fwd, engine.kl_f32_bwd, tables, direction, rel, (a, p, rowptr, col),
+                              (label_weight, chunk_cols), label_weight=label_weight, label_bias=label_bias,
+                              chunk_cols=chunk_cols)
 
 
-class _FusedBCEDist(torch.autograd.Function):
+class _FusedBCE(_LossRows):
+    """KvsAll BCE-with-logits, summed over all entities, on bf16 tables (kge_bce_fwd / kge_bce_bwd); bce_fused composes
+    label smoothing around this node or _FusedBCEF32."""
+
+    @staticmethod
+    def forward(ctx, direction, ent, rel, a, p, rowptr, col, offset, tables16):
+        return _LossRows.rows(ctx, engine.bce_fwd, engine.bce_bwd, tables16, direction, rel, (a, p, rowptr, col, offset))
+
+
+class _FusedBCEDist(_LossRows):
     """_FusedBCE for TransE / RotatE on float32 tables (kge_bce_dist_fwd / kge_bce_dist_bwd)."""
 
     @staticmethod
     def forward(ctx, direction, ent, rel, a, p, rowptr, col, offset, tables, chunk_cols=0):
-        loss_rows = engine.bce_dist_fwd(tables, direction, a, p, rowptr, col, offset, chunk_cols)
-        ctx.t, ctx.direction, ctx.idx, ctx.offset, ctx.chunk_cols = tables, direction, (a, p, rowptr, col), offset, chunk_cols
-        ctx.rel_shape = rel.shape
-        return loss_rows
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, p, rowptr, col = ctx.idx
-        g_a, g_p, ge = engine.bce_dist_bwd(ctx.t, ctx.direction, a, p, rowptr, col, ctx.offset,
-                                           g_rows=g_rows.contiguous(), chunk_cols=ctx.chunk_cols)
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)
-        return None, ge, gr, None, None, None, None, None, None, None
+        return _LossRows.rows(ctx, engine.bce_dist_fwd, engine.bce_dist_bwd, tables, direction, rel,
+                              (a, p, rowptr, col, offset), (chunk_cols,), chunk_cols=chunk_cols)
 
 
-class _FusedKLF32(torch.autograd.Function):
-    """_FusedKL for ComplEx / DistMult on FLOAT32 tables (kge_kl_f32_fwd / kge_kl_f32_bwd): `tables` are the parameters
-    themselves, labels an int64 CSR (rowptr [n + 1], col [nnz]; ids in any order).  _FusedKL's signature -- these scores
-    are linear in the target row, so label_bias (the uniform term of smoothed labels) is taken inside the gradient
-    kernel as there: kl_fused composes label smoothing around either.  The backward walks the entity columns in chunks
-    of `chunk_cols` (0: the library's default)."""
-
-    @staticmethod
-    def forward(ctx, direction, ent, rel, a, p, rowptr, col, label_weight, label_bias, tables, chunk_cols=0):
-        loss_rows, lse = engine.kl_f32_fwd(tables, direction, a, p, rowptr, col, label_weight, chunk_cols)
-        ctx.t, ctx.direction, ctx.chunk_cols = tables, direction, chunk_cols
-        ctx.idx = (a, p, rowptr, col, label_weight, label_bias)
-        ctx.rel_shape = rel.shape
-        ctx.save_for_backward(lse)
-        return loss_rows
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, p, rowptr, col, label_weight, label_bias = ctx.idx
-        (lse,) = ctx.saved_tensors
-        g_a, g_p, ge = engine.kl_f32_bwd(ctx.t, ctx.direction, a, p, rowptr, col, lse, g_rows=g_rows.contiguous(),
-                                         label_weight=label_weight, label_bias=label_bias, chunk_cols=ctx.chunk_cols)
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)  # ge [E, d] is fresh: the dense target gradient + the query rows
-        return None, ge, gr, None, None, None, None, None, None, None, None
-
-
-class _FusedBCEF32(torch.autograd.Function):
-    """_FusedBCE for ComplEx / DistMult on FLOAT32 tables (kge_bce_f32_fwd / kge_bce_f32_bwd); _FusedBCE's signature
-    (bce_fused composes label smoothing around either)."""
+class _FusedBCEF32(_LossRows):
+    """_FusedBCE for ComplEx / DistMult on FLOAT32 tables (kge_bce_f32_fwd / kge_bce_f32_bwd); _FusedBCE's signature."""
 
     @staticmethod
     def forward(ctx, direction, ent, rel, a, p, rowptr, col, offset, tables, chunk_cols=0):
-        loss_rows = engine.bce_f32_fwd(tables, direction, a, p, rowptr, col, offset, chunk_cols)
-        ctx.t, ctx.direction, ctx.idx, ctx.offset, ctx.chunk_cols = tables, direction, (a, p, rowptr, col), offset, chunk_cols
-        ctx.rel_shape = rel.shape
-        return loss_rows
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, p, rowptr, col = ctx.idx
-        g_a, g_p, ge = engine.bce_f32_bwd(ctx.t, ctx.direction, a, p, rowptr, col, ctx.offset,
-                                          g_rows=g_rows.contiguous(), chunk_cols=ctx.chunk_cols)
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)
-        return None, ge, gr, None, None, None, None, None, None, None
+        return _LossRows.rows(ctx, engine.bce_f32_fwd, engine.bce_f32_bwd, tables, direction, rel,
+                              (a, p, rowptr, col, offset), (chunk_cols,), chunk_cols=chunk_cols)
 
 
 class _FusedCE2(torch.autograd.Function):
@@ -1642,30 +1544,6 @@ def ce_fused_dropout(scorer: str, l_norm: float, direction: str, ent: Tensor, re
     return _FusedCEEmb.apply(scorer, l_norm, direction, table, a_rows, p_rows, label)
 
 
-class _FusedKL(torch.autograd.Function):
-    """Per-row KvsAll KL loss fused with the sp_/_po scoring (kge_kl_fwd / kge_kl_bwd); labels as an
-    int64 CSR (rowptr [n + 1], col [nnz]) of the rows' known answers."""
-
-    @staticmethod
-    def forward(ctx, direction, ent, rel, a, p, rowptr, col, label_weight, label_bias, tables16):
-        loss_rows, lse = engine.kl_fwd(tables16, direction, a, p, rowptr, col, label_weight)
-        ctx.t16, ctx.direction, ctx.idx = tables16, direction, (a, p, rowptr, col, label_weight, label_bias)
-        ctx.rel_shape = rel.shape
-        ctx.save_for_backward(lse)
-        return loss_rows
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, p, rowptr, col, label_weight, label_bias = ctx.idx
-        (lse,) = ctx.saved_tensors
-        g_a, g_p, ge = engine.kl_bwd(ctx.t16, ctx.direction, a, p, rowptr, col, lse, g_rows=g_rows.contiguous(),
-                                     label_weight=label_weight, label_bias=label_bias)
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)
-        return None, ge, gr, None, None, None, None, None, None, None
-
-
 class _FusedMultiLabel2(torch.autograd.Function):
     """Both query types of a KvsAll batch: (loss rows of the sp_ queries, loss rows of the _po queries), each from its
     fused forward (kge_kl_fwd / kge_bce_fwd), and ONE backward for both (kge_multilabel2_bwd_accum): two d loss / d score
@@ -1735,28 +1613,6 @@ def kl_fused(name: str, l_norm, direction: str, ent: Tensor, rel: Tensor, a: Ten
     return fused - b_w * s_all + const
 
 
-class _FusedBCE(torch.autograd.Function):
-    """Per-row BCE-with-logits (summed over all entities) fused with the sp_/_po scoring
-    (kge_bce_fwd / kge_bce_bwd); labels as an int64 CSR of the rows' positives."""
-
-    @staticmethod
-    def forward(ctx, direction, ent, rel, a, p, rowptr, col, offset, tables16):
-        loss_rows = engine.bce_fwd(tables16, direction, a, p, rowptr, col, offset)
-        ctx.t16, ctx.direction, ctx.idx, ctx.offset = tables16, direction, (a, p, rowptr, col), offset
-        ctx.rel_shape = rel.shape
-        return loss_rows
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, p, rowptr, col = ctx.idx
-        g_a, g_p, ge = engine.bce_bwd(ctx.t16, ctx.direction, a, p, rowptr, col, ctx.offset,
-                                      g_rows=g_rows.contiguous())
-        gr = torch.zeros(ctx.rel_shape, dtype=torch.float32, device=ge.device)
-        _scatter_rows(gr, p, g_p)
-        _scatter_rows(ge, a, g_a)
-        return None, ge, gr, None, None, None, None, None, None
-
-
 def _score_against_column_sum(name: str, l_norm, direction: str, ent: Tensor, rel: Tensor, a: Tensor,
                               p: Tensor) -> Tensor:
     """[n]: sum_j score(i, j) over ALL entities j.  ComplEx and DistMult are linear in the target row, so
@@ -1806,6 +1662,34 @@ def bce_fused(name: str, l_norm, direction: str, ent: Tensor, rel: Tensor, a: Te
     s_lab = torch.zeros(n, dtype=torch.float32, device=ent.device).index_add(0, rows, lab.view(-1) + offset)
     s_all = _score_against_column_sum(name, l_norm, direction, ent, rel, a, p) + E * offset
     return fused + eps * s_lab - s_all / E
+
+
+_LOSS_NODES = {"ce": (_FusedCE, _FusedCEDist, _FusedCEF32), "kl": (_FusedKL, _FusedKLDist, _FusedKLF32),
+               "bce": (_FusedBCE, _FusedBCEDist, _FusedBCEF32)}
+
+
+def fused_loss_rows(kind: str, direction: str, name: str, l_norm, weights, a: Tensor, p: Tensor, labels: tuple,
+                    eps: float, bf16, dist, f32):
+    """The [n] loss rows of the queries (a, p) ("sp": a = s; "po": a = o) from the first family of fused losses that
+    takes the model's tables, or None when none does -- the one place that decides it, for KgeModel (which then composes
+    the loss from the scores) and for the LibKGE plugin's models (which hand the None to the job).  kind / labels:
+    "ce" (label,) -- "kl" (rowptr, col) -- "bce" (rowptr, col, offset); eps: label smoothing (0.0 for "ce").
+    bf16, dist, f32: the model's _ce_tables, _ce_dist_tables, _ce_f32_tables -- asked in this order, each only when the
+    ones before it returned None, and dist not under label smoothing (its uniform term is not linear in the table for a
+    distance scorer).  weights: () -> (ent, rel), the parameters the gradients go to, asked once a family applies."""
+    node16, node_dist, node32 = _LOSS_NODES[kind]
+    t, node = bf16(), node16
+    if t is None and eps == 0.0:
+        t = dist()
+        if t is not None:
+            return node_dist.apply(direction, *weights(), a, p, *labels, *((None,) if kind == "kl" else ()), t)
+    if t is None:
+        t, node = f32(), node32
+    if t is None:
+        return None
+    if kind == "ce":
+        return node.apply(direction, *weights(), a, p, *labels, t)
+    return (kl_fused if kind == "kl" else bce_fused)(name, l_norm, direction, *weights(), a, p, *labels, eps, t, node)
 
 
 class _ScoreEmb(torch.autograd.Function):
