@@ -1371,6 +1371,53 @@ int kge_adagrad_step_touched(float* param, int64_t param_ld, float* grad, int64_
                              int64_t sum_ld, uint32_t* bitmap, int64_t num_rows, int64_t dim, float minus_clr,
                              float eps, void* bf16_copy, int64_t copy_ld, void* stream);
 
+/* ---- SparseAdam over the rows a batch touched (csrc/touched.hip) -------------------------------
+ * torch.optim.SparseAdam (kge/util/optimizer.py:15-20 with train.optimizer.default.type: SparseAdam and
+ * lookup_embedder.yaml:78-81 `sparse: True`) on the rows whose bit is set in `bitmap` (kge_touched_mark; bits of rows
+ * >= num_rows are ignored): the bitmap stands for the index set of the coalesced sparse gradient, the persistent dense
+ * `grad` for its values.  A dense Adam step cannot be cut down to these rows -- its momentum moves rows that have no
+ * gradient --; SparseAdam is DEFINED row-wise, so this is that optimizer.
+ *
+ * The clock.  `clock` is the parameter's kge_adam_clock record, the layout of kge_adam_step_multi.  A one-workgroup
+ * kernel in front of the update advances it, in float64 with IEEE division and square root:
+ *   t += 1;  beta1_pow *= beta1;  beta2_pow *= beta2;  root = sqrt(1 - beta2_pow)
+ *   step_size = (float)((lr * root) / (1 - beta1_pow));  bias_correction2_sqrt = (float)root
+ * For THIS entry the record's first float is SparseAdam's whole step size lr * sqrt(1 - beta2^t) / (1 - beta1^t) --
+ * not Adam's lr / (1 - beta1^t) --, and the second float, sqrt(1 - beta2^t), is written for the record's readers but
+ * not read by the update: SparseAdam's denominator is sqrt(exp_avg_sq) + eps, without the bias correction inside.  A
+ * record must not be shared between this entry and kge_adam_step_multi.  A fresh record is {T, beta1^T, beta2^T, 0, 0}.
+ * The clock advances ONCE PER CALL, whether or not any bit is set and also when num_rows == 0 (torch counts a step for
+ * every step() call in which the parameter has a gradient, an empty one included); a call that returns an error
+ * advances nothing.  The caller must NOT call this entry for a parameter torch would skip (`grad is None`: a step in
+ * which no backward ran for the table), or the step counts part.
+ *
+ * The update.  For every set bit r < num_rows and every column of row r, in float32, every operation rounded on its
+ * own (no fused multiply-add anywhere), with omb1 = (float)(1 - beta1), omb2 = (float)(1 - beta2) formed in double
+ * and rounded once, g = grad[r], m = exp_avg[r], v = exp_avg_sq[r], p = param[r] -- torch's functional sparse_adam,
+ * operation for operation:
+ *   u1 = (g - m) * omb1             (grad_values.sub(old_exp_avg_values).mul_(1 - beta1))
+ *   m  = m + u1                     (exp_avg.add_(...); the same bits as numer = u1 + m)
+ *   u2 = (g * g - v) * omb2         (grad_values.pow(2).sub_(old_exp_avg_sq_values).mul_(1 - beta2))
+ *   v  = v + u2                     (exp_avg_sq.add_(...); the same bits as u2 + v under the square root)
+ *   d  = sqrt(v) + eps              (IEEE square root)
+ *   p  = p + (-step_size) * (m / d) (IEEE division; the quotient, then the product, then the sum)
+ * then bf16_copy[r] = bf16(p) (RNE) if a copy was given, zeros are stored over grad[r, 0:dim] and, once all rows of a
+ * word are done, over the word.  On return the bitmap is all zero, and grad is all zero provided it was zero outside
+ * the marked rows on entry.  Rows whose bit is clear are neither read nor written, in any of the five arrays.  A
+ * marked row whose gradient is exactly zero STILL decays its moments and moves (m = m - m * omb1 ...): that is what
+ * torch does with a row present in the sparse gradient, and what separates this from the Adagrad entry above.
+ * Every shape is taken: four floats per lane when dim % 4 == 0, param, grad, exp_avg and exp_avg_sq are 16-byte
+ * aligned with pitches % 4 == 0 (and bf16_copy, if given, 8-byte aligned with copy_ld % 4 == 0), one float per lane
+ * otherwise.
+ * KGE_ERR_INVALID_ARG: num_rows or dim < 0, dim > 2^31 - 1, a pitch < dim, a NULL param, grad, exp_avg, exp_avg_sq or
+ * bitmap (num_rows > 0), a NULL or not 8-byte aligned clock (whatever num_rows), beta1 or beta2 outside [0, 1).
+ * KGE_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups (256 rows each); checked before the clock.
+ * num_rows == 0: KGE_OK; the clock kernel is the one launch. */
+int kge_sparse_adam_step_touched(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* exp_avg,
+                                 int64_t avg_ld, float* exp_avg_sq, int64_t sq_ld, uint32_t* bitmap, int64_t num_rows,
+                                 int64_t dim, kge_adam_clock* clock, double lr, double beta1, double beta2, float eps,
+                                 void* bf16_copy, int64_t copy_ld, void* stream);
+
 /* ---- backward (autograd twins) ------------------------------------------ */
 /* All gradients are f32 and OVERWRITTEN; tables/embeddings must be f32, except
  * kge_score_pairs_bwd for ComplEx/DistMult, which also takes bf16 tables (mixed-precision

@@ -251,6 +251,9 @@ PROTOTYPES = {
     "kge_touched_mark": (ctypes.c_int, [KgeIndex, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "kge_adagrad_step_touched": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64,
                                                 ctypes.c_float, ctypes.c_float, c_vp, c_i64, c_vp]),
+    "kge_sparse_adam_step_touched": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                                    c_i64, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.c_float, c_vp, c_i64, c_vp]),
     "kge_score_pairs_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, KgeIndex,
                                            c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                            c_i64, c_vp]),

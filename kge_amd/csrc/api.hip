@@ -256,6 +256,10 @@ int run_touched_mark(const Index& ids, long long n, long long k, long long ld, l
 int run_adagrad_touched(float* param, long long param_ld, float* grad, long long grad_ld, float* sum, long long sum_ld,
                         unsigned int* bitmap, long long num_rows, int dim, float minus_clr, float eps,
                         unsigned short* copy16, long long c_ld, hipStream_t st);
+int run_sparse_adam_touched(float* param, long long param_ld, float* grad, long long grad_ld, float* m1, long long m1_ld,
+                            float* m2, long long m2_ld, unsigned int* bitmap, long long num_rows, int dim,
+                            kge_adam_clock* clock, double lr, double beta1, double beta2, float eps,
+                            unsigned short* copy16, long long c_ld, hipStream_t st);
 int run_kl_fwd(int scorer, const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n,
                long long m, const long long* rowptr, const long long* col, float* loss_rows, float* lse, void* ws,
                long long ws_bytes, hipStream_t st, const float* label_weight = nullptr, long long col_lo = 0);
@@ -2662,6 +2666,22 @@ int kge_adagrad_step_touched(float* param, int64_t param_ld, float* grad, int64_
   if (param_ld < dim || grad_ld < dim || sum_ld < dim || (bf16_copy && copy_ld < dim)) return KGE_ERR_INVALID_ARG;
   return run_adagrad_touched(param, param_ld, grad, grad_ld, state_sum, sum_ld, bitmap, num_rows, (int)dim, minus_clr,
                              eps, (unsigned short*)bf16_copy, copy_ld, (hipStream_t)stream);
+}
+
+int kge_sparse_adam_step_touched(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* exp_avg,
+                                 int64_t avg_ld, float* exp_avg_sq, int64_t sq_ld, uint32_t* bitmap, int64_t num_rows,
+                                 int64_t dim, kge_adam_clock* clock, double lr, double beta1, double beta2, float eps,
+                                 void* bf16_copy, int64_t copy_ld, void* stream) {
+  KGE_RANGE();
+  if (num_rows < 0 || dim < 0 || dim > 0x7fffffff) return KGE_ERR_INVALID_ARG;
+  if (num_rows > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !bitmap)) return KGE_ERR_INVALID_ARG;
+  if (param_ld < dim || grad_ld < dim || avg_ld < dim || sq_ld < dim || (bf16_copy && copy_ld < dim))
+    return KGE_ERR_INVALID_ARG;
+  if (!clock || ((uintptr_t)clock & 7)) return KGE_ERR_INVALID_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return KGE_ERR_INVALID_ARG;
+  return run_sparse_adam_touched(param, param_ld, grad, grad_ld, exp_avg, avg_ld, exp_avg_sq, sq_ld, bitmap, num_rows,
+                                 (int)dim, clock, lr, beta1, beta2, eps, (unsigned short*)bf16_copy, copy_ld,
+                                 (hipStream_t)stream);
 }
 
 int kge_bce_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,

@@ -1415,6 +1415,40 @@ def adagrad_step_touched(param: torch.Tensor, grad: torch.Tensor, state_sum: tor
             0 if bf16_copy is None else ld(bf16_copy), _stream_handle(device)), "kge_adagrad_step_touched")
 
 
+def sparse_adam_step_touched(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                             bitmap: torch.Tensor, clock: torch.Tensor, lr: float, beta1: float, beta2: float,
+                             eps: float, bf16_copy: torch.Tensor = None) -> None:
+    """torch.optim.SparseAdam's update on the rows whose bit is set (kge_sparse_adam_step_touched; DESIGN.md section
+    33); afterwards the marked rows of `grad` and the bitmap are zero and the 32-byte `clock` record (int64 [4] on the
+    device: kge_adam_clock) is one step further -- whether or not a bit was set.  param, grad, exp_avg, exp_avg_sq:
+    float32 [E, d] with unit inner stride (any row pitch), bf16_copy: bfloat16 / int16 [E, d] or None; rows whose bit
+    is clear are neither read nor written."""
+    device = param.device
+    if device.type != "cuda":
+        raise RuntimeError(f"kge_amd: sparse_adam_step_touched steps on a GPU, not on '{device}' (no CPU path)")
+    E, d = param.shape
+    for t, what in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if not (t.device == device and t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (E, d)
+                and (d <= 1 or t.stride(1) == 1) and (E <= 1 or t.stride(0) >= d)):
+            raise ValueError(f"kge_amd: sparse_adam_step_touched: {what} is float32 [E, d] with unit inner stride on "
+                             f"{device}")
+    if bf16_copy is not None and not (bf16_copy.device == device and bf16_copy.element_size() == 2
+                                      and tuple(bf16_copy.shape) == (E, d) and (d <= 1 or bf16_copy.stride(1) == 1)
+                                      and (E <= 1 or bf16_copy.stride(0) >= d)):
+        raise ValueError("kge_amd: sparse_adam_step_touched: bf16_copy is a 2-byte [E, d] tensor with unit inner stride")
+    if not (torch.is_tensor(clock) and clock.device == device and clock.dtype == torch.int64 and clock.numel() == 4
+            and clock.is_contiguous()):
+        raise ValueError(f"kge_amd: sparse_adam_step_touched: the clock record is a contiguous int64 [4] on {device}")
+    _bitmap_ok(bitmap, E, device, "sparse_adam_step_touched")
+    ld = lambda t: t.stride(0) if E > 1 else max(d, 1)
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_sparse_adam_step_touched(
+            param.data_ptr(), ld(param), grad.data_ptr(), ld(grad), exp_avg.data_ptr(), ld(exp_avg),
+            exp_avg_sq.data_ptr(), ld(exp_avg_sq), bitmap.data_ptr(), E, d, clock.data_ptr(), float(lr), float(beta1),
+            float(beta2), float(eps), None if bf16_copy is None else bf16_copy.data_ptr(),
+            0 if bf16_copy is None else ld(bf16_copy), _stream_handle(device)), "kge_sparse_adam_step_touched")
+
+
 KVSALL_COLLATE_MAX_N = _lib.KVSALL_COLLATE_MAX_N
 
 

@@ -16,6 +16,9 @@ Usage inside an unmodified LibKGE installation (config-default.yaml:137, README.
     #           plus bf16_copies: true to keep the bf16 scoring tables fresh without a cast; HipAdam also takes
     #           device_step: true -- the step count on the device, one launch over all tables, folded penalty terms
     #           and a capturable step, so hip_1vsAll / hip_KvsAll / hip_negative_sampling graph_step work under Adam)
+    # optional: train.optimizer.default.type: HipSparseAdam with hip_negative_sampling.touched_rows: true
+    #           (torch.optim.SparseAdam's row-wise update on the rows a batch marked, step count on the device;
+    #           checkpoints interchangeable with SparseAdam on `sparse: true` embedders)
 
 `Config._import("hip_complex")` finds hip_complex.yaml in this package (config.py:280-325)
 and `init_from(class_name, modules)` (misc.py:13-42) resolves the classes below.  They
@@ -45,6 +48,8 @@ from .sharded_job import (HipShardedEntityRankingJob, HipShardedTrainingJob1vsAl
 import torch.optim as _torch_optim
 from ..optim import Adagrad as HipAdagrad  # noqa: E402
 from ..optim import Adam as HipAdam  # noqa: E402
+from ..optim import SparseAdam as HipSparseAdam  # noqa: E402
 
 _torch_optim.HipAdagrad = HipAdagrad
 _torch_optim.HipAdam = HipAdam
+_torch_optim.HipSparseAdam = HipSparseAdam

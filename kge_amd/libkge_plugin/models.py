@@ -126,11 +126,12 @@ class _FusedScoring:
     def _w(self):
         return (self.get_s_embedder()._embeddings.weight, self.get_p_embedder()._embeddings.weight)
 
-    def set_touched_rows(self, pair):
+    def set_touched_rows(self, pair, rel_pair=None):
         """hip_negative_sampling.touched_rows: `pair` = HipAdagrad.enable_touched_rows(entity table) -> (grad, bitmap),
         or None.  score_spo / score_neg / score_neg_blocks hand it to their autograd nodes while the model trains: the
-        backward accumulates the entity gradient into the persistent buffer and marks the rows (kge_amd.model)."""
-        self._touched_rows = pair
+        backward accumulates the entity gradient into the persistent buffer and marks the rows (kge_amd.model).
+        `rel_pair` = HipSparseAdam.enable_touched_rows(relation table): the relation gradient goes the same way."""
+        self._touched_rows = pair if rel_pair is None else (pair, rel_pair)
 
     def _touched_pair(self):
         return getattr(self, "_touched_rows", None) if self.training else None
@@ -500,7 +501,7 @@ class HipTransH(_FusedScoring, _RefTransH):
                 name.lstrip("_")))
         super().__setattr__(name, value)
 
-    def set_touched_rows(self, pair):
+    def set_touched_rows(self, pair, rel_pair=None):
         if pair is not None:
             raise ValueError("hip_transh: touched_rows is not supported")
         self._touched_rows = None
@@ -541,7 +542,7 @@ class HipRescal(_FusedScoring, _RefRescal):
                 name.lstrip("_")))
         super().__setattr__(name, value)
 
-    def set_touched_rows(self, pair):
+    def set_touched_rows(self, pair, rel_pair=None):
         if pair is not None:
             raise ValueError("hip_rescal: touched_rows is not supported")
         self._touched_rows = None
@@ -612,7 +613,7 @@ class HipRelationalTucker3(Tucker3Routes, _FusedScoring, _RefRelationalTucker3):
                              "losses)".format(name.lstrip("_")))
         super().__setattr__(name, value)
 
-    def set_touched_rows(self, pair):
+    def set_touched_rows(self, pair, rel_pair=None):
         if pair is not None:
             raise ValueError("hip_relational_tucker3: touched_rows is not supported")
         self._touched_rows = None
@@ -755,7 +756,7 @@ class HipConvE(ConveRoutes, _FusedScoring, _RefConvE):
                 name.lstrip("_")))
         super().__setattr__(name, value)
 
-    def set_touched_rows(self, pair):
+    def set_touched_rows(self, pair, rel_pair=None):
         if pair is not None:
             raise ValueError("hip_conve: touched_rows is not supported")
         self._touched_rows = None

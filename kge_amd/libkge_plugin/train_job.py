@@ -1090,24 +1090,34 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         from kge.model import LookupEmbedder
         from kge.util.sampler import DefaultBatchNegativeSample
         from ..model import neg_blocks_fusable
-        from ..optim import Adagrad as HipAdagrad
+        from ..optim import Adagrad as HipAdagrad, SparseAdam as HipSparseAdam
         from .models import _FusedScoring
         model, opt = self.model, self.optimizer
         if not str(self.device).startswith("cuda"):
             return "not a CUDA device"
         if not isinstance(model, _FusedScoring) or not model._fused():
             return "the model's fused gather + score path does not apply"
-        if not isinstance(opt, HipAdagrad):
-            return "the optimizer is not HipAdagrad (dense Adam moves rows without a gradient)"
+        if not isinstance(opt, (HipAdagrad, HipSparseAdam)):
+            return "the optimizer is not HipAdagrad or HipSparseAdam (dense Adam moves rows without a gradient)"
         emb = model.get_s_embedder()
         w = emb._embeddings.weight
         group = next((g for g in opt.param_groups if any(q is w for q in g["params"])), None)
-        if group is None or group["weight_decay"] != 0:
+        if group is None or group.get("weight_decay", 0) != 0:
             return "weight_decay != 0 in the entity table's parameter group"
         if type(emb) is not LookupEmbedder or emb.dropout.p > 0:
             return "the entity embedder is not a plain LookupEmbedder without dropout"
         if not (emb.regularize == "" or emb.get_option("regularize_weight") == 0.0):
             return "regularize_weight > 0 on the entity embedder (a penalty term touches every row)"
+        if isinstance(opt, HipSparseAdam):  # the relation table goes through a bitmap too: the same conditions
+            rel = model.get_p_embedder()
+            if not any(q is rel._embeddings.weight for g in opt.param_groups for q in g["params"]):
+                return "the relation table is in none of the optimizer's parameter groups"
+            if type(rel) is not LookupEmbedder or rel.dropout.p > 0:
+                return "the relation embedder is not a plain LookupEmbedder without dropout"
+            if not (rel.regularize == "" or rel.get_option("regularize_weight") == 0.0):
+                return "regularize_weight > 0 on the relation embedder (a penalty term touches every row)"
+            if sum(p.requires_grad for p in model.parameters()) != 2:
+                return "parameters other than the two embedding tables (HipSparseAdam has no dense step)"
         if self._sampler.num_samples[P] > 0:
             return "negative samples for the relation slot"
         slots = [slot for slot in (S, O) if self._sampler.num_samples[slot] > 0]
@@ -1122,16 +1132,29 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             want = bool(self.config.get_default("hip_negative_sampling.touched_rows"))
         except KeyError:
             want = False
+        from ..optim import SparseAdam as HipSparseAdam
+        sparse_adam = isinstance(self.optimizer, HipSparseAdam)
         self.touched_rows = False
-        if not want or self.is_forward_only:
+        if self.is_forward_only:
+            return
+        if not want:
+            if sparse_adam:  # (no dense path to fall back to)
+                raise ValueError("train.optimizer.default.type: HipSparseAdam needs hip_negative_sampling.touched_rows: "
+                                 "true (it steps the rows a batch marked; it has no dense step)")
             return
         why = self._touched_rows_why_not(batch)
         if why is not None:
             self.touched_rows_declined = why
+            if sparse_adam:
+                raise ValueError(f"hip_negative_sampling.touched_rows with HipSparseAdam: {why}")
             self.config.log(f"hip_negative_sampling.touched_rows: the dense path runs: {why}")
             return
         pair = self.optimizer.enable_touched_rows(self.model.get_s_embedder()._embeddings.weight)
-        self.model.set_touched_rows(pair)
+        if sparse_adam:
+            self.model.set_touched_rows(pair, self.optimizer.enable_touched_rows(
+                self.model.get_p_embedder()._embeddings.weight))
+        else:
+            self.model.set_touched_rows(pair)
         self.touched_rows = True
 
     def _process_subbatch(self, batch_index, batch, subbatch_slice, result):

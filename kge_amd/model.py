@@ -234,14 +234,18 @@ class KgeModel(torch.nn.Module):
     def _make_relation_embedder(self, num_relations, rel_dim, dtype, device, relation_args):
         return LookupEmbedder(num_relations, rel_dim, dtype=dtype, device=device, **relation_args)
 
-    def set_touched_rows(self, pair):
+    def set_touched_rows(self, pair, rel_pair=None):
         """`pair` = kge_amd.optim.Adagrad.enable_touched_rows(entity table) -> (grad, bitmap), or None to switch it off:
         score_spo, score_neg and score_neg_blocks hand it to their autograd nodes, whose backward then accumulates the
         entity gradient into the persistent `grad`, marks the rows in `bitmap` and leaves the table's `.grad` None
-        (DESIGN.md section 25).  Shared samples (score_neg_shared) keep the dense gradient: do not mix them with it."""
+        (DESIGN.md section 25).  Shared samples (score_neg_shared) keep the dense gradient: do not mix them with it.
+        `rel_pair` = kge_amd.optim.SparseAdam.enable_touched_rows(relation table): the relation gradient goes the same
+        way, the batch's `p` rows marked; None: a fresh dense relation gradient per node."""
         if pair is not None and self.scorer_cls in (TransHScorer, RescalScorer):
             raise ValueError("{}: touched_rows is not supported".format(type(self).__name__))
-        self._touched_rows = pair
+        if pair is None and rel_pair is not None:
+            raise ValueError("{}: the relation table's touched rows need the entity table's".format(type(self).__name__))
+        self._touched_rows = pair if rel_pair is None else (pair, rel_pair)
 
     # -- accessors (kge_model.py:649-661)
     def get_s_embedder(self):
@@ -954,7 +958,7 @@ class ConvE(ConveRoutes, KgeModel):
     def tables(self, flags: int = 0):
         raise ValueError("ConvE: there are no kge_tables of a ConvE model (its score is not a function of three rows)")
 
-    def set_touched_rows(self, pair):
+    def set_touched_rows(self, pair, rel_pair=None):
         if pair is not None:
             raise ValueError("ConvE: touched_rows is not supported")
         self._touched_rows = None
@@ -1078,19 +1082,45 @@ def _scatter_rows(grad_table, idx, rows):
 def _touched_pair(t, touched):
     """`touched` = (grad, bitmap) of kge_amd.optim.Adagrad.enable_touched_rows for the entity table, checked: the
     backward then accumulates the entity gradient into the persistent `grad`, marks the rows it adds to in `bitmap`
-    and returns None for the table -- no zeros_like(ent) fill, no dense gradient for the optimizer to sweep."""
-    grad, bitmap = touched
+    and returns None for the table -- no zeros_like(ent) fill, no dense gradient for the optimizer to sweep.
+    Or ((grad, bitmap), (rel_grad, rel_bitmap)): the pairs of kge_amd.optim.SparseAdam.enable_touched_rows for the
+    entity AND the relation table -> (entity pair, relation pair or None)."""
+    ent, rel = (touched, None) if torch.is_tensor(touched[0]) else touched
+    grad, bitmap = ent
     if not (grad.shape == t.ent.shape and grad.dtype == torch.float32 and t.ent.dtype == torch.float32
             and grad.device == t.ent.device and grad.stride(1) == 1):
         raise ValueError("kge_amd: the touched-row gradient buffer is a float32 tensor of the entity table's shape on "
                          "its device")
-    return grad, bitmap
+    if rel is not None:
+        rgrad, _ = rel
+        if not (rgrad.shape == t.rel.shape and rgrad.dtype == torch.float32 and t.rel.dtype == torch.float32
+                and rgrad.device == t.rel.device and rgrad.stride(1) == 1):
+            raise ValueError("kge_amd: the relation table's touched-row gradient buffer is a float32 tensor of the "
+                             "table's shape on its device")
+    return ent, rel
 
 
 def _mark_touched(t, bitmap, *ids):
     for x in ids:
         if x is not None:
             engine.touched_mark(x, bitmap, t.ent.shape[0])
+
+
+def _touched_buffers(t, touched, p, *ent_ids):
+    """What a backward node on the touched-row route accumulates into -> (entity gradient buffer, relation gradient,
+    whether the relation gradient is a persistent buffer too).  Marks `ent_ids` in the entity bitmap; with a relation
+    pair also the batch's `p` in the relation bitmap, and the relation gradient is that pair's buffer instead of a
+    fresh zeros_like(rel).  A pair that keeps a `pending` flag (kge_amd.optim.SparseAdam) is told a backward ran."""
+    ent, rel = touched
+    _mark_touched(t, ent[1], *ent_ids)
+    if hasattr(ent, "pending"):
+        ent.pending = True
+    if rel is None:
+        return ent[0], torch.zeros_like(t.rel), False
+    engine.touched_mark(p, rel[1], t.rel.shape[0])
+    if hasattr(rel, "pending"):
+        rel.pending = True
+    return ent[0], rel[0], True
 
 
 class _ScoreSPO(torch.autograd.Function):
@@ -1108,12 +1138,10 @@ class _ScoreSPO(torch.autograd.Function):
         s, p, o = ctx.idx
         (scores,) = ctx.saved_tensors
         if ctx.touched is not None:  # the accumulate route on the persistent buffer, or nothing
-            ge, bitmap = ctx.touched
-            gr = torch.zeros_like(ctx.t.rel)
-            _mark_touched(ctx.t, bitmap, s, o)
+            ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o)
             if not engine.score_spo_bwd_accum(ctx.t, s, p, o, gout.contiguous(), scores, ge, gr):
                 raise RuntimeError("kge_amd: kge_score_spo_bwd_accum declined a shape the touched-row step admitted")
-            return None, None, None, gr, None, None, None, None
+            return None, None, None, None if rel_kept else gr, None, None, None, None
         ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
         # one kernel: row gradients accumulated into the table gradients (runs of equal s / p
         # summed in registers first); fallback: row gradients + three scatter-adds
@@ -1145,12 +1173,10 @@ class _ScoreNeg(torch.autograd.Function):
         s, p, o, neg = ctx.idx
         (scores,) = ctx.saved_tensors
         if ctx.touched is not None:  # the accumulate kernel on the persistent buffer, or nothing
-            ge, bitmap = ctx.touched
-            gr = torch.zeros_like(ctx.t.rel)
-            _mark_touched(ctx.t, bitmap, s, o, neg)
+            ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o, neg)
             if not engine.score_neg_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr):
                 raise RuntimeError("kge_amd: kge_score_neg_bwd_accum declined a shape the touched-row step admitted")
-            return None, None, None, gr, None, None, None, None, None, None
+            return None, None, None, None if rel_kept else gr, None, None, None, None, None, None
         ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
         if not engine.score_neg_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr):
             # shapes the accumulate kernel does not take (bf16 parameters, d > 1024): expanded triples
@@ -1228,20 +1254,21 @@ class _ScoreNegBlocks(torch.autograd.Function):
     def backward(ctx, g_pos, g_s, g_o):
         s, p, o, neg_s, neg_o = ctx.idx
         pos, sc_s, sc_o = ctx.saved_tensors
-        gr = torch.zeros_like(ctx.t.rel)
+        rel_kept = False
         if ctx.touched is not None:
             # the persistent buffer in place of a fresh zeros_like(ent); s, o and the blocks differentiated are marked
-            ge, bitmap = ctx.touched
-            _mark_touched(ctx.t, bitmap, s, o, neg_s if g_s is not None else None, neg_o if g_o is not None else None)
+            ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o, neg_s if g_s is not None else None,
+                                                neg_o if g_o is not None else None)
         else:
-            ge = torch.zeros_like(ctx.t.ent)
+            ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
         if g_pos is not None and not engine.score_spo_bwd_accum(ctx.t, s, p, o, g_pos.contiguous(), pos, ge, gr):
             raise RuntimeError("kge_amd: kge_score_spo_bwd_accum declined a shape score_neg_blocks admitted")
         for slot, neg, g, sc in ((0, neg_s, g_s, sc_s), (2, neg_o, g_o, sc_o)):
             if neg is not None and g is not None:
                 if not engine.score_neg_bwd_accum(ctx.t, s, p, o, slot, neg, g, sc, ge, gr):
                     raise RuntimeError("kge_amd: kge_score_neg_bwd_accum declined a shape score_neg_blocks admitted")
-        return None, None, None if ctx.touched is not None else ge, gr, None, None, None, None, None, None
+        return (None, None, None if ctx.touched is not None else ge, None if rel_kept else gr, None, None, None, None,
+                None, None)
 
 
 def neg_shared_fusable(ent: torch.Tensor, n: int) -> bool:

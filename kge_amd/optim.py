@@ -2,7 +2,8 @@
 table of a device in one launch, kge_adagrad_step_rows for row-sparse gradients, kge_adagrad_step_touched for a table
 whose backward marks the rows it touched (Adagrad.enable_touched_rows), kge_adam_step per parameter, or
 kge_adam_step_multi with Adam(device_step=True): the step count on the device, one launch, capturable), optionally
-maintaining the bf16 copies of the tables that mixed-precision scoring reads.
+maintaining the bf16 copies of the tables that mixed-precision scoring reads.  `SparseAdam`: torch.optim.SparseAdam on
+the rows a backward marked (kge_sparse_adam_step_touched), the plugin's `HipSparseAdam`.
 
 Drop-in for `torch.optim.Adagrad` (same constructor arguments, same `state_dict`: per-parameter
 "step" and "sum"), so LibKGE's optimizer checkpoints load either way.  Parameters the kernel does
@@ -504,3 +505,154 @@ class Adam(_FoldedPenalties, torch.optim.Adam):
         finally:
             for q, g in stash:
                 q.grad = g
+
+
+class _TouchedRows(tuple):
+    """(grad, bitmap) of SparseAdam.enable_touched_rows.  `pending`: a backward accumulated into the pair since the last
+    step() -- set by the backward nodes of kge_amd.model; what `p.grad is not None` tells torch.optim.SparseAdam."""
+    pending = False
+
+
+class SparseAdam(torch.optim.SparseAdam):
+    """torch.optim.SparseAdam (same constructor arguments and `state_dict`: "step", "exp_avg", "exp_avg_sq"; a
+    checkpoint of either class loads into the other) for tables whose backward marks the rows it touched
+    (`enable_touched_rows`, as kge_amd.optim.Adagrad): kge_sparse_adam_step_touched applies torch's row-wise update to
+    the marked rows, with the step count on the device (state[p]["clock"], a kge_adam_clock record as
+    Adam(device_step=True) keeps, not part of `state_dict()`), so the step is `graph_capturable`.
+    Parameters that arrive with a genuinely sparse gradient are stepped by torch's own code; a dense gradient raises
+    torch's error: SparseAdam has no dense form -- a dense Adam step moves rows that have no gradient."""
+
+    graph_capturable = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, maximize=False, weight_decay=0,
+                 bf16_copies: bool = False):
+        if weight_decay != 0:
+            raise ValueError("kge_amd.optim.SparseAdam: weight_decay moves rows without a gradient: it must be 0")
+        if maximize:
+            raise NotImplementedError("kge_amd.optim.SparseAdam: maximize is not supported")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, maximize=False)
+        self.bf16_copies = bool(bf16_copies)
+        self._touched = {}   # parameter -> _TouchedRows(persistent dense gradient [rows, d], bitmap)
+        self._stepped = []   # the parameters the last step() updated: stepped_params
+
+    def enable_touched_rows(self, param):
+        """From now on `param` -- a 2-D contiguous float32 GPU table -- is stepped on the rows its backward MARKED:
+        allocates, once, a zero [rows, d] gradient buffer and a zero row bitmap (`touched_rows(param)`).  A backward
+        that knows the pair (kge_amd.model's score_spo / score_neg / score_neg_blocks nodes) accumulates the table's
+        gradient into the buffer, marks the rows it adds to, sets the pair's `pending` and leaves `param.grad` None;
+        step() applies torch.optim.SparseAdam's update to the marked rows -- the index set of the coalesced sparse
+        gradient `sparse=True` embeddings would have produced -- and zeroes the buffer's rows and the bitmap again."""
+        name = "kge_amd.optim.SparseAdam.enable_touched_rows"
+        group = next((g for g in self.param_groups if any(q is param for q in g["params"])), None)
+        if group is None:
+            raise ValueError(f"{name}: not a parameter of this optimizer")
+        if not (torch.is_tensor(param) and param.is_cuda and param.dim() == 2 and param.dtype == torch.float32
+                and param.is_contiguous()):
+            raise ValueError(f"{name}: needs a 2-D contiguous float32 GPU parameter")
+        if param not in self._touched:
+            self._touched[param] = _TouchedRows((torch.zeros_like(param, requires_grad=False).detach(),
+                                                 engine.touched_bitmap(param.shape[0], param.device)))
+        return self._touched[param]
+
+    def touched_rows(self, param):
+        """(grad, bitmap) of a parameter switched to the touched-row step, else None."""
+        return self._touched.get(param)
+
+    def stepped_params(self):
+        """The parameters the last step() updated (kge_amd.train_graph.GraphedStep: `p.grad is not None` misses the
+        touched-row parameters, whose gradient never reaches `.grad`)."""
+        return list(self._stepped)
+
+    def after_graph_replay(self, params):
+        """`params`: the parameters the captured step() updated.  The replayed clock kernel advanced their device
+        records; the host's state["step"] -- what the checkpoint carries and a record is seeded from -- follows."""
+        for p in params:
+            st = self.state.get(p)
+            if st is not None and "step" in st:
+                st["step"] += 1
+
+    def device_step_count(self, param) -> int:
+        """`t` of the parameter's device clock record (a host read: synchronizes)."""
+        return int(self.state[param]["clock"][0])
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = {k: {n: v for n, v in st.items() if n != "clock"} for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            st.pop("clock", None)  # seeded again from the restored state["step"] by the next step()
+
+    def _step_touched(self, p, group):
+        name = "kge_amd.optim.SparseAdam"
+        if p.grad is not None:
+            raise RuntimeError(f"{name}: a gradient reached `.grad` of a parameter switched to the touched-row step (a "
+                               "backward route that does not know its gradient buffer)")
+        pair = self._touched[p]
+        if not pair.pending:  # no backward touched the table: torch skips a parameter whose grad is None
+            return False
+        capturing = torch.cuda.is_current_stream_capturing()
+        state = self.state[p]
+        if len(state) == 0:
+            if capturing:
+                raise RuntimeError(f"{name}: the first step() of a parameter cannot be captured (its moments would be "
+                                   "zeroed by every replay): take one step eagerly first")
+            state["step"] = 0
+            state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        beta1, beta2 = group["betas"]
+        clock = state.get("clock")
+        if clock is None or clock.device != p.device:
+            if capturing:
+                raise RuntimeError(f"{name}: the first step() of a parameter cannot be captured (its clock record is "
+                                   "made on the host): take one step eagerly first")
+            import struct
+            t = int(state["step"])
+            rec = struct.pack("<qddff", t, float(beta1) ** t, float(beta2) ** t, 0.0, 0.0)
+            clock = state["clock"] = torch.frombuffer(bytearray(rec), dtype=torch.int64).to(p.device)
+        state["step"] += 1  # (the checkpoint's count; the kernel's own is the record's t)
+        pair.pending = False
+        grad, bitmap = pair
+        copy = None
+        if self.bf16_copies:
+            # only the marked rows are rewritten: the copy must be FRESH before (as Adagrad._step_touched)
+            copy = bf16_copy_of(p)
+            if copy is None:
+                rec = getattr(p, BF16_ATTR, None)
+                if rec is not None and rec[0].shape == p.shape and rec[0].data_ptr() != 0:
+                    copy = rec[0]
+                    copy.copy_(p.detach())
+                else:
+                    copy = p.detach().to(torch.bfloat16)
+        engine.sparse_adam_step_touched(p.detach(), grad, state["exp_avg"], state["exp_avg_sq"], bitmap, clock,
+                                        float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), copy)
+        torch.autograd.graph.increment_version(p)
+        if copy is not None:
+            setattr(p, BF16_ATTR, (copy, p._version, p.data_ptr()))
+        return True
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            if group.get("maximize"):
+                raise NotImplementedError("kge_amd.optim.SparseAdam: maximize is not supported")
+        # torch's own step first: the parameters with a sparse gradient; its error for a dense one.  (The touched-row
+        # parameters have no `.grad`: it skips them.)
+        stepped = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        for p in stepped:
+            if self._touched and p in self._touched:
+                self._step_touched(p, None)  # raises: a gradient in `.grad`
+        torch.optim.SparseAdam.step(self)
+        if self._touched:
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if p in self._touched and self._step_touched(p, group):
+                        stepped.append(p)
+        self._stepped = stepped
+        return loss
