@@ -456,6 +456,21 @@ int kge_score_neg_shared(const kge_tables* t, kge_index s, kge_index p, kge_inde
                          const void* unique, int32_t unique_itype, int64_t num_unique, const int64_t* drop,
                          const int64_t* repeat, int64_t num_repeat, float* out, int64_t ldo, void* stream);
 
+/* Relation prediction: KgeModel.score_so, kge/model/kge_model.py:727-747.  out[i*ldo + j] = score of (s[i], rels[j],
+ * o[i]): n (s, o) pairs against m relations -- rels.ptr == NULL: all of them, m == t->num_rel; else the listed ids
+ * (they may repeat and need not be sorted).  The reference composes these scores from three repeats to [n*m, dim] and
+ * the spo scorer (the generic "s_o" fallback of RelationalScorer.score_emb, kge_model.py:202-209); here a workgroup
+ * stages a tile of relation rows once in LDS (RotatE: cos / sin of the phases, evaluated once per staged row) and
+ * its pairs walk them from registers.  Every score has the bits kge_score_spo stores for the same triple; nothing
+ * outside [n, m] is written.  ComplEx, DistMult, TransE and RotatE on float32 / bf16 tables; other scorers and rows
+ * too wide for the LDS tile (f32 dim > 1024, bf16 dim > 2048): KGE_ERR_UNSUPPORTED.  n == 0 or m == 0: KGE_OK, nothing
+ * is launched.  rels.ptr == NULL with m != t->num_rel, negative sizes, ldo < m: KGE_ERR_INVALID_ARG.  workspace:
+ * kge_score_so_workspace_bytes(t, n, m) bytes of device scratch (currently 0 for every shape: pass NULL); less than
+ * that: KGE_ERR_WORKSPACE. */
+int64_t kge_score_so_workspace_bytes(const kge_tables* t, int64_t n, int64_t m);
+int kge_score_so(const kge_tables* t, kge_index s, kge_index o, int64_t n, kge_index rels, int64_t m, float* out,
+                 int64_t ldo, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- embedding-level scoring (dense inputs, no gather) ----------------- */
 /* RelationalScorer.score_emb.  `t` supplies scorer, dtype, dim, rel_dim and
  * l_norm only (t->ent/rel ignored).  SPO: all three [n, *] -> out[n];
@@ -1512,6 +1527,21 @@ int kge_score_neg_shared_bwd_accum(const kge_tables* t, kge_index s, kge_index p
                                    const float* scores, int64_t lds, float* grad_ent, int64_t grad_ent_ld,
                                    float* grad_rel, int64_t grad_rel_ld, void* workspace, int64_t workspace_bytes,
                                    void* stream);
+
+/* Backward of kge_score_so (replaces autograd through the three [n*m, dim] repeats of the reference's "s_o"
+ * composition, kge/model/kge_model.py:727-747 and :202-209): gradients of sum_{i,j} gout[i*ldg + j] * out[i, j]
+ * ACCUMULATED into the dense table gradients like kge_score_neg_shared_bwd_accum.  A pair's s and o row gradients are
+ * summed in registers over a tile of 64 / NC relation rows, a relation entry's gradient over a tile of 32 / NC pairs
+ * (NC = 1, 2, 4, 8 coordinate pairs per lane for ceil(dim / 2) <= 64, 128, 256, 512): one atomic row flush per (owner,
+ * tile), none per (pair, relation) occurrence; s[i] == o[i], repeated pairs and repeated rels entries add up.
+ * `scores` = the forward output (row pitch lds; needed for TransE / RotatE with l_norm != 1 -- NULL there:
+ * KGE_ERR_INVALID_ARG --, may be NULL otherwise).  f32 tables, dim <= 1024 (odd dims included); bf16 tables and wider
+ * dims: KGE_ERR_UNSUPPORTED, gradients untouched.  Rows no index names are not touched; rows that only zero weights
+ * reach get +0.f added.  workspace: as kge_score_so. */
+int kge_score_so_bwd_accum(const kge_tables* t, kge_index s, kge_index o, int64_t n, kge_index rels, int64_t m,
+                           const float* gout, int64_t ldg, const float* scores, int64_t lds, float* grad_ent,
+                           int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld, void* workspace,
+                           int64_t workspace_bytes, void* stream);
 
 /* Backward of kge_score_emb (dense embeddings).  SPO: g_s,g_o [n,dim], g_p [n,rel_dim].
  * SP_: g_s [n,dim], g_p [n,rel_dim], g_o [m,dim].  PO_: g_o [n,dim], g_p, g_s [m,dim]. */

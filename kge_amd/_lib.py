@@ -169,6 +169,10 @@ PROTOTYPES = {
     "kge_score_neg_shared_bwd_accum": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, ctypes.c_int, c_vp,
                                                       ctypes.c_int32, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
                                                       c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kge_score_so_workspace_bytes": (c_i64, [_PT, c_i64, c_i64]),
+    "kge_score_so": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kge_score_so_bwd_accum": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                              c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_score_emb": (ctypes.c_int, [_PT, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                      c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_embed": (ctypes.c_int, [_PT, KgeIndex, c_i64, c_vp, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp]),

@@ -63,6 +63,14 @@ int run_neg_shared_bwd_accum(int scorer, float lp, const Operand& S, const Opera
                              const long long* rep, long long nrep, const float* gout, long long ldg,
                              const float* scores, long long lds, float* ge, long long ge_ld, float* gr, long long gr_ld,
                              void* ws, long long ws_bytes, hipStream_t st);
+// score_so.hip
+bool so_tables_ok(int scorer, int dtype, long long d);
+bool so_bwd_needs_scores(int scorer, float lp);
+int run_so(int scorer, int dtype, const Operand& S, const Operand& R, const Operand& O, int d, int dr, long long n,
+           long long m, float lp, float* out, long long ldo, hipStream_t st);
+int run_so_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                     long long n, long long m, const float* gout, long long ldg, const float* scores, long long lds,
+                     float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st);
 int run_pairs_exact(int scorer, int dtype, bool use_mfma, const Operand& A, const Operand& R,
                     const Operand& TG, int dir, int d, int dr, long long n, long long m,
                     float lp, float* out, long long ldo, hipStream_t st, bool round_query = true,
@@ -1111,6 +1119,64 @@ int kge_score_neg_shared_bwd_accum(const kge_tables* t, kge_index s, kge_index p
                                   (const long long*)drop, (const long long*)repeat, num_repeat, gout, ldg, scores, lds,
                                   grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, workspace, workspace_bytes,
                                   (hipStream_t)stream);
+}
+
+// ---- relation prediction: KgeModel.score_so (kge_model.py:727-747) ----
+// the checks both entries share, in the order the header lists them; *done: nothing to launch
+static int check_so(const kge_tables* t, const kge_index& s, const kge_index& o, int64_t n, const kge_index& rels,
+                    int64_t m, int64_t workspace_bytes, bool* done) {
+  *done = false;
+  int rc = check_tables(t, true);
+  if (rc) return rc;
+  if (n < 0 || m < 0 || workspace_bytes < 0) return KGE_ERR_INVALID_ARG;
+  if (!rels.ptr && m != t->num_rel) return KGE_ERR_INVALID_ARG;
+  if (n == 0 || m == 0) {
+    *done = true;
+    return KGE_OK;
+  }
+  if ((rc = check_index(s, false)) || (rc = check_index(o, false)) || (rc = check_index(rels, true))) return rc;
+  return KGE_OK;
+}
+
+int64_t kge_score_so_workspace_bytes(const kge_tables* t, int64_t n, int64_t m) {
+  (void)t, (void)n, (void)m;
+  return 0;  // cos / sin of RotatE's phases live in the LDS tile; gout and the scores are read in place
+}
+
+int kge_score_so(const kge_tables* t, kge_index s, kge_index o, int64_t n, kge_index rels, int64_t m, float* out,
+                 int64_t ldo, void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  bool done;
+  int rc = check_so(t, s, o, n, rels, m, workspace_bytes, &done);
+  if (rc) return rc;
+  if (ldo < m || (n * m > 0 && !out)) return KGE_ERR_INVALID_ARG;
+  if (done) return KGE_OK;
+  if (!so_tables_ok(t->scorer, t->dtype, t->dim)) return KGE_ERR_UNSUPPORTED;
+  const int64_t need = kge_score_so_workspace_bytes(t, n, m);
+  if (need > 0 && (!workspace || workspace_bytes < need)) return KGE_ERR_WORKSPACE;
+  return run_so(t->scorer, t->dtype, ent_op(t, s), rel_op(t, rels), ent_op(t, o), (int)t->dim, (int)t->rel_dim, n, m,
+                t->l_norm, out, ldo, (hipStream_t)stream);
+}
+
+int kge_score_so_bwd_accum(const kge_tables* t, kge_index s, kge_index o, int64_t n, kge_index rels, int64_t m,
+                           const float* gout, int64_t ldg, const float* scores, int64_t lds, float* grad_ent,
+                           int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  bool done;
+  int rc = check_so(t, s, o, n, rels, m, workspace_bytes, &done);
+  if (rc) return rc;
+  if (n * m > 0 && (!gout || !grad_ent || !grad_rel)) return KGE_ERR_INVALID_ARG;
+  if (ldg < m || (scores && lds < m)) return KGE_ERR_INVALID_ARG;
+  if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
+  if (done) return KGE_OK;
+  if (!so_tables_ok(t->scorer, t->dtype, t->dim) || t->dtype != KGE_F32 || t->dim > 1024) return KGE_ERR_UNSUPPORTED;
+  if (so_bwd_needs_scores(t->scorer, t->l_norm) && !scores) return KGE_ERR_INVALID_ARG;
+  const int64_t need = kge_score_so_workspace_bytes(t, n, m);
+  if (need > 0 && (!workspace || workspace_bytes < need)) return KGE_ERR_WORKSPACE;
+  return run_so_bwd_accum(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, rels), ent_op(t, o), (int)t->dim,
+                          (int)t->rel_dim, n, m, gout, ldg, scores, lds, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld,
+                          (hipStream_t)stream);
 }
 
 // ---- LookupEmbedder.embed: gathered entity rows and relation rows of a batch, one launch

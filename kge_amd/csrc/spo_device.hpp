@@ -1,4 +1,4 @@
-// spo_device.hpp -- device pieces of the row-wise scoring kernels (score_spo.hip, score_neg_shared.hip): one
+// spo_device.hpp -- device pieces of the row-wise scoring kernels (score_spo.hip, score_neg_shared.hip, score_so.hip): one
 // lane's chunk of 8 coordinates, the fixed side of a triple, the per-chunk arithmetic and the group butterfly.  One
 // definition, so that every kernel built from them produces the same bits.
 #pragma once
@@ -61,6 +61,28 @@ __device__ __forceinline__ Fixed prep_chunk(int slot, const f32x8& e0, const f32
     }
   }
   return F;
+}
+
+// score_so.hip: the query q(s, r) of one chunk as prep_chunk<SCORER>(2, ...) forms it, for a relation row that was
+// staged once and is shared by many (s, o) pairs.  RotatE: r0 / r1 are cos / sin of the row's phases (sincos_canon
+// evaluated where the row was staged, not per pair) and enter the expressions of prep_chunk above unchanged; the other
+// scorers: prep_chunk itself.  Same operations in the same order (-ffp-contract=off): the same bits.
+template <int SCORER>
+__device__ __forceinline__ Fixed prep_chunk_staged(const f32x8& e0, const f32x8& e1, const f32x8& r0,
+                                                   const f32x8& r1) {
+  if constexpr (SCORER != KGE_ROTATE) {
+    return prep_chunk<SCORER>(2, e0, e1, r0, r1);
+  } else {
+    Fixed F;
+    F.f0 = r0; F.f1 = r1; F.f2 = e0; F.f3 = e1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float cs = r0.v[i], sn = r1.v[i];
+      F.f0.v[i] = e0.v[i] * cs - e1.v[i] * sn;
+      F.f1.v[i] = e0.v[i] * sn + e1.v[i] * cs;
+    }
+    return F;
+  }
 }
 
 // accumulate one chunk (x0/x1 = halves of the varying entity row) into the lane partial P

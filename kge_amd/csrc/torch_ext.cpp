@@ -100,6 +100,55 @@ at::Tensor score_spo(const at::Tensor& ent, const at::Tensor& rel, int64_t score
   return out;
 }
 
+// KgeModel.score_so (kge_model.py:727-747): [n, m] scores of (s[i], rels[j], o[i]); rels absent = all relations
+at::Tensor score_so(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t flags,
+                    const at::Tensor& s, const at::Tensor& o, const c10::optional<at::Tensor>& rels) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, flags);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1, m = -1;
+  const kge_index si = index_of(s, ent, keep, &n), oi = index_of(o, ent, keep, &n);
+  const kge_index ri = index_of(rels, ent, keep, &m);
+  if (m < 0) m = t.num_rel;
+  at::Tensor out = empty_f32({n, m}, ent);
+  check(kge_score_so(&t, si, oi, n, ri, m, out.data_ptr<float>(), m > 0 ? m : 1, nullptr, 0, stream_of(ent)),
+        "kge_score_so");
+  return out;
+}
+
+// its backward, accumulated into the dense float32 table gradients; false where the kernel declines the tables
+bool score_so_bwd_accum(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, const at::Tensor& s,
+                        const at::Tensor& o, const c10::optional<at::Tensor>& rels, const at::Tensor& gout,
+                        const c10::optional<at::Tensor>& scores, at::Tensor grad_ent, at::Tensor grad_rel) {
+  const kge_tables t = tables_of(ent, rel, scorer, l_norm, 0);
+  std::vector<at::Tensor> keep;
+  int64_t n = -1, m = -1;
+  const kge_index si = index_of(s, ent, keep, &n), oi = index_of(o, ent, keep, &n);
+  const kge_index ri = index_of(rels, ent, keep, &m);
+  if (m < 0) m = t.num_rel;
+  const bool has_sc = scores.has_value() && scores->defined();
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.dim() == 2 && gout.size(0) == n &&
+                  gout.size(1) == m && (m <= 1 || gout.stride(1) == 1),
+              "kge_amd: score_so_bwd_accum: gout is an [n, m] float32 GPU tensor with unit inner stride");
+  TORCH_CHECK(!has_sc || (scores->is_cuda() && scores->scalar_type() == at::kFloat && scores->dim() == 2 &&
+                          scores->size(0) == n && scores->size(1) == m && (m <= 1 || scores->stride(1) == 1)),
+              "kge_amd: score_so_bwd_accum: scores is an [n, m] float32 GPU tensor with unit inner stride");
+  for (const at::Tensor* g : {&grad_ent, &grad_rel})
+    TORCH_CHECK(g->is_cuda() && g->scalar_type() == at::kFloat && g->dim() == 2 && g->stride(1) == 1,
+                "kge_amd: score_so_bwd_accum: the table gradients are float32 GPU matrices");
+  TORCH_CHECK(grad_ent.size(0) == ent.size(0) && grad_ent.size(1) == ent.size(1) && grad_rel.size(0) == rel.size(0) &&
+                  grad_rel.size(1) == rel.size(1),
+              "kge_amd: score_so_bwd_accum: the table gradients have the tables' shapes");
+  const int64_t one = m > 0 ? m : 1;
+  const int rc = kge_score_so_bwd_accum(&t, si, oi, n, ri, m, gout.data_ptr<float>(), n > 1 ? gout.stride(0) : one,
+                                        has_sc ? scores->data_ptr<float>() : nullptr,
+                                        has_sc ? (n > 1 ? scores->stride(0) : one) : 0, grad_ent.data_ptr<float>(),
+                                        grad_ent.stride(0), grad_rel.data_ptr<float>(), grad_rel.stride(0), nullptr, 0,
+                                        stream_of(ent));
+  if (rc == KGE_ERR_UNSUPPORTED) return false;
+  check(rc, "kge_score_so_bwd_accum");
+  return true;
+}
+
 // combine: 1 = sp_ (a = s), 2 = _po (a = o), 3 = both blocks [n, 2 m] (a = s, b = o)
 at::Tensor score_pairs(const at::Tensor& ent, const at::Tensor& rel, int64_t scorer, double l_norm, int64_t flags,
                        int64_t combine, const at::Tensor& a, const at::Tensor& p, const c10::optional<at::Tensor>& b,
@@ -692,6 +741,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("abi_version", []() { return kge_abi_version(); });
   mod.def("score_spo", &score_spo, "KgeModel.score_spo: [n] scores");
   mod.def("score_pairs", &score_pairs, "KgeModel.score_sp / score_po / score_sp_po: [n, m] / [n, 2 m] scores");
+  mod.def("score_so", &score_so, "KgeModel.score_so: [n, m] scores of (s[i], rels[j], o[i]); rels None = all relations");
+  mod.def("score_so_bwd_accum", &score_so_bwd_accum, "its backward into the dense table gradients; False: declined");
   mod.def("queries_bytes", &queries_bytes);
   mod.def("build_queries_group", &build_queries_group);
   mod.def("score_queries_group", &score_queries_group);

@@ -9,6 +9,7 @@ Function <-> reference map (paths relative to the reference tree):
   score_emb                                        RelationalScorer.score_emb  kge_model.py:151-213
   score_neg                                        BatchNegativeSample.score   kge/util/sampler.py:263-306
   score_neg_shared                                 Naive/DefaultSharedNegativeSample.score  kge/util/sampler.py:428-463, 537-578
+  score_so                                         KgeModel.score_so           kge/model/kge_model.py:727-747
   rank_counts                                      EntityRankingJob._filter_and_rank  kge/job/eval_entity_ranking.py:533-596
 """
 import ctypes
@@ -22,7 +23,7 @@ from . import _lib
 from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT_QUERY, I32, I64, PO_,
                    RESCAL_MAX_DIM, SCORERS, TUCKER3_MAX_BASE_DIM, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
 
-__all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "shared_samples",
+__all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "score_so", "shared_samples",
            "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "neg_sample", "kvsall_collate", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
            "FLAG_SPLIT_QUERY", "reserve_cus", "Queries", "build_queries", "score_queries", "ScorePipeline"]
 
@@ -1058,6 +1059,69 @@ def score_neg_shared_bwd_accum(t: Tables, s, p, o, slot: int, unique, drop, repe
         return False
     if rc:
         _lib.check(rc, "kge_score_neg_shared_bwd_accum")
+    return True
+
+
+# ---- relation prediction: KgeModel.score_so (kge_model.py:727-747) ---------------------------------------------------
+SO_SCORERS = ("complex", "distmult", "transe", "rotate")
+
+
+def score_so_supported(scorer: str, dtype, d: int, n: int) -> bool:
+    """Does kge_score_so take these tables and `n` pairs?  (ComplEx / DistMult / TransE / RotatE; a relation row that
+    fits the LDS tile: float32 d <= 1024, bfloat16 d <= 2048; at most 65535 tiles of 32 pairs.)"""
+    limit = {torch.float32: 1024, torch.bfloat16: 2048}.get(dtype)
+    return scorer in SO_SCORERS and limit is not None and d <= limit and n <= 65535 * 32
+
+
+def _so_args(t, s, o, rels, what):
+    keep = []
+    si, oi = _index(s, t.device, keep), _index(o, t.device, keep)
+    n = _same_len(keep[:2], what)
+    ri = _index(rels, t.device, keep)
+    m = t.rel.shape[0] if rels is None else keep[-1].numel()
+    return keep, si, oi, n, ri, m
+
+
+def score_so(t: Tables, s, o, rels=None, out=None) -> torch.Tensor:
+    """[n, m] scores of (s[i], rels[j], o[i]) -- rels None: all relations --, each bit-identical to score_spo on that
+    triple, without the three [n m, d] repeats of the reference's composition (kge_model.py:202-209): a workgroup
+    stages a tile of relation rows once and its pairs walk them (kge_score_so).  `out`: an [n, m] float32 view with
+    unit inner stride to write into."""
+    keep, si, oi, n, ri, m = _so_args(t, s, o, rels, "score_so")
+    if out is None:
+        out = _empty((n, m), t.device)
+    elif (out.shape != (n, m) or out.dtype != torch.float32 or out.device != t.device
+          or (m > 1 and out.stride(1) != 1)):
+        raise ValueError("kge_amd: score_so: out must be an [n, m] float32 view with unit inner stride")
+    with _on_device(t.device):
+        tc = t.c()
+        _lib.check(_lib.lib().kge_score_so(ctypes.byref(tc), si, oi, n, ri, m, out.data_ptr(),
+                                           out.stride(0) if n > 1 else max(m, 1), None, 0, _stream(t.device)),
+                   "kge_score_so")
+    return out
+
+
+def score_so_bwd(t: Tables, s, o, rels, gout, scores, grad_ent, grad_rel) -> bool:
+    """Backward of score_so accumulated straight into the dense table gradients `grad_ent` [E, d] and `grad_rel`
+    [R, d_r] (f32, modified in place); False if the kernel does not take the tables (bf16, d > 1024)."""
+    keep, si, oi, n, ri, m = _so_args(t, s, o, rels, "score_so_bwd")
+    gout = gout.to(device=t.device, dtype=torch.float32)
+    if gout.dim() != 2 or gout.shape != (n, m) or (m > 1 and gout.stride(1) != 1) or (n > 1 and gout.stride(0) < m):
+        gout = gout.contiguous().view(n, m)  # (an expanded gradient, e.g. of .sum(): rows of their own)
+    sc = None
+    if scores is not None:
+        sc = scores if (scores.dim() == 2 and (m <= 1 or scores.stride(1) == 1)) else scores.contiguous().view(n, m)
+    with _on_device(t.device):
+        tc = t.c()
+        rc = _lib.lib().kge_score_so_bwd_accum(
+            ctypes.byref(tc), si, oi, n, ri, m, gout.data_ptr(), gout.stride(0) if n > 1 else max(m, 1),
+            None if sc is None else sc.data_ptr(), 0 if sc is None else (sc.stride(0) if n > 1 else max(m, 1)),
+            grad_ent.data_ptr(), grad_ent.stride(0), grad_rel.data_ptr(), grad_rel.stride(0), None, 0,
+            _stream_handle(t.device))
+    if rc == _lib.KGE_ERR_UNSUPPORTED:
+        return False
+    if rc:
+        _lib.check(rc, "kge_score_so_bwd_accum")
     return True
 
 

@@ -18,8 +18,9 @@ from kge.model.transh import transh_set_relation_embedder_dim
 
 from .. import engine
 from ..model import (BF16Shadow, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared,
-                     _ScorePairs, _ScoreSPO, ConveNetOps, ConveRoutes, Tucker3Routes, ce_fused_dropout, fused_loss_rows,
-                     neg_blocks_fusable, neg_shared_fusable, predict_filters, topk_composed)
+                     _ScorePairs, _ScoreSO, _ScoreSPO, ConveNetOps, ConveRoutes, Tucker3Routes, ce_fused_dropout,
+                     fused_loss_rows, neg_blocks_fusable, neg_shared_fusable, predict_filters, score_so_fusable,
+                     topk_composed)
 
 
 class _HipScorer(RelationalScorer):
@@ -285,6 +286,19 @@ class _FusedScoring:
         ent, rel = self._w()
         return _ScorePairs.apply(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, s,
                                  self._fwd_tables(), self._padded())
+
+    def score_so(self, s: Tensor, o: Tensor, p: Tensor = None) -> Tensor:
+        """KgeModel.score_so (kge_model.py:727-747) from kge_score_so: what hip_KvsAll calls for `s_o` queries and the
+        reference sampler for the relation slot under `negative_sampling.implementation: batch`.  The reference's own
+        composition (kge_model.py:202-209) wherever the kernel does not apply (other scorers, dropout, CPU, bf16 tables
+        with a recorded gradient)."""
+        if not self._fused():
+            return super().score_so(s, o, p)
+        ent, rel = self._w()
+        if not score_so_fusable(self._scorer.name, ent, rel, s.numel()):
+            return super().score_so(s, o, p)
+        return _ScoreSO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, o, p,
+                              self._touched_pair() if torch.is_grad_enabled() else None)
 
     # filtered top-k link prediction (kge_topk): score_sp / score_po + the masking of _filter_and_rank + torch.topk
     def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):

@@ -236,7 +236,7 @@ class KgeModel(torch.nn.Module):
 
     def set_touched_rows(self, pair, rel_pair=None):
         """`pair` = kge_amd.optim.Adagrad.enable_touched_rows(entity table) -> (grad, bitmap), or None to switch it off:
-        score_spo, score_neg and score_neg_blocks hand it to their autograd nodes, whose backward then accumulates the
+        score_spo, score_neg, score_neg_blocks and score_so hand it to their autograd nodes, whose backward then accumulates the
         entity gradient into the persistent `grad`, marks the rows in `bitmap` and leaves the table's `.grad` None
         (DESIGN.md section 25).  Shared samples (score_neg_shared) keep the dense gradient: do not mix them with it.
         `rel_pair` = kge_amd.optim.SparseAdam.enable_touched_rows(relation table): the relation gradient goes the same
@@ -524,7 +524,17 @@ class KgeModel(torch.nn.Module):
                     label_smoothing: float = 0.0) -> Tensor:
         return self._bce_rows("po", o, p, lbl_rowptr, lbl_col, offset, label_smoothing)
 
+    # kge_score_so behind score_so (False: always the composed path; tests and tools/score_so_probe.py compare the two)
+    fused_score_so = True
+
     def score_so(self, s: Tensor, o: Tensor, p: Tensor = None) -> Tensor:
+        """[n, R] scores of (s_i, ?, o_i) against all relations, or [n, len(p)] against the relations `p`
+        (kge_model.py:727-747): kge_score_so where the lookups are plain, the parameters on a GPU and the scorer one of
+        ComplEx / DistMult / TransE / RotatE; else composed as the reference does (kge_model.py:202-209)."""
+        ent, rel = self._entity_embedder.weight, self._relation_embedder.weight
+        if self.fused_score_so and self._fused() and score_so_fusable(self._scorer.name, ent, rel, s.numel()):
+            return _ScoreSO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, o, p,
+                                  self._touched_rows if torch.is_grad_enabled() else None)
         se, oe = self._entity_embedder.embed(s), self._entity_embedder.embed(o)
         pe = self._relation_embedder.embed_all() if p is None else self._relation_embedder.embed(p)
         return self._scorer.score_emb(se, pe, oe, combine="s_o")
@@ -1228,6 +1238,48 @@ class _ScoreNegShared(torch.autograd.Function):
                 _scatter_rows(gr, tr[1], g_p)
                 ge, gr = ge.to(ctx.t.ent.dtype), gr.to(ctx.t.rel.dtype)
         return None, None, ge, gr, None, None, None, None, None, None, None
+
+
+class _ScoreSO(torch.autograd.Function):
+    """[n, m] scores of (s[i], rels[j], o[i]) -- rels None: all relations -- = KgeModel.score_so (kge_model.py:727-747)
+    from kge_score_so: the relation rows staged once per workgroup, none of the three [n m, d] repeats of the
+    reference's composition (kge_model.py:202-209) in either pass; backward = kge_score_so_bwd_accum (complete table
+    gradients, one row flush per (pair, tile) and (relation, tile))."""
+
+    @staticmethod
+    def forward(ctx, name, l_norm, ent, rel, s, o, rels, touched=None):
+        t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
+        out = engine.score_so(t, s, o, rels)
+        ctx.t, ctx.idx = t, (s, o, rels)
+        ctx.touched = None if touched is None else _touched_pair(t, touched)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        s, o, rels = ctx.idx
+        (scores,) = ctx.saved_tensors
+        if ctx.touched is not None:  # the accumulate kernel on the persistent buffers, or nothing
+            p = rels if rels is not None else torch.arange(ctx.t.rel.shape[0], device=ctx.t.rel.device)
+            ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o)
+            if not engine.score_so_bwd(ctx.t, s, o, rels, gout, scores, ge, gr):
+                raise RuntimeError("kge_amd: kge_score_so_bwd_accum declined a shape the touched-row step admitted")
+            return None, None, None, None if rel_kept else gr, None, None, None, None
+        ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
+        if not engine.score_so_bwd(ctx.t, s, o, rels, gout, scores, ge, gr):
+            raise RuntimeError("kge_amd: kge_score_so_bwd_accum declined tables score_so admitted")
+        return None, None, ge, gr, None, None, None, None
+
+
+def score_so_fusable(name: str, ent: torch.Tensor, rel: torch.Tensor, n: int) -> bool:
+    """Where KgeModel.score_so runs kge_score_so: one of its four scorers, tables on a GPU that the kernel takes, and
+    -- with a recorded gradient -- tables kge_score_so_bwd_accum takes (float32, dim <= 1024); anything else goes the
+    composed way (bf16 tables under autograd included, as score_neg does where its backward declines)."""
+    if not ent.is_cuda or not engine.score_so_supported(name, ent.dtype, ent.shape[1], n):
+        return False
+    if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
+        return ent.dtype == torch.float32 and rel.dtype == torch.float32 and ent.shape[1] <= 1024
+    return True
 
 
 class _ScoreNegBlocks(torch.autograd.Function):
