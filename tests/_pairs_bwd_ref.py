@@ -295,10 +295,10 @@ def gemm_split(M, N, K, scratch_floats):
     return -(-K // kc), kc
 
 
-def gemm_vec(lda, ldb):
+def gemm_vec(lda, ldb, es=4, al=16):
     """`vec` of run_gemm32 on float32 operands whose base addresses are 16-byte aligned (the tests' are): both row
-    pitches whole 16-byte pieces"""
-    return int((lda * 4) % 16 == 0 and (ldb * 4) % 16 == 0)
+    pitches whole 16-byte pieces.  (es, al) = (2, 8): its `in16` rule, bf16 operands in 8-byte pieces."""
+    return int((lda * es) % al == 0 and (ldb * es) % al == 0)
 
 
 def dot_branches(case):

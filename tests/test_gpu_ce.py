@@ -129,6 +129,9 @@ def _grads64(model, ent16, rel16, a, p, lab, direction, g):
 
 @pytest.mark.parametrize("model,d,E,R,n,scale", CASES[:2] + CASES[4:5] + CASES[6:8])
 def test_ce_bwd(eng, model, d, E, R, n, scale):
+    """kge_ce_bwd against float64 autograd (norm-wise) and against the unfused mixed-precision backward,
+    score_pairs_bwd on bf16 tables -- a yardstick that is itself asserted elementwise against float64, inside a derived
+    bound, in tests/test_gpu_pairs_bwd16.py."""
     ent, rel, s, p, o = _case(3 * d + n, model, d, E, R, n, scale)
     T = _tables(eng, model, ent, rel)
     rng = np.random.default_rng(1)
