@@ -1485,6 +1485,74 @@ int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
                             const float* scores, int64_t lds, float* grad_ent,
                             int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld,
                             void* stream);
+
+/* ---- Embedder dropout inside the triple-wise kernels -----------------------------------------------------------------
+ * LookupEmbedder._postprocess applies torch.nn.Dropout to every gathered row (kge/model/embedder/
+ * lookup_embedder.py:96-105).  The entries below compute that mask inside the kernel from a counter-based generator: no
+ * mask and no gathered row goes to memory, and a backward regenerates the mask of its forward from (seed, call).
+ *
+ * THE MASK (one definition; kge_amd/csrc/philox.hpp is its device form, tests/_dropout_ref.py its numpy restatement).
+ * For a gathered row occurrence, element c of the row is DROPPED iff r < thr, where
+ *   r       = word (c % 4) of Philox4x32-10(counter, key)        (the generator of kge_neg_sample)
+ *   counter = (c / 4, occ, (uint32)call, role)                    role: 0 = the s row, 1 = the p row, 2 = the o row
+ *   key     = (seed low 32, (seed high 32) ^ 0x44524F50)          (apart from kge_neg_sample's streams of the same seed)
+ *   thr     = (uint32)floor(p * 2^32), computed in double          p = p_ent for entity rows, p_rel for relation rows
+ * A kept element becomes x * scale with scale = 1.0f / (1.0f - p) (one float32 division on the host, one float32
+ * multiply in the kernel); a dropped element becomes x * 0.0f: the value and sign torch.nn.Dropout produces.  p == 0 for
+ * a table means thr = 0, scale = 1: that table's rows pass through untouched, bit for bit.  For RotatE the relation
+ * mask lies on the rel_dim = dim / 2 phases.
+ *
+ * Occurrences:
+ *   kge_score_spo_dropout    the three rows of triple i: occ = i, roles 0 / 1 / 2 (the law of the reference's three
+ *                            embed() calls, kge_model.py:663-680)
+ *   kge_score_neg_dropout    the two uncorrupted rows of positive i: occ = i, masked ONCE per positive (as score_sp /
+ *                            score_po embed them once under `implementation: batch`, sampler.py:307-362); the corrupted
+ *                            row of (i, k): role = slot, occ = i * num_neg + k (as under `implementation: triple`,
+ *                            sampler.py:291-306).  The marginal law of every element is the reference's (kept with
+ *                            probability 1 - p, scaled by 1 / (1 - p)); its own implementations differ in the joint law.
+ *
+ * KGE_ERR_UNSUPPORTED, nothing launched: an occurrence number or n * num_neg at or above 2^32; p_ent or p_rel outside
+ * [0, 1), or both 0; bf16 tables; TransH and RESCAL tables; dim > 1024 (the scoring and backward entries).  A NULL
+ * kge_dropout: KGE_ERR_INVALID_ARG.  A TransH or RESCAL table is declined in front of every other check, as by every
+ * entry without such a kernel; otherwise every KGE_ERR_INVALID_ARG of the undropped entry is reported first. */
+typedef struct kge_dropout {
+  float p_ent, p_rel; /* drop probabilities of the entity / relation embedder, each in [0, 1), not both 0 */
+  uint64_t seed;      /* the model's dropout seed                                                         */
+  uint64_t call;      /* one number per fused call; the backward passes its forward's                     */
+} kge_dropout;
+
+/* embed() in training mode (lookup_embedder.py:96-105): out[i, :] = mask(table[idx[i], :]) for the occurrences
+ * occ0 .. occ0 + n of `role` (0 / 1 / 2).  table: 0 = the entity table (p_ent), 1 = the relation table (p_rel).
+ * out: float32 [n, dim or rel_dim], row pitch out_ld elements.  Useful on its own, and the device-side statement of the
+ * mask.  The other table's probability may be 0 or not; the table's own may be 0 (a plain gather). */
+int kge_embed_dropout(const kge_tables* t, int table, kge_index idx, int64_t n, int role, int64_t occ0,
+                      const kge_dropout* dropout, float* out, int64_t out_ld, void* stream);
+
+/* kge_score_spo / kge_score_neg (kge_model.py:663-680; sampler.py:263-306) on rows under the mask above, the dropout of
+ * LookupEmbedder._postprocess (lookup_embedder.py:96-105) on every row the reference's embed() gathers.  The mask is
+ * applied where a row chunk reaches the registers; everything after it is the arithmetic of the undropped kernel in the
+ * same order: the scores carry the bits kge_score_spo / kge_score_neg return on tables that hold the masked rows.
+ * float32 ComplEx, DistMult, TransE (every l_norm) and RotatE tables, dim <= 1024. */
+int kge_score_spo_dropout(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, float* out,
+                          const kge_dropout* dropout, void* stream);
+int kge_score_neg_dropout(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                          const void* neg, int32_t neg_itype, int64_t neg_ld, int64_t num_neg, float* out, int64_t ldo,
+                          const kge_dropout* dropout, void* stream);
+
+/* kge_score_spo_bwd_accum / kge_score_neg_bwd_accum of the two entries above (lookup_embedder.py:96-105 backward;
+ * sampler.py:263-306, train_negative_sampling.py:142-163): the masks of the forward's (seed, call) are regenerated, the
+ * row gradients are evaluated on the masked rows, multiplied by the row's mask factor and accumulated into grad_ent /
+ * grad_rel as the undropped entries do, with the same register summing of the fixed rows.  `scores`: the DROPOUT
+ * forward's output.  A fully masked row still receives its (zero) atomics. */
+int kge_score_spo_dropout_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n,
+                                    const float* gout, const float* scores, float* grad_ent, int64_t grad_ent_ld,
+                                    float* grad_rel, int64_t grad_rel_ld, const kge_dropout* dropout, void* stream);
+int kge_score_neg_dropout_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                                    const void* neg, int32_t neg_itype, int64_t neg_ld, int64_t num_neg,
+                                    const float* gout, int64_t ldg, const float* scores, int64_t lds, float* grad_ent,
+                                    int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld,
+                                    const kge_dropout* dropout, void* stream);
+
 /* The same backward with the [n, num_neg] occurrences SORTED by the entity they corrupt: `order` = int64 [n * num_neg]
  * (device), the positions i * num_neg + k in ascending neg[i, k] (any order among equal ids: kge_neg_order above).  kge_score_neg_bwd_accum issues one float atomic per element and occurrence into
  * grad_ent (262 M per slot at the WN18RR shape with 512 x 1000 negatives: 73 % of that training step); here a wave keeps

@@ -132,8 +132,14 @@ class KgeConveNet(ctypes.Structure):
                 ("bn1_eps", ctypes.c_float), ("bn2_eps", ctypes.c_float)]
 
 
+class KgeDropout(ctypes.Structure):
+    _fields_ = [("p_ent", ctypes.c_float), ("p_rel", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("call", ctypes.c_uint64)]
+
+
 # every symbol include/kge_amd.h declares: name -> (restype, argtypes)
 _PT = ctypes.POINTER(KgeTables)
+_PD = ctypes.POINTER(KgeDropout)
 PROTOTYPES = {
     "kge_abi_version": (ctypes.c_int, []),
     "kge_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -327,6 +333,15 @@ PROTOTYPES = {
     "kge_score_neg_bwd_accum": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, ctypes.c_int, c_vp,
                                                ctypes.c_int32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                                                c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kge_embed_dropout": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, c_i64, ctypes.c_int, c_i64, _PD, c_vp, c_i64, c_vp]),
+    "kge_score_spo_dropout": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, _PD, c_vp]),
+    "kge_score_neg_dropout": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, ctypes.c_int, c_vp,
+                                             ctypes.c_int32, c_i64, c_i64, c_vp, c_i64, _PD, c_vp]),
+    "kge_score_spo_dropout_bwd_accum": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_vp, c_vp,
+                                                       c_i64, c_vp, c_i64, _PD, c_vp]),
+    "kge_score_neg_dropout_bwd_accum": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, ctypes.c_int, c_vp,
+                                                       ctypes.c_int32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                                       c_vp, c_i64, c_vp, c_i64, _PD, c_vp]),
     "kge_neg_order": (ctypes.c_int, [c_vp, ctypes.c_int32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "kge_score_neg_bwd_accum_sorted": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, ctypes.c_int, c_vp,
                                                       ctypes.c_int32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,

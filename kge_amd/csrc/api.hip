@@ -4,9 +4,24 @@
 #include <dlfcn.h>
 #include "common.hpp"
 #include "bf16_queries.hpp"
+#include "philox.hpp"
+#include <cmath>
 #include <cstdlib>
 
 namespace kge {
+// embedder dropout (philox.hpp): embed.hip, score_spo.hip, bwd.hip
+int run_embed_dropout(const float* table, long long ld, const Index& idx, long long n, int d, unsigned occ0,
+                      const RowMask& m0, const DropKey& dk, float* out, long long ldo, hipStream_t st);
+int run_spo_drop(int scorer, bool neg_mode, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                 long long n, int slot, const void* neg, int neg_itype, long long neg_ld, long long K, float lp,
+                 float* out, long long ldo, const DropKey& dk, hipStream_t st);
+int run_spo_bwd_accum_drop(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                           long long n, const float* gout, const float* scores, float* ge, long long ge_ld, float* gr,
+                           long long gr_ld, const DropKey& dk, hipStream_t st);
+int run_neg_bwd_accum_drop(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                           long long n, int slot, const void* neg, int neg_itype, long long neg_ld, long long K,
+                           const float* gout, long long ldg, const float* scores, long long lds, float* ge,
+                           long long ge_ld, float* gr, long long gr_ld, const DropKey& dk, hipStream_t st);
 // tucker3.hip
 int run_tucker3_project(const float* Bm, long long ldb, const Index& idx, const float* W, long long ldw, int d, int dr,
                         long long n, float* out, long long ldo, hipStream_t st);
@@ -2853,6 +2868,122 @@ int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
   return run_neg_bwd_accum(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
                            (int)t->rel_dim, n, slot, neg, neg_itype, neg_ld, num_neg, gout, ldg, scores,
                            lds, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, (hipStream_t)stream);
+}
+
+// ---- embedder dropout inside the triple-wise kernels (include/kge_amd.h "Embedder dropout"; philox.hpp) ----
+// the gate shared by the five entries, called after the undropped entry's own argument checks: `occs` = the number of
+// occurrences the call numbers from `occ0`
+static int check_dropout(const kge_tables* t, const kge_dropout* dr, int64_t occ0, int64_t occs, bool rows_le_1024,
+                         kge::DropKey* dk) {
+  if (!dr) return KGE_ERR_INVALID_ARG;
+  if (t->scorer == KGE_TRANSH || t->scorer == KGE_RESCAL || t->dtype != KGE_F32) return KGE_ERR_UNSUPPORTED;
+  if (rows_le_1024 && t->dim > 1024) return KGE_ERR_UNSUPPORTED;
+  if (!(dr->p_ent >= 0.0f && dr->p_ent < 1.0f) || !(dr->p_rel >= 0.0f && dr->p_rel < 1.0f)) return KGE_ERR_UNSUPPORTED;
+  if (dr->p_ent == 0.0f && dr->p_rel == 0.0f) return KGE_ERR_UNSUPPORTED;
+  if (occ0 < 0) return KGE_ERR_INVALID_ARG;
+  if (occ0 >= (1LL << 32) || occs > (1LL << 32) || occ0 + occs > (1LL << 32)) return KGE_ERR_UNSUPPORTED;
+  dk->k0 = (unsigned)dr->seed;
+  dk->k1 = (unsigned)(dr->seed >> 32) ^ kge::KGE_DROPOUT_KEY_XOR;
+  dk->call = (unsigned)dr->call;
+  dk->thr_ent = (unsigned)floor((double)dr->p_ent * 4294967296.0);
+  dk->thr_rel = (unsigned)floor((double)dr->p_rel * 4294967296.0);
+  dk->sc_ent = 1.0f / (1.0f - dr->p_ent);
+  dk->sc_rel = 1.0f / (1.0f - dr->p_rel);
+  return KGE_OK;
+}
+
+int kge_embed_dropout(const kge_tables* t, int table, kge_index idx, int64_t n, int role, int64_t occ0,
+                      const kge_dropout* dropout, float* out, int64_t out_ld, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true);  // (a TransH / RESCAL table: KGE_ERR_UNSUPPORTED here, as in every entry without such a kernel)
+  if (rc) return rc;
+  if ((table != 0 && table != 1) || role < 0 || role > 2 || n < 0 || (n > 0 && !out)) return KGE_ERR_INVALID_ARG;
+  const int64_t width = table == 0 ? t->dim : t->rel_dim;
+  if (out_ld < width) return KGE_ERR_INVALID_ARG;
+  if ((rc = check_index(idx, false, n))) return rc;
+  kge::DropKey dk;
+  if ((rc = check_dropout(t, dropout, occ0, n, false, &dk))) return rc;
+  if (n == 0) return KGE_OK;
+  const kge::RowMask m0 = table == 0 ? kge::ent_mask(dk, (unsigned)role, 0u)
+                                     : kge::RowMask{0u, (unsigned)role, dk.thr_rel, dk.sc_rel};
+  return run_embed_dropout((const float*)(table == 0 ? t->ent : t->rel), table == 0 ? t->ent_ld : t->rel_ld,
+                           make_index(idx), n, (int)width, (unsigned)occ0, m0, dk, out, out_ld, (hipStream_t)stream);
+}
+
+int kge_score_spo_dropout(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, float* out,
+                          const kge_dropout* dropout, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true);  // (a TransH / RESCAL table: KGE_ERR_UNSUPPORTED here, as in every entry without such a kernel)
+  if (rc) return rc;
+  if (n < 0 || (!out && n > 0)) return KGE_ERR_INVALID_ARG;
+  if (n > 0 && ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false)))) return rc;
+  kge::DropKey dk;
+  if ((rc = check_dropout(t, dropout, 0, n, true, &dk))) return rc;
+  if (n == 0) return KGE_OK;
+  return run_spo_drop(t->scorer, false, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, (int)t->rel_dim, n, 2,
+                      nullptr, 0, 0, 0, t->l_norm, out, 0, dk, (hipStream_t)stream);
+}
+
+int kge_score_neg_dropout(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                          const void* neg, int32_t neg_itype, int64_t neg_ld, int64_t num_neg, float* out, int64_t ldo,
+                          const kge_dropout* dropout, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true);  // (a TransH / RESCAL table: KGE_ERR_UNSUPPORTED here, as in every entry without such a kernel)
+  if (rc) return rc;
+  if (n < 0 || num_neg < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
+  if (n * num_neg > 0 && (!out || !neg)) return KGE_ERR_INVALID_ARG;
+  if (neg_ld < num_neg || ldo < num_neg) return KGE_ERR_INVALID_ARG;
+  if (neg_itype != KGE_I32 && neg_itype != KGE_I64) return KGE_ERR_INVALID_ARG;
+  if (n * num_neg > 0 && ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false))))
+    return rc;
+  kge::DropKey dk;
+  if (num_neg > 0 && n > (1LL << 32) / num_neg) return KGE_ERR_UNSUPPORTED;  // n * num_neg >= 2^32 (no overflow)
+  if ((rc = check_dropout(t, dropout, 0, n * num_neg, true, &dk))) return rc;
+  if (n * num_neg >= (1LL << 32)) return KGE_ERR_UNSUPPORTED;
+  if (n == 0 || num_neg == 0) return KGE_OK;
+  if (n > 65535) return KGE_ERR_UNSUPPORTED;  // grid.y, as kge_score_neg
+  return run_spo_drop(t->scorer, true, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, (int)t->rel_dim, n, slot,
+                      neg, neg_itype, neg_ld, num_neg, t->l_norm, out, ldo, dk, (hipStream_t)stream);
+}
+
+int kge_score_spo_dropout_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n,
+                                    const float* gout, const float* scores, float* grad_ent, int64_t grad_ent_ld,
+                                    float* grad_rel, int64_t grad_rel_ld, const kge_dropout* dropout, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true);  // (a TransH / RESCAL table: KGE_ERR_UNSUPPORTED here, as in every entry without such a kernel)
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!gout || !grad_ent || !grad_rel))) return KGE_ERR_INVALID_ARG;
+  if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
+  if (n > 0 && ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false)))) return rc;
+  kge::DropKey dk;
+  if ((rc = check_dropout(t, dropout, 0, n, true, &dk))) return rc;
+  return run_spo_bwd_accum_drop(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
+                                (int)t->rel_dim, n, gout, scores, grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, dk,
+                                (hipStream_t)stream);
+}
+
+int kge_score_neg_dropout_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                                    const void* neg, int32_t neg_itype, int64_t neg_ld, int64_t num_neg,
+                                    const float* gout, int64_t ldg, const float* scores, int64_t lds, float* grad_ent,
+                                    int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld,
+                                    const kge_dropout* dropout, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true);  // (a TransH / RESCAL table: KGE_ERR_UNSUPPORTED here, as in every entry without such a kernel)
+  if (rc) return rc;
+  if (n < 0 || num_neg < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
+  if (n * num_neg > 0 && (!gout || !neg || !grad_ent || !grad_rel)) return KGE_ERR_INVALID_ARG;
+  if (neg_ld < num_neg || ldg < num_neg || (scores && lds < num_neg)) return KGE_ERR_INVALID_ARG;
+  if (neg_itype != KGE_I32 && neg_itype != KGE_I64) return KGE_ERR_INVALID_ARG;
+  if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
+  if (n * num_neg > 0 && ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false))))
+    return rc;
+  kge::DropKey dk;
+  if (num_neg > 0 && n > (1LL << 32) / num_neg) return KGE_ERR_UNSUPPORTED;  // n * num_neg >= 2^32 (no overflow)
+  if ((rc = check_dropout(t, dropout, 0, n * num_neg, true, &dk))) return rc;
+  if (n * num_neg >= (1LL << 32)) return KGE_ERR_UNSUPPORTED;
+  return run_neg_bwd_accum_drop(t->scorer, t->l_norm, ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim,
+                                (int)t->rel_dim, n, slot, neg, neg_itype, neg_ld, num_neg, gout, ldg, scores, lds,
+                                grad_ent, grad_ent_ld, grad_rel, grad_rel_ld, dk, (hipStream_t)stream);
 }
 
 int kge_neg_order(const void* neg, int32_t neg_itype, int64_t neg_ld, int64_t n, int64_t num_neg, int64_t num_ent,

@@ -15,6 +15,7 @@
 // reduction index streamed through LDS in chunks of 16; each thread owns 4 rows x 2
 // coordinate pairs.
 #include "bwd_device.hpp"
+#include "philox.hpp"
 
 namespace kge {
 
@@ -284,13 +285,15 @@ __global__ __launch_bounds__(256) void bwd_spo_kernel(Operand S, Operand R, Oper
 // element.  d <= 1024 (8 coordinate pairs per lane).
 constexpr int SPA_CH = 32, SPA_NC = 8;
 
-template <int SCORER, int NORM>
-__global__ __launch_bounds__(256) void bwd_spo_accum_kernel(Operand S, Operand R, Operand O, int d, int dr,
-                                                            long long n, float lp,
-                                                            const float* __restrict__ gout,
-                                                            const float* __restrict__ scores,
-                                                            float* __restrict__ ge, long long ge_ld,
-                                                            float* __restrict__ gr, long long gr_ld, int ch) {
+// DROP (kge_score_spo_dropout_bwd_accum): the masks of the forward's (seed, call) are regenerated (philox.hpp: triple i
+// is occurrence i, roles 0 / 1 / 2), the row gradients are evaluated on the masked rows and multiplied by the row's mask
+// factor before they are summed.  A lane owns single columns here, so it evaluates one Philox block per column.
+template <int SCORER, int NORM, bool DROP>
+__device__ __forceinline__ void bwd_spo_accum_body(const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                                                   long long n, float lp, const float* __restrict__ gout,
+                                                   const float* __restrict__ scores, float* __restrict__ ge,
+                                                   long long ge_ld, float* __restrict__ gr, long long gr_ld, int ch,
+                                                   const DropKey& dk) {
   // `ch` triples per wave: SPA_CH for the n*K triples of a negative-sampling batch (runs of equal s / p are
   // summed in registers), fewer when there are few triples -- a wave walks its chunk sequentially (index ->
   // rows -> atomics per triple), and the 512 positives of a batch in 16 chunks of 32 took 77 us of latency
@@ -342,7 +345,17 @@ __global__ __launch_bounds__(256) void bwd_spo_accum_kernel(Operand S, Operand R
       const float o0 = orow[c], o1 = has1 ? orow[hh + c] : 0.f;
       const float r0 = c < rl0 ? rrow[c] : 0.f, r1 = c < rl1 ? rrow[hh + c] : 0.f;
       float ds0, ds1, dp0, dp1, do0, do1;
-      spo_pair_grads<SCORER, NORM>(s0, s1, r0, r1, o0, o1, has1, g, dist, lp, ds0, ds1, dp0, dp1, do0, do1);
+      if constexpr (DROP) {
+        const RowMask ms = ent_mask(dk, 0u, (unsigned)i), mp = rel_mask(dk, (unsigned)i), mo = ent_mask(dk, 2u, (unsigned)i);
+        const float fs0 = drop_factor(c, ms, dk), fs1 = has1 ? drop_factor(hh + c, ms, dk) : 0.f;
+        const float fo0 = drop_factor(c, mo, dk), fo1 = has1 ? drop_factor(hh + c, mo, dk) : 0.f;
+        const float fp0 = c < rl0 ? drop_factor(c, mp, dk) : 0.f, fp1 = c < rl1 ? drop_factor(hh + c, mp, dk) : 0.f;
+        spo_pair_grads<SCORER, NORM>(s0 * fs0, s1 * fs1, r0 * fp0, r1 * fp1, o0 * fo0, o1 * fo1, has1, g, dist, lp, ds0,
+                                     ds1, dp0, dp1, do0, do1);
+        ds0 *= fs0; ds1 *= fs1; dp0 *= fp0; dp1 *= fp1; do0 *= fo0; do1 *= fo1;
+      } else {
+        spo_pair_grads<SCORER, NORM>(s0, s1, r0, r1, o0, o1, has1, g, dist, lp, ds0, ds1, dp0, dp1, do0, do1);
+      }
       as0[k] += ds0;
       as1[k] += ds1;
       ap0[k] += dp0;
@@ -355,6 +368,26 @@ __global__ __launch_bounds__(256) void bwd_spo_accum_kernel(Operand S, Operand R
   flush(gr, gr_ld, run_p, ap0, ap1, rl0, rl1);
 }
 
+template <int SCORER, int NORM>
+__global__ __launch_bounds__(256) void bwd_spo_accum_kernel(Operand S, Operand R, Operand O, int d, int dr,
+                                                            long long n, float lp,
+                                                            const float* __restrict__ gout,
+                                                            const float* __restrict__ scores,
+                                                            float* __restrict__ ge, long long ge_ld,
+                                                            float* __restrict__ gr, long long gr_ld, int ch) {
+  bwd_spo_accum_body<SCORER, NORM, false>(S, R, O, d, dr, n, lp, gout, scores, ge, ge_ld, gr, gr_ld, ch, DropKey{});
+}
+
+template <int SCORER, int NORM>
+__global__ __launch_bounds__(256) void bwd_spo_accum_drop_kernel(Operand S, Operand R, Operand O, int d, int dr,
+                                                                 long long n, float lp, const float* __restrict__ gout,
+                                                                 const float* __restrict__ scores,
+                                                                 float* __restrict__ ge, long long ge_ld,
+                                                                 float* __restrict__ gr, long long gr_ld, int ch,
+                                                                 DropKey dk) {
+  bwd_spo_accum_body<SCORER, NORM, true>(S, R, O, d, dr, n, lp, gout, scores, ge, ge_ld, gr, gr_ld, ch, dk);
+}
+
 // Backward of kge_score_neg (BatchNegativeSample.score, sampler.py:263-306, followed by autograd's
 // scatter-add of the gathered rows): gradients of sum_{i,k} gout[i,k] * score(triple i with `slot`
 // replaced by neg[i,k]) accumulated into the dense table gradients.  One wave per (positive, chunk
@@ -364,12 +397,15 @@ __global__ __launch_bounds__(256) void bwd_spo_accum_kernel(Operand S, Operand R
 // out per negative.  No [n*K, 3] index tensor, no [n*K, d] row-gradient tensors.  d <= 1024.
 constexpr int NGA_CH = 64;
 
-template <int SCORER, int NORM, int SLOT>
-__global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
-    Operand S, Operand R, Operand O, int d, int dr, long long n, const void* __restrict__ neg,
+// DROP (kge_score_neg_dropout_bwd_accum): the fixed rows are masked ONCE where they are loaded (occurrence `row`, roles
+// 1 and 0 / 2) and their summed gradients are multiplied by the regenerated factors at the flush; the corrupted row of
+// (row, kk) carries the mask of occurrence row K + kk, role SLOT, and its gradient is multiplied before the atomic.
+template <int SCORER, int NORM, int SLOT, bool DROP>
+__device__ __forceinline__ void bwd_neg_accum_body(
+    const Operand& S, const Operand& R, const Operand& O, int d, int dr, long long n, const void* __restrict__ neg,
     int neg_itype, long long neg_ld, long long K, int chunks_per_row, int ch, float lp,
     const float* __restrict__ gout, long long ldg, const float* __restrict__ scores, long long lds,
-    float* __restrict__ ge, long long ge_ld, float* __restrict__ gr, long long gr_ld) {
+    float* __restrict__ ge, long long ge_ld, float* __restrict__ gr, long long gr_ld, const DropKey& dk) {
   const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const long long row = w / chunks_per_row;
   if (row >= n) return;
@@ -385,6 +421,7 @@ __global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
   const float* rrow = (const float*)R.base + pi * R.ld;
   float f0[SPA_NC], f1[SPA_NC], r0[SPA_NC], r1[SPA_NC];
   float af0[SPA_NC], af1[SPA_NC], ap0[SPA_NC], ap1[SPA_NC];
+  const RowMask mf = ent_mask(dk, SLOT == 0 ? 2u : 0u, (unsigned)row), mp = rel_mask(dk, (unsigned)row);
 #pragma unroll
   for (int k = 0; k < SPA_NC; ++k) {
     const int c = lane + 64 * k;
@@ -392,6 +429,12 @@ __global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
     f1[k] = c < lim1 ? frow[hh + c] : 0.f;
     r0[k] = c < rl0 ? rrow[c] : 0.f;
     r1[k] = c < rl1 ? rrow[hh + c] : 0.f;
+    if constexpr (DROP) {
+      if (c < hh) f0[k] *= drop_factor(c, mf, dk);
+      if (c < lim1) f1[k] *= drop_factor(hh + c, mf, dk);
+      if (c < rl0) r0[k] *= drop_factor(c, mp, dk);
+      if (c < rl1) r1[k] *= drop_factor(hh + c, mp, dk);
+    }
     af0[k] = af1[k] = ap0[k] = ap1[k] = 0.f;
   }
   for (long long kk = k0; kk < k1; ++kk) {
@@ -407,7 +450,15 @@ __global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
       const int c = lane + 64 * k;
       if (c >= hh) break;
       const bool has1 = c < lim1;
-      const float v0 = vrow[c], v1 = has1 ? vrow[hh + c] : 0.f;
+      float v0 = vrow[c], v1 = has1 ? vrow[hh + c] : 0.f;
+      float fv0 = 1.f, fv1 = 1.f;
+      if constexpr (DROP) {
+        const RowMask mv = ent_mask(dk, (unsigned)SLOT, (unsigned)(row * K + kk));
+        fv0 = drop_factor(c, mv, dk);
+        fv1 = has1 ? drop_factor(hh + c, mv, dk) : 0.f;
+        v0 *= fv0;
+        v1 *= fv1;
+      }
       float ds0, ds1, dp0, dp1, do0, do1;
       if (SLOT == 0)
         spo_pair_grads<SCORER, NORM>(v0, v1, r0[k], r1[k], f0[k], f1[k], has1, g, dist, lp, ds0, ds1, dp0, dp1,
@@ -415,7 +466,11 @@ __global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
       else
         spo_pair_grads<SCORER, NORM>(f0[k], f1[k], r0[k], r1[k], v0, v1, has1, g, dist, lp, ds0, ds1, dp0, dp1,
                                      do0, do1);
-      const float dv0 = SLOT == 0 ? ds0 : do0, dv1 = SLOT == 0 ? ds1 : do1;
+      float dv0 = SLOT == 0 ? ds0 : do0, dv1 = SLOT == 0 ? ds1 : do1;
+      if constexpr (DROP) {
+        dv0 *= fv0;
+        dv1 *= fv1;
+      }
       af0[k] += SLOT == 0 ? do0 : ds0;
       af1[k] += SLOT == 0 ? do1 : ds1;
       ap0[k] += dp0;
@@ -429,6 +484,12 @@ __global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
 #pragma unroll
   for (int k = 0; k < SPA_NC; ++k) {
     const int c = lane + 64 * k;
+    if constexpr (DROP) {
+      if (c < hh) af0[k] *= drop_factor(c, mf, dk);
+      if (c < lim1) af1[k] *= drop_factor(hh + c, mf, dk);
+      if (c < rl0) ap0[k] *= drop_factor(c, mp, dk);
+      if (c < rl1) ap1[k] *= drop_factor(hh + c, mp, dk);
+    }
     if (c < hh) unsafeAtomicAdd(gf + c, af0[k]);
     if (c < lim1) unsafeAtomicAdd(gf + hh + c, af1[k]);
     if (c < rl0) unsafeAtomicAdd(gp + c, ap0[k]);
@@ -436,10 +497,31 @@ __global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
   }
 }
 
-int run_neg_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d,
-                      int dr, long long n, int slot, const void* neg, int neg_itype, long long neg_ld,
-                      long long K, const float* gout, long long ldg, const float* scores, long long lds,
-                      float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st) {
+template <int SCORER, int NORM, int SLOT>
+__global__ __launch_bounds__(256) void bwd_neg_accum_kernel(
+    Operand S, Operand R, Operand O, int d, int dr, long long n, const void* __restrict__ neg,
+    int neg_itype, long long neg_ld, long long K, int chunks_per_row, int ch, float lp,
+    const float* __restrict__ gout, long long ldg, const float* __restrict__ scores, long long lds,
+    float* __restrict__ ge, long long ge_ld, float* __restrict__ gr, long long gr_ld) {
+  bwd_neg_accum_body<SCORER, NORM, SLOT, false>(S, R, O, d, dr, n, neg, neg_itype, neg_ld, K, chunks_per_row, ch, lp,
+                                                gout, ldg, scores, lds, ge, ge_ld, gr, gr_ld, DropKey{});
+}
+
+template <int SCORER, int NORM, int SLOT>
+__global__ __launch_bounds__(256) void bwd_neg_accum_drop_kernel(
+    Operand S, Operand R, Operand O, int d, int dr, long long n, const void* __restrict__ neg,
+    int neg_itype, long long neg_ld, long long K, int chunks_per_row, int ch, float lp,
+    const float* __restrict__ gout, long long ldg, const float* __restrict__ scores, long long lds,
+    float* __restrict__ ge, long long ge_ld, float* __restrict__ gr, long long gr_ld, DropKey dk) {
+  bwd_neg_accum_body<SCORER, NORM, SLOT, true>(S, R, O, d, dr, n, neg, neg_itype, neg_ld, K, chunks_per_row, ch, lp,
+                                               gout, ldg, scores, lds, ge, ge_ld, gr, gr_ld, dk);
+}
+
+static int run_neg_bwd_accum_impl(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d,
+                                  int dr, long long n, int slot, const void* neg, int neg_itype, long long neg_ld,
+                                  long long K, const float* gout, long long ldg, const float* scores, long long lds,
+                                  float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st,
+                                  const DropKey* dk) {
   if (n == 0 || K == 0) return KGE_OK;
   if ((d + 1) / 2 > 64 * SPA_NC) return KGE_ERR_UNSUPPORTED;
   const int norm = norm_mode(lp);
@@ -457,13 +539,17 @@ int run_neg_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, 
   if (cpr > (1LL << 30) || (waves + 3) / 4 > 0x7fffffffLL) return KGE_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((waves + 3) / 4));
 #define KGE_NA2(SC, NM, SL)                                                                         \
-  hipLaunchKernelGGL((bwd_neg_accum_kernel<SC, NM, SL>), grid, dim3(256), 0, st, S, R, O, d, dr, n,  \
-                     neg, neg_itype, neg_ld, K, (int)cpr, ch, lp, gout, ldg, scores, lds, ge, ge_ld, gr, \
-                     gr_ld)
+  if (dk)                                                                                           \
+    hipLaunchKernelGGL((bwd_neg_accum_drop_kernel<SC, NM, SL>), grid, dim3(256), 0, st, S, R, O, d, dr, n, neg, \
+                       neg_itype, neg_ld, K, (int)cpr, ch, lp, gout, ldg, scores, lds, ge, ge_ld, gr, gr_ld, *dk); \
+  else                                                                                              \
+    hipLaunchKernelGGL((bwd_neg_accum_kernel<SC, NM, SL>), grid, dim3(256), 0, st, S, R, O, d, dr, n, \
+                       neg, neg_itype, neg_ld, K, (int)cpr, ch, lp, gout, ldg, scores, lds, ge, ge_ld, gr, \
+                       gr_ld)
 #define KGE_NA(SC, NM)                                                \
   {                                                                   \
-    if (slot == 0) KGE_NA2(SC, NM, 0);                                \
-    else KGE_NA2(SC, NM, 2);                                          \
+    if (slot == 0) { KGE_NA2(SC, NM, 0); }                            \
+    else { KGE_NA2(SC, NM, 2); }                                      \
     return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; \
   }
   switch (scorer) {
@@ -481,6 +567,22 @@ int run_neg_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, 
 #undef KGE_NA
 #undef KGE_NA2
   return KGE_ERR_INVALID_ARG;
+}
+
+int run_neg_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d,
+                      int dr, long long n, int slot, const void* neg, int neg_itype, long long neg_ld,
+                      long long K, const float* gout, long long ldg, const float* scores, long long lds,
+                      float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st) {
+  return run_neg_bwd_accum_impl(scorer, lp, S, R, O, d, dr, n, slot, neg, neg_itype, neg_ld, K, gout, ldg, scores, lds,
+                                ge, ge_ld, gr, gr_ld, st, nullptr);
+}
+
+int run_neg_bwd_accum_drop(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                           long long n, int slot, const void* neg, int neg_itype, long long neg_ld, long long K,
+                           const float* gout, long long ldg, const float* scores, long long lds, float* ge,
+                           long long ge_ld, float* gr, long long gr_ld, const DropKey& dk, hipStream_t st) {
+  return run_neg_bwd_accum_impl(scorer, lp, S, R, O, d, dr, n, slot, neg, neg_itype, neg_ld, K, gout, ldg, scores, lds,
+                                ge, ge_ld, gr, gr_ld, st, &dk);
 }
 
 // ---- kge_score_neg_bwd_accum_sorted: the backward of the negatives without one atomic per occurrence -------------
@@ -906,9 +1008,9 @@ int run_spo_bwd(int scorer, float lp, const Operand& S, const Operand& R, const 
   return KGE_ERR_INVALID_ARG;
 }
 
-int run_spo_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d,
-                      int dr, long long n, const float* gout, const float* scores, float* ge, long long ge_ld,
-                      float* gr, long long gr_ld, hipStream_t st) {
+static int run_spo_bwd_accum_impl(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d,
+                                  int dr, long long n, const float* gout, const float* scores, float* ge,
+                                  long long ge_ld, float* gr, long long gr_ld, hipStream_t st, const DropKey* dk) {
   if (n == 0) return KGE_OK;
   if ((d + 1) / 2 > 64 * SPA_NC) return KGE_ERR_UNSUPPORTED;
   const int norm = norm_mode(lp);
@@ -922,8 +1024,12 @@ int run_spo_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, 
   const dim3 grid((unsigned)((chunks + 3) / 4));
 #define KGE_SA(SC, NM)                                                                                \
   {                                                                                                   \
-    hipLaunchKernelGGL((bwd_spo_accum_kernel<SC, NM>), grid, dim3(256), 0, st, S, R, O, d, dr, n, lp,  \
-                       gout, scores, ge, ge_ld, gr, gr_ld, ch);                                       \
+    if (dk)                                                                                           \
+      hipLaunchKernelGGL((bwd_spo_accum_drop_kernel<SC, NM>), grid, dim3(256), 0, st, S, R, O, d, dr, n, lp, \
+                         gout, scores, ge, ge_ld, gr, gr_ld, ch, *dk);                                \
+    else                                                                                              \
+      hipLaunchKernelGGL((bwd_spo_accum_kernel<SC, NM>), grid, dim3(256), 0, st, S, R, O, d, dr, n, lp, \
+                         gout, scores, ge, ge_ld, gr, gr_ld, ch);                                     \
     return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;                                 \
   }
   switch (scorer) {
@@ -940,6 +1046,18 @@ int run_spo_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, 
   }
 #undef KGE_SA
   return KGE_ERR_INVALID_ARG;
+}
+
+int run_spo_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d,
+                      int dr, long long n, const float* gout, const float* scores, float* ge, long long ge_ld,
+                      float* gr, long long gr_ld, hipStream_t st) {
+  return run_spo_bwd_accum_impl(scorer, lp, S, R, O, d, dr, n, gout, scores, ge, ge_ld, gr, gr_ld, st, nullptr);
+}
+
+int run_spo_bwd_accum_drop(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
+                           long long n, const float* gout, const float* scores, float* ge, long long ge_ld, float* gr,
+                           long long gr_ld, const DropKey& dk, hipStream_t st) {
+  return run_spo_bwd_accum_impl(scorer, lp, S, R, O, d, dr, n, gout, scores, ge, ge_ld, gr, gr_ld, st, &dk);
 }
 
 }  // namespace kge

@@ -4,6 +4,7 @@
 // all-gather): two (table, index, out) jobs per launch, so the entity rows and the relation rows
 // of a batch are one kernel.  HBM gather bound: 16-byte loads / stores, one wave per row slice.
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace kge {
 
@@ -28,6 +29,44 @@ int run_embed2(const EmbedJob& a, const EmbedJob& b, int rowbytes, int esize, hi
   if (chunks == 0) return KGE_OK;
   hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, a, b, rowbytes,
                      esize);
+  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+}
+
+// ---- kge_embed_dropout: embed() in training mode (lookup_embedder.py:96-105: the gather, then torch.nn.Dropout) ----
+// out[i, c] = table[idx[i], c] * factor(c, occurrence occ0 + i, role): the mask of philox.hpp, one thread and one Philox
+// block per four columns.  float32 rows of any width and pitch (scalar loads and stores).
+__global__ __launch_bounds__(256) void embed_dropout_kernel(const float* __restrict__ table, long long ld, Index idx,
+                                                            long long n, int d, unsigned occ0, RowMask m0, DropKey dk,
+                                                            float* __restrict__ out, long long ldo) {
+  const int qpr = (d + 3) >> 2;  // quads per row
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long i = t / qpr;
+  if (i >= n) return;
+  const int c0 = (int)(t - i * qpr) * 4;
+  const float* src = table + index_at(idx, i) * ld;
+  float* dst = out + i * ldo;
+  RowMask m = m0;
+  m.occ = occ0 + (unsigned)i;
+  float f[4] = {m.scale, m.scale, m.scale, m.scale};
+  if (m.thr != 0) {
+    const Philox4 r = philox4x32_10((unsigned)(c0 >> 2), m.occ, dk.call, m.role, dk.k0, dk.k1);
+    f[0] = r.r0 < m.thr ? 0.0f : m.scale;
+    f[1] = r.r1 < m.thr ? 0.0f : m.scale;
+    f[2] = r.r2 < m.thr ? 0.0f : m.scale;
+    f[3] = r.r3 < m.thr ? 0.0f : m.scale;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c0 + j < d) dst[c0 + j] = m.thr != 0 ? src[c0 + j] * f[j] : src[c0 + j];
+}
+
+int run_embed_dropout(const float* table, long long ld, const Index& idx, long long n, int d, unsigned occ0,
+                      const RowMask& m0, const DropKey& dk, float* out, long long ldo, hipStream_t st) {
+  const long long threads = n * ((d + 3) >> 2);
+  if (threads == 0) return KGE_OK;
+  if ((threads + 255) / 256 > 0x7fffffffLL) return KGE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(embed_dropout_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, table, ld, idx, n, d,
+                     occ0, m0, dk, out, ldo);
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 

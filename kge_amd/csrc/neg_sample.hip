@@ -20,29 +20,9 @@
 // range, per lane; the redraw loop diverges per lane.  A lane gives up after KGE_NEG_SAMPLE_MAX_ATTEMPTS attempts and
 // keeps its last draw (the reference loops forever on a key whose answers cover the vocabulary).  stats: per row the
 // number of rejected attempts and the number of columns that hit the cap, wave-reduced, one plain store each.
-#include "common.hpp"
+#include "philox.hpp"
 
 namespace kge {
-
-struct Philox4 {
-  unsigned r0, r1, r2, r3;
-};
-
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                                 unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1;
-    c3 = (unsigned)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return Philox4{c0, c1, c2, c3};
-}
 
 template <bool ALIAS, bool FILTER>
 __global__ __launch_bounds__(256) void neg_sample_kernel(long long n, long long K, unsigned long long vocab, unsigned k0,

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace kge {
 
@@ -130,17 +131,34 @@ __device__ __forceinline__ float apply_chunk(int slot, float P, const Fixed& F,
   return P;
 }
 
+// one lane's chunk of the half of a row that starts at column `half` (0 or h), with the embedder dropout of that row
+// occurrence applied where the chunk reaches the registers (DROP; philox.hpp): everything after the load is the
+// arithmetic of the undropped kernel.  VEC implies half % 4 == 0 and c0 % 8 == 0 (vec_ok): two Philox blocks per chunk.
+template <typename T, bool VEC, bool DROP>
+__device__ __forceinline__ f32x8 load_chunk_d(const T* row, int half, int c0, int limit, const RowMask& m,
+                                              const DropKey& k) {
+  f32x8 r = load_chunk<T, VEC>(row + half, c0, limit);
+  if constexpr (DROP) mask_chunk<VEC>(r, half + c0, m, k);
+  return r;
+}
+
 // load the fixed side of chunk c0 for (entity row erow, relation row rrow)
+template <int SCORER, typename T, bool VEC, bool DROP>
+__device__ __forceinline__ Fixed load_fixed_d(int slot, const T* erow, const T* rrow, int c0, int D, int h,
+                                              const RowMask& em, const RowMask& rm, const DropKey& k) {
+  constexpr bool CPLX = (SCORER == KGE_COMPLEX || SCORER == KGE_ROTATE);
+  f32x8 e0 = load_chunk_d<T, VEC, DROP>(erow, 0, c0, D, em, k);
+  f32x8 r0 = load_chunk_d<T, VEC, DROP>(rrow, 0, c0, D, rm, k);
+  f32x8 e1 = e0, r1 = r0;
+  if (CPLX) e1 = load_chunk_d<T, VEC, DROP>(erow, h, c0, D, em, k);
+  if (SCORER == KGE_COMPLEX) r1 = load_chunk_d<T, VEC, DROP>(rrow, h, c0, D, rm, k);
+  return prep_chunk<SCORER>(slot, e0, e1, r0, r1);
+}
+
 template <int SCORER, typename T, bool VEC>
 __device__ __forceinline__ Fixed load_fixed(int slot, const T* erow, const T* rrow, int c0,
                                             int D, int h) {
-  constexpr bool CPLX = (SCORER == KGE_COMPLEX || SCORER == KGE_ROTATE);
-  f32x8 e0 = load_chunk<T, VEC>(erow, c0, D);
-  f32x8 r0 = load_chunk<T, VEC>(rrow, c0, D);
-  f32x8 e1 = e0, r1 = r0;
-  if (CPLX) e1 = load_chunk<T, VEC>(erow + h, c0, D);
-  if (SCORER == KGE_COMPLEX) r1 = load_chunk<T, VEC>(rrow + h, c0, D);
-  return prep_chunk<SCORER>(slot, e0, e1, r0, r1);
+  return load_fixed_d<SCORER, T, VEC, false>(slot, erow, rrow, c0, D, h, RowMask{}, RowMask{}, DropKey{});
 }
 
 template <int SCORER, int NORM>

@@ -12,6 +12,7 @@ Function <-> reference map (paths relative to the reference tree):
   score_so                                         KgeModel.score_so           kge/model/kge_model.py:727-747
   rank_counts                                      EntityRankingJob._filter_and_rank  kge/job/eval_entity_ranking.py:533-596
 """
+import collections
 import ctypes
 import math
 import os
@@ -2862,3 +2863,132 @@ def score_emb_bwd(scorer, s_emb, p_emb, o_emb, combine: str, l_norm, gout, score
             None if sc is None else sc.data_ptr(), max(m, 1), g_s.data_ptr(), g_p.data_ptr(),
             g_o.data_ptr(), _stream(dev)), "kge_score_emb_bwd")
     return g_s, g_p, g_o
+
+
+# ---- embedder dropout inside the triple-wise kernels (include/kge_amd.h "Embedder dropout") ---------------------------
+class Dropout(collections.namedtuple("Dropout", "p_ent p_rel seed call")):
+    """The mask of one fused dropout call: drop probabilities of the two embedders, the model's seed and the call
+    number.  A backward passes its forward's record: the kernels regenerate the mask from it."""
+    __slots__ = ()
+
+    def c(self):
+        return _lib.KgeDropout(float(self.p_ent), float(self.p_rel), int(self.seed) & (2 ** 64 - 1),
+                               int(self.call) & (2 ** 64 - 1))
+
+
+def embed_dropout(t: Tables, table: str, idx, role: int, occ0: int, dropout: Dropout, out=None) -> torch.Tensor:
+    """embed() in training mode: the rows idx of the 'ent' / 'rel' table under the mask of occurrences occ0 .. occ0 + n
+    of `role` (0 = s, 1 = p, 2 = o).  out: float32 [n, >= width] with unit column stride, or None."""
+    keep = []
+    ix = _index(idx, t.device, keep)
+    n = _same_len(keep[:1], "embed_dropout")
+    which = {"ent": 0, "rel": 1}[table]
+    width = (t.ent if which == 0 else t.rel).shape[1]
+    if out is None:
+        out = _empty((n, width), t.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1:
+        raise ValueError("kge_amd: embed_dropout out must be float32 [n, width] with unit column stride")
+    dc = dropout.c()
+    with _on_device(t.device):
+        tc = t.c()
+        _lib.check(_lib.lib().kge_embed_dropout(ctypes.byref(tc), which, ix, n, int(role), int(occ0), ctypes.byref(dc),
+                                                out.data_ptr(), out.stride(0) if n > 1 else max(width, out.shape[1]),
+                                                _stream_handle(t.device)), "kge_embed_dropout")
+    return out
+
+
+def score_spo_dropout(t: Tables, s, p, o, dropout: Dropout) -> torch.Tensor:
+    """score_spo on rows under embedder dropout: triple i is occurrence i, its rows carry roles 0 / 1 / 2."""
+    keep = []
+    si, pi, oi = (_index(x, t.device, keep) for x in (s, p, o))
+    n = _same_len(keep[:3], "score_spo_dropout")
+    out = _empty((n,), t.device)
+    dc = dropout.c()
+    with _on_device(t.device):
+        tc = t.c()
+        _lib.check(_lib.lib().kge_score_spo_dropout(ctypes.byref(tc), si, pi, oi, n, out.data_ptr(), ctypes.byref(dc),
+                                                    _stream_handle(t.device)), "kge_score_spo_dropout")
+    return out
+
+
+def _neg_matrix(neg, n):
+    if neg.dtype not in (torch.int32, torch.int64):
+        neg = neg.long()
+    if neg.dim() != 2 or neg.shape[0] != n:
+        raise ValueError("kge_amd: neg must be [n, K]")
+    if neg.stride(1) != 1:
+        neg = neg.contiguous()
+    return neg
+
+
+def score_neg_dropout(t: Tables, s, p, o, slot: int, neg: torch.Tensor, dropout: Dropout) -> torch.Tensor:
+    """score_neg under embedder dropout: the fixed rows of positive i are masked once (occurrence i), the corrupted row
+    of (i, k) is occurrence i K + k with role = slot."""
+    keep = []
+    si, pi, oi = (_index(x, t.device, keep) for x in (s, p, o))
+    n = _same_len(keep[:3], "score_neg_dropout")
+    _require_gpu(neg, "negative samples")
+    neg = _neg_matrix(neg, n)
+    K = neg.shape[1]
+    out = _empty((n, K), t.device)
+    dc = dropout.c()
+    with _on_device(t.device):
+        tc = t.c()
+        _lib.check(_lib.lib().kge_score_neg_dropout(
+            ctypes.byref(tc), si, pi, oi, n, int(slot), neg.data_ptr(), I32 if neg.dtype == torch.int32 else I64,
+            neg.stride(0) if n > 1 else max(K, 1), K, out.data_ptr(), max(K, 1), ctypes.byref(dc),
+            _stream_handle(t.device)), "kge_score_neg_dropout")
+    return out
+
+
+def score_spo_dropout_bwd_accum(t: Tables, s, p, o, gout, scores, grad_ent, grad_rel, dropout: Dropout):
+    """Backward of score_spo_dropout (the forward's Dropout record) accumulated into the dense table gradients; False if
+    the kernel does not take this shape."""
+    keep = []
+    si, pi, oi = (_index(x, t.device, keep) for x in (s, p, o))
+    n = _same_len(keep[:3], "score_spo_dropout_bwd_accum")
+    gout = _f32c(gout, t.device)
+    sc = None if scores is None else _f32c(scores, t.device)
+    dc = dropout.c()
+    with _on_device(t.device):
+        tc = t.c()
+        rc = _lib.lib().kge_score_spo_dropout_bwd_accum(
+            ctypes.byref(tc), si, pi, oi, n, gout.data_ptr(), None if sc is None else sc.data_ptr(),
+            grad_ent.data_ptr(), grad_ent.stride(0), grad_rel.data_ptr(), grad_rel.stride(0), ctypes.byref(dc),
+            _stream_handle(t.device))
+    if rc == _lib.KGE_ERR_UNSUPPORTED:
+        return False
+    if rc:
+        _lib.check(rc, "kge_score_spo_dropout_bwd_accum")
+    return True
+
+
+def score_neg_dropout_bwd_accum(t: Tables, s, p, o, slot: int, neg: torch.Tensor, gout, scores, grad_ent, grad_rel,
+                                dropout: Dropout):
+    """Backward of score_neg_dropout (the forward's Dropout record) accumulated into the dense table gradients; False if
+    the kernel does not take this shape."""
+    keep = []
+    si, pi, oi = (_index(x, t.device, keep) for x in (s, p, o))
+    n = _same_len(keep[:3], "score_neg_dropout_bwd_accum")
+    neg = _neg_matrix(neg, n)
+    K = neg.shape[1]
+    gout = gout.to(device=t.device, dtype=torch.float32)
+    if gout.dim() != 2 or gout.stride(1) != 1:
+        gout = gout.contiguous().view(n, K)
+    sc = None
+    if scores is not None:
+        sc = scores if (scores.dim() == 2 and scores.stride(1) == 1) else scores.contiguous().view(n, K)
+    dc = dropout.c()
+    with _on_device(t.device):
+        tc = t.c()
+        rc = _lib.lib().kge_score_neg_dropout_bwd_accum(
+            ctypes.byref(tc), si, pi, oi, n, int(slot), neg.data_ptr(), I32 if neg.dtype == torch.int32 else I64,
+            neg.stride(0) if n > 1 else max(K, 1), K, gout.data_ptr(), gout.stride(0) if n > 1 else max(K, 1),
+            None if sc is None else sc.data_ptr(), 0 if sc is None else (sc.stride(0) if n > 1 else max(K, 1)),
+            grad_ent.data_ptr(), grad_ent.stride(0), grad_rel.data_ptr(), grad_rel.stride(0), ctypes.byref(dc),
+            _stream_handle(t.device))
+    if rc == _lib.KGE_ERR_UNSUPPORTED:
+        return False
+    if rc:
+        _lib.check(rc, "kge_score_neg_dropout_bwd_accum")
+    return True

@@ -18,7 +18,8 @@ from kge.model.transh import transh_set_relation_embedder_dim
 
 from .. import engine
 from ..model import (BF16Shadow, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared,
-                     _ScorePairs, _ScoreSO, _ScoreSPO, ConveNetOps, ConveRoutes, Tucker3Routes, ce_fused_dropout,
+                     _ScorePairs, _ScoreSO, _ScoreSPO, _ScoreNegDropout, _ScoreSPODropout, DropoutClock,
+                     dropout_triple_fusable, ConveNetOps, ConveRoutes, Tucker3Routes, ce_fused_dropout,
                      fused_loss_rows, neg_blocks_fusable, neg_shared_fusable, predict_filters, score_so_fusable,
                      topk_composed)
 
@@ -124,6 +125,34 @@ class _FusedScoring:
             return None
         return float(se.dropout.p), float(pe.dropout.p)
 
+    def _dropout_triple(self):
+        """(p_entity, p_relation) if `hip_negative_sampling.fused_dropout` was set on this model (set_fused_dropout) and
+        the ONLY thing that keeps `_fused()` from holding is embedder dropout in training mode, on tables the dropout
+        kernels take (float32, the four scorers, dim <= 1024): score_spo / score_neg then compute the masks inside the
+        kernels (kge_score_spo_dropout / kge_score_neg_dropout; lookup_embedder.py:96-105).  Else None."""
+        from kge.model import LookupEmbedder
+        if not getattr(self, "_fused_dropout", False) or not self.training:
+            return None
+        se, oe, pe = self.get_s_embedder(), self.get_o_embedder(), self.get_p_embedder()
+        if se is not oe or type(se) is not LookupEmbedder or type(pe) is not LookupEmbedder:
+            return None
+        ent, rel = self._w()
+        p_ent, p_rel = float(se.dropout.p), float(pe.dropout.p)
+        if not ent.is_cuda or not dropout_triple_fusable(self._scorer.name, ent, rel, p_ent, p_rel):
+            return None
+        return p_ent, p_rel
+
+    def _next_dropout(self, probs):
+        """the engine.Dropout record of the next fused dropout call: the model's seed (torch.initial_seed() at the first
+        call; `dropout_seed` is settable) and a host counter incremented once per call"""
+        if getattr(self, "_dropout_clock", None) is None:
+            self._dropout_clock = DropoutClock(getattr(self, "dropout_seed", None))
+        return self._dropout_clock.next(*probs)
+
+    def set_fused_dropout(self, on: bool):
+        """hip_negative_sampling.fused_dropout: embedder dropout inside the fused triple-wise kernels"""
+        self._fused_dropout = bool(on)
+
     def _w(self):
         return (self.get_s_embedder()._embeddings.weight, self.get_p_embedder()._embeddings.weight)
 
@@ -168,6 +197,11 @@ class _FusedScoring:
 
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
         if not self._fused():
+            probs = self._dropout_triple()
+            if probs is not None:
+                ent, rel = self._w()
+                return _ScoreSPODropout.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o,
+                                              self._next_dropout(probs), self._touched_pair())
             return super().score_spo(s, p, o, direction)
         ent, rel = self._w()
         return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, self._touched_pair())
@@ -177,8 +211,15 @@ class _FusedScoring:
         BatchNegativeSample.score returns (kge/util/sampler.py:263-306), from kge_score_neg -- the
         positives' fixed rows are read once, only the corrupted rows stream; None if the fused
         path does not apply (HipTrainingJobNegativeSampling then calls the sampler's own score)."""
-        if not self._fused() or slot not in (0, 2):
+        if slot not in (0, 2):
             return None
+        if not self._fused():
+            probs = self._dropout_triple()
+            if probs is None:
+                return None
+            ent, rel = self._w()
+            return _ScoreNegDropout.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), neg,
+                                          self._next_dropout(probs), self._touched_pair())
         ent, rel = self._w()
         if not ent.is_cuda:
             return None
@@ -851,6 +892,16 @@ class HipReciprocalRelationsModel(_RefReciprocal):
         b = self._base_model
         return isinstance(b, _FusedScoring) and b._fused()
 
+    def _base_triples(self) -> bool:
+        """score_spo / score_neg of the base model run fused: plain lookups, or embedder dropout inside the kernels
+        (hip_negative_sampling.fused_dropout)"""
+        b = self._base_model
+        return self._base_fused() or (isinstance(b, _FusedScoring) and b._dropout_triple() is not None)
+
+    def set_fused_dropout(self, on: bool):
+        if hasattr(self._base_model, "set_fused_dropout"):
+            self._base_model.set_fused_dropout(on)
+
     # ---- scores
     def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
         if not self._base_fused():
@@ -893,7 +944,7 @@ class HipReciprocalRelationsModel(_RefReciprocal):
 
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
         # (reciprocal_relations_model.py:74-82: "o" scores the triple as it stands, "s" the reversed triple with p + R)
-        if not self._base_fused() or direction not in ("o", "s"):
+        if not self._base_triples() or direction not in ("o", "s"):
             return super().score_spo(s, p, o, direction)
         if direction == "o":
             return self._base_model.score_spo(s, p, o, "o")
@@ -905,7 +956,7 @@ class HipReciprocalRelationsModel(_RefReciprocal):
         which asks score_spo(..., direction) of this wrapper): a corrupted SUBJECT is the corrupted object of the
         reversed triple (o, p + R, s').  None: the sampler's own code."""
         b = self._base_model
-        if not self._base_fused() or not hasattr(b, "score_neg"):
+        if not self._base_triples() or not hasattr(b, "score_neg"):
             return None
         if slot == 2:
             return b.score_neg(s, p, o, 2, neg)

@@ -925,6 +925,14 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             self._fused_shared = bool(config.get("hip_negative_sampling.fused_shared"))
         except KeyError:
             self._fused_shared = False
+        # embedder dropout inside the fused triple-wise kernels (hip_negative_sampling.fused_dropout, false by default: a
+        # model with active dropout is scored by the sampler's and the reference model's own code)
+        try:
+            fused_dropout = bool(config.get("hip_negative_sampling.fused_dropout"))
+        except KeyError:
+            fused_dropout = False
+        if hasattr(self.model, "set_fused_dropout"):
+            self.model.set_fused_dropout(fused_dropout and str(self.device).startswith("cuda"))
         # the samples of the subject / object slot drawn on the device (hip_negative_sampling.device_sampler, false by
         # default: every slot's samples come from the reference's sampler on the host)
         try:

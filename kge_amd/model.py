@@ -183,8 +183,15 @@ class KgeModel(torch.nn.Module):
 
     def __init__(self, num_entities: int, num_relations: int, dim: int, l_norm: float = 1.0,
                  dtype=torch.float32, device=None, entity_args=None, relation_args=None,
-                 score_dtype=None, fused_dist_loss: bool = False, fused_f32_loss: bool = False, scorer_args=None):
+                 score_dtype=None, fused_dist_loss: bool = False, fused_f32_loss: bool = False, scorer_args=None,
+                 fused_dropout: bool = False):
         super().__init__()
+        # fused_dropout=True (ComplEx / DistMult / TransE / RotatE, float32 parameters on a GPU, dim <= 1024): in training
+        # mode with embedder dropout, score_spo and score_neg stay on the fused kernels -- the masks are computed inside
+        # them (kge_score_spo_dropout / kge_score_neg_dropout and their backward) from `dropout_seed` (taken from
+        # torch.initial_seed() here; settable) and a host call counter; off by default
+        self.fused_dropout = bool(fused_dropout)
+        self._dropout_clock = DropoutClock()
         # fused_f32_loss=True (ComplEx / DistMult, float32 parameters on a GPU scored in float32, dim % 8 == 0): loss_sp /
         # loss_po / loss_sp_po / loss_sp_po_sum without an [n, E] matrix (kge_ce_f32_fwd / _bwd), and kl_loss_sp /
         # kl_loss_po / bce_loss_sp / bce_loss_po with or without label smoothing (kge_kl_f32_* / kge_bce_f32_*); off by
@@ -276,11 +283,35 @@ class KgeModel(torch.nn.Module):
     def _fused(self) -> bool:
         return self._entity_embedder.fused_ok() and self._relation_embedder.fused_ok()
 
+    @property
+    def dropout_seed(self) -> int:
+        return self._dropout_clock.seed
+
+    @dropout_seed.setter
+    def dropout_seed(self, seed: int):
+        self._dropout_clock.seed = int(seed)
+
+    def _dropout_triple(self):
+        """(p_entity, p_relation) if `fused_dropout` is set and embedder dropout in training mode is what keeps `_fused()`
+        from holding, on tables the dropout kernels take; else None."""
+        if not self.fused_dropout or self._fused() or type(self._relation_embedder) is not LookupEmbedder:
+            return None
+        pe, pr = float(self._entity_embedder.dropout.p), float(self._relation_embedder.dropout.p)
+        if not dropout_triple_fusable(self._scorer.name, self._entity_embedder.weight, self._relation_embedder.weight,
+                                      pe, pr):
+            return None
+        return pe, pr
+
     # -- scoring
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
         if self._fused():
             return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
                                    self._relation_embedder.weight, s, p, o, self._touched_rows)
+        dp = self._dropout_triple()
+        if dp is not None:
+            return _ScoreSPODropout.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
+                                          self._relation_embedder.weight, s, p, o, self._dropout_clock.next(*dp),
+                                          self._touched_rows)
         se, pe, oe = self._entity_embedder.embed(s), self._relation_embedder.embed(p), self._entity_embedder.embed(o)
         return self._scorer.score_emb(se, pe, oe, combine="spo").view(-1)
 
@@ -290,6 +321,11 @@ class KgeModel(torch.nn.Module):
         if self._fused() and slot in (0, 2):
             return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
                                    self._relation_embedder.weight, s, p, o, int(slot), neg, self._touched_rows)
+        dp = self._dropout_triple() if slot in (0, 2) else None
+        if dp is not None:
+            return _ScoreNegDropout.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
+                                          self._relation_embedder.weight, s, p, o, int(slot), neg,
+                                          self._dropout_clock.next(*dp), self._touched_rows)
         K = neg.shape[1]
         tr = [x.reshape(-1).long().repeat_interleave(K) for x in (s, p, o)]
         tr[slot] = neg.reshape(-1).long()
@@ -1201,6 +1237,90 @@ class _ScoreNeg(torch.autograd.Function):
             _scatter_rows(gr, tr[1], g_p)
             ge, gr = ge.to(ctx.t.ent.dtype), gr.to(ctx.t.rel.dtype)
         return None, None, ge, gr, None, None, None, None, None, None
+
+
+# ---- embedder dropout inside the triple-wise kernels (include/kge_amd.h "Embedder dropout") ----------------
+DROPOUT_TRIPLE_SCORERS = ("complex", "distmult", "transe", "rotate")
+DROPOUT_CALLS = 0  # fused dropout calls of this process (the plugin's tests count them)
+
+
+def dropout_triple_fusable(name: str, ent: Tensor, rel: Tensor, p_ent: float, p_rel: float) -> bool:
+    """What kge_score_spo_dropout / kge_score_neg_dropout and their backward take: float32 GPU tables of the four
+    scorers, dim <= 1024, probabilities in [0, 1) that are not both 0."""
+    return (name in DROPOUT_TRIPLE_SCORERS and ent.is_cuda and rel.is_cuda and ent.dtype == torch.float32 and
+            rel.dtype == torch.float32 and ent.shape[1] <= 1024 and 0.0 <= p_ent < 1.0 and 0.0 <= p_rel < 1.0 and
+            (p_ent > 0.0 or p_rel > 0.0))
+
+
+class DropoutClock:
+    """The (seed, call) source of a model's fused dropout calls: `seed` taken from torch.initial_seed() where the model
+    is built (settable), `call` a host counter incremented once per fused dropout call."""
+
+    def __init__(self, seed=None):
+        self.seed = int(torch.initial_seed() if seed is None else seed)
+        self.call = 0
+
+    def next(self, p_ent: float, p_rel: float) -> engine.Dropout:
+        global DROPOUT_CALLS
+        self.call += 1
+        DROPOUT_CALLS += 1
+        return engine.Dropout(float(p_ent), float(p_rel), self.seed, self.call)
+
+
+class _ScoreSPODropout(torch.autograd.Function):
+    """_ScoreSPO with the embedder dropout of the three gathered rows inside the kernels: the forward's Dropout record
+    (seed, call) is saved and handed to the backward, which regenerates the masks."""
+
+    @staticmethod
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, dropout, touched=None):
+        t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
+        ctx.t, ctx.idx, ctx.dropout = t, (s, p, o), dropout
+        ctx.touched = None if touched is None else _touched_pair(t, touched)
+        out = engine.score_spo_dropout(t, s, p, o, dropout)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        s, p, o = ctx.idx
+        (scores,) = ctx.saved_tensors
+        if ctx.touched is not None:
+            ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o)
+        else:
+            ge, gr, rel_kept = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel), False
+        if not engine.score_spo_dropout_bwd_accum(ctx.t, s, p, o, gout.contiguous(), scores, ge, gr, ctx.dropout):
+            raise RuntimeError("kge_amd: kge_score_spo_dropout_bwd_accum declined a shape its forward took")
+        if ctx.touched is not None:
+            return None, None, None, None if rel_kept else gr, None, None, None, None, None
+        return None, None, ge, gr, None, None, None, None, None
+
+
+class _ScoreNegDropout(torch.autograd.Function):
+    """_ScoreNeg with the embedder dropout inside the kernels: the fixed rows of a positive masked once, every corrupted
+    row occurrence with its own mask; the backward regenerates them from the forward's Dropout record."""
+
+    @staticmethod
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, slot, neg, dropout, touched=None):
+        t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
+        out = engine.score_neg_dropout(t, s, p, o, slot, neg, dropout)
+        ctx.t, ctx.idx, ctx.slot, ctx.dropout = t, (s, p, o, neg), slot, dropout
+        ctx.touched = None if touched is None else _touched_pair(t, touched)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        s, p, o, neg = ctx.idx
+        (scores,) = ctx.saved_tensors
+        if ctx.touched is not None:
+            ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o, neg)
+        else:
+            ge, gr, rel_kept = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel), False
+        if not engine.score_neg_dropout_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr, ctx.dropout):
+            raise RuntimeError("kge_amd: kge_score_neg_dropout_bwd_accum declined a shape its forward took")
+        if ctx.touched is not None:
+            return None, None, None, None if rel_kept else gr, None, None, None, None, None, None, None
+        return None, None, ge, gr, None, None, None, None, None, None, None
 
 
 class _ScoreNegShared(torch.autograd.Function):
