@@ -421,6 +421,11 @@ int kge_score_queries(const kge_tables* t, int combine, const void* queries, int
  *   kge_score_queries_multi   scores the group; `next` (may be NULL) describes the NEXT group -- num_batches batches of
  *                             next->n rows each, index vectors of num_batches * next->n entries, fragments next_stride
  *                             bytes apart in next->queries -- built by the same launch behind its last unit.
+ *                             The next group's fragments are complete when the launch is complete.  At dim 512 the
+ *                             workgroups that finish their scores early claim the build's slices through a counter
+ *                             pair the library keeps per stream (launches of one stream are serial and leave it at 0;
+ *                             DESIGN.md 37); a launch on a stream that is being captured builds a fixed slice per
+ *                             workgroup instead (a captured launch may be replayed on any stream).  The same fragments.
  * Scores are bit-identical to num_batches kge_score_queries calls.  bf16 ComplEx / DistMult at dim 512 against all
  * entities; anything else KGE_ERR_UNSUPPORTED (loop over kge_score_queries instead). */
 int kge_build_queries_multi(const kge_tables* t, int combine, kge_index s, kge_index p, kge_index o, int64_t n,

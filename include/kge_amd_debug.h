@@ -35,8 +35,17 @@ int kge_debug_score_sp_bf16_v2(const kge_tables* t, kge_index s, kge_index p, in
 
 /* Launches of the persistent kernels issued by this process so far: which 0 = pairs_bf16_v8_kernel (the store kernel:
  * kge_score_queries_multi, and kge_score_sp / _po / _sp_po with >= 1024 rows at d = 512), 1 = pairs_bf16_v8_rank_kernel
- * (the counting kernel); -1 for any other `which`.  Tests use it to prove which kernel a product call reached. */
+ * (the counting kernel), 2 = the launches of 0 that build the next group's fragments in claimed slices (the
+ * others with a `next` build it in fixed slices); -1 for any other `which`.  Tests use it to prove which kernel a product
+ * call reached. */
 int kge_debug_launch_count(int which);
+
+/* The counter pair of the claimed build that belongs to `stream` on the current device: get2 (host, may be
+ * NULL) receives {next ticket, workgroups done} -- {0, 0} between two launches --, then set2 (host, may be NULL)
+ * overwrites the pair (tests/test_gpu_v8_tail_build.py plants a sentinel to see that a launch without `next` leaves it
+ * alone; a pair that is not {0, 0} makes the stream's next build skip slices).  Synchronises the device.  Returns 1, 0 if
+ * the stream has no pair (no launch with claimed slices on it yet), or a negative kge_status. */
+int kge_debug_v8_claim_counters(void* stream, const uint32_t* set2, uint32_t* get2);
 
 /* The matrix pipe alone (bench.py's `matrix_pipe_probe`): one workgroup of eight waves per compute unit, every wave
  * `iters` x 16 v_mfma_f32_32x32x16_bf16 on two independent accumulators from `operands` (8 waves x 4 x 1 KiB of bf16

@@ -167,6 +167,7 @@ int run_pairs_bf16_v8_rank(int scorer, bool split, const Operand& TG, int d, lon
                            const CeArgs& ce, hipStream_t st, unsigned long long* dbg, int reserve_cus, bool band = false,
                            long long* band_lists = nullptr);
 int v8_launch_count(int which);
+int v8_claim_counters(hipStream_t st, const unsigned int* set2, unsigned int* get2);
 int run_embed2(const EmbedJob& a, const EmbedJob& b, int rowbytes, int esize, hipStream_t st);
 int run_ns_bce(int kind, const float* scores, long long ld, long long n, long long c, float offset, float temp,
                float* loss_rows, float* grad, long long ldg, hipStream_t st);
@@ -613,12 +614,12 @@ int pairs_entry(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t 
 
 // ---- measurement switches (switches.hpp, include/kge_amd_debug.h) ----
 namespace kge {
-static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-static_assert(SW_COUNT == 21, "g_switch's initialiser");
+static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(SW_COUNT == 22, "g_switch's initialiser");
 static const char* const g_switch_name[SW_COUNT] = {
     "ONE_CALL_PREPARED", "ONE_CALL_V8", "ONE_CALL_V8_MIN_ROWS", "V8_RANK", "RANK_FUSED_FRONT", "BWD_GEMM_LIB",
     "CE_V3", "CE_V8", "V4_OWN_BUILD", "V4_INTERLEAVE", "V4_STORE_SC1", "V6", "V7", "V7_NOSTORE", "V7_PROBE", "V8",
-    "V8_VAR", "V8_MFMA32", "V8R_PROBE", "TRANSE_GENERIC", "TOPK_COL_TILES"};
+    "V8_VAR", "V8_MFMA32", "V8_TAIL_FIXED", "V8R_PROBE", "TRANSE_GENERIC", "TOPK_COL_TILES"};
 long long sw(Switch s) { return __atomic_load_n(&g_switch[(int)s], __ATOMIC_RELAXED); }
 static int switch_index(const char* name) {
   if (name == nullptr) return -1;
@@ -3073,6 +3074,9 @@ int kge_debug_sqrt_check(uint32_t first_bits, uint64_t count, uint64_t* mismatch
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 int kge_debug_launch_count(int which) { return kge::v8_launch_count(which); }
+int kge_debug_v8_claim_counters(void* stream, const uint32_t* set2, uint32_t* get2) {
+  return kge::v8_claim_counters((hipStream_t)stream, set2, get2);
+}
 
 int kge_debug_set_switch(const char* name, int64_t value) {
   const int i = kge::switch_index(name);

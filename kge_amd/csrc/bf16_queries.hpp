@@ -74,7 +74,72 @@ struct Q16Out {
   long long zero_cnt;
 };
 
-// items [item0, item0 + stride, ...) of the batch: one item = 8 coordinates of both halves of one query row
+// items of a build: one item = 8 coordinates of both halves of one query row
+template <int HH, int SPLIT>
+__host__ __device__ __forceinline__ long long v4_build_items(const NextQ& nx) {
+  constexpr int CGR = HH / 8;
+  constexpr int RGR = SPLIT ? 64 : 128;  // real rows per row group
+  const int nb = nx.nbatch > 1 ? nx.nbatch : 1;
+  return (long long)nb * nx.rgn * RGR * CGR;
+}
+
+// item `it` of the build: two gathered rows -> four (SPLIT) / two fragment words of 16 bytes
+template <int SCORER, int HH, int SPLIT, bool WITH_Q16 = false>
+__device__ __forceinline__ void v4_build_item(const NextQ& nx, long long it, const Q16Out* qo = nullptr) {
+  constexpr int NKB = 2 * HH / 16, NKH = HH / 16, CGR = HH / 8;
+  constexpr int RGR = SPLIT ? 64 : 128;  // real rows per row group
+  const int rgg = (int)(it / (RGR * CGR));
+  const int lb = rgg / nx.rgn, rg = rgg - lb * nx.rgn;  // batch of the group, row group of the batch
+  const int rr = (int)((it / CGR) % RGR);
+  const int c8 = (int)(it % CGR);
+  const bool second = rg >= nx.rgn1;
+  const long long lrow = (long long)(second ? rg - nx.rgn1 : rg) * RGR + rr;
+  const long long qrow = (lrow < nx.n ? lrow : nx.n - 1) + (long long)lb * nx.n;  // padded rows repeat row n-1
+  const Operand& E = second ? nx.A2 : nx.A;
+  const int dir = second ? KGE_PO_ : nx.dir;
+  const unsigned short* a = (const unsigned short*)E.base + index_at(E.idx, qrow) * E.ld + c8 * 8;
+  const unsigned short* r = (const unsigned short*)nx.R.base + index_at(nx.R.idx, qrow) * nx.R.ld + c8 * 8;
+  const u32x4 a0 = *reinterpret_cast<const u32x4*>(a), a1 = *reinterpret_cast<const u32x4*>(a + HH);
+  const u32x4 r0 = *reinterpret_cast<const u32x4*>(r), r1 = *reinterpret_cast<const u32x4*>(r + HH);
+  u32x4 q0, q1, l0, l1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if constexpr (SPLIT) {
+      f32x2q Q0, Q1;
+      v4_q_f32<SCORER>(dir, a0[e], a1[e], r0[e], r1[e], Q0, Q1);
+      q0[e] = bf16_pack_hw(Q0);
+      q1[e] = bf16_pack_hw(Q1);
+      const f32x2q H0 = {__uint_as_float(q0[e] << 16), __uint_as_float(q0[e] & 0xffff0000u)};
+      const f32x2q H1 = {__uint_as_float(q1[e] << 16), __uint_as_float(q1[e] & 0xffff0000u)};
+      l0[e] = bf16_pack_hw(Q0 - H0);  // exact differences (Sterbenz-like: |q - q_hi| <= ulp_bf16(q) / 2)
+      l1[e] = bf16_pack_hw(Q1 - H1);
+    } else {
+      unsigned int x0, x1;
+      bf16_qpair_fast<SCORER>(dir, a0[e], a1[e], r0[e], r1[e], x0, x1);
+      q0[e] = x0;
+      q1[e] = x1;
+    }
+  }
+  // fragment-major (as the in-launch build below): K-block kb of 32-row block rb is 64 lanes x 16 B
+  const long long row = (long long)rg * 128 + rr;  // virtual row (SPLIT: the q_hi row; q_lo 64 rows behind)
+  u32x4* dst = nx.qf + (long long)lb * nx.qstride + ((row >> 5) * NKB) * 64 + (row & 31) + 32 * (c8 & 1);
+  dst[(c8 >> 1) * 64] = q0;
+  dst[(NKH + (c8 >> 1)) * 64] = q1;
+  if constexpr (WITH_Q16) {
+    if (qo->q16 != nullptr && lrow < nx.n) {
+      unsigned short* qr = qo->q16 + ((second ? nx.n : 0) + lrow) * (2 * HH) + c8 * 8;
+      *reinterpret_cast<u32x4*>(qr) = q0;
+      *reinterpret_cast<u32x4*>(qr + HH) = q1;
+    }
+  }
+  if constexpr (SPLIT) {
+    u32x4* dl = dst + 2 * NKB * 64;  // two 32-row blocks further
+    dl[(c8 >> 1) * 64] = l0;
+    dl[(NKH + (c8 >> 1)) * 64] = l1;
+  }
+}
+
+// items [item0, item0 + stride, ...) of the batch
 template <int SCORER, int HH, int SPLIT, bool WITH_Q16 = false>
 __device__ __forceinline__ void v4_build_queries(const NextQ& nx, long long item0, long long stride,
                                                  const Q16Out* qo = nullptr) {
@@ -82,61 +147,8 @@ __device__ __forceinline__ void v4_build_queries(const NextQ& nx, long long item
     if (qo->zero != nullptr)
       for (long long k = item0; k < qo->zero_cnt; k += stride) qo->zero[k] = 0.0f;
   }
-  constexpr int NKB = 2 * HH / 16, NKH = HH / 16, CGR = HH / 8;
-  constexpr int RGR = SPLIT ? 64 : 128;  // real rows per row group
-  const int nb = nx.nbatch > 1 ? nx.nbatch : 1;
-  const long long items = (long long)nb * nx.rgn * RGR * CGR;
-  for (long long it = item0; it < items; it += stride) {
-    const int rgg = (int)(it / (RGR * CGR));
-    const int lb = rgg / nx.rgn, rg = rgg - lb * nx.rgn;  // batch of the group, row group of the batch
-    const int rr = (int)((it / CGR) % RGR);
-    const int c8 = (int)(it % CGR);
-    const bool second = rg >= nx.rgn1;
-    const long long lrow = (long long)(second ? rg - nx.rgn1 : rg) * RGR + rr;
-    const long long qrow = (lrow < nx.n ? lrow : nx.n - 1) + (long long)lb * nx.n;  // padded rows repeat row n-1
-    const Operand& E = second ? nx.A2 : nx.A;
-    const int dir = second ? KGE_PO_ : nx.dir;
-    const unsigned short* a = (const unsigned short*)E.base + index_at(E.idx, qrow) * E.ld + c8 * 8;
-    const unsigned short* r = (const unsigned short*)nx.R.base + index_at(nx.R.idx, qrow) * nx.R.ld + c8 * 8;
-    const u32x4 a0 = *reinterpret_cast<const u32x4*>(a), a1 = *reinterpret_cast<const u32x4*>(a + HH);
-    const u32x4 r0 = *reinterpret_cast<const u32x4*>(r), r1 = *reinterpret_cast<const u32x4*>(r + HH);
-    u32x4 q0, q1, l0, l1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if constexpr (SPLIT) {
-        f32x2q Q0, Q1;
-        v4_q_f32<SCORER>(dir, a0[e], a1[e], r0[e], r1[e], Q0, Q1);
-        q0[e] = bf16_pack_hw(Q0);
-        q1[e] = bf16_pack_hw(Q1);
-        const f32x2q H0 = {__uint_as_float(q0[e] << 16), __uint_as_float(q0[e] & 0xffff0000u)};
-        const f32x2q H1 = {__uint_as_float(q1[e] << 16), __uint_as_float(q1[e] & 0xffff0000u)};
-        l0[e] = bf16_pack_hw(Q0 - H0);  // exact differences (Sterbenz-like: |q - q_hi| <= ulp_bf16(q) / 2)
-        l1[e] = bf16_pack_hw(Q1 - H1);
-      } else {
-        unsigned int x0, x1;
-        bf16_qpair_fast<SCORER>(dir, a0[e], a1[e], r0[e], r1[e], x0, x1);
-        q0[e] = x0;
-        q1[e] = x1;
-      }
-    }
-    // fragment-major (as the in-launch build below): K-block kb of 32-row block rb is 64 lanes x 16 B
-    const long long row = (long long)rg * 128 + rr;  // virtual row (SPLIT: the q_hi row; q_lo 64 rows behind)
-    u32x4* dst = nx.qf + (long long)lb * nx.qstride + ((row >> 5) * NKB) * 64 + (row & 31) + 32 * (c8 & 1);
-    dst[(c8 >> 1) * 64] = q0;
-    dst[(NKH + (c8 >> 1)) * 64] = q1;
-    if constexpr (WITH_Q16) {
-      if (qo->q16 != nullptr && lrow < nx.n) {
-        unsigned short* qr = qo->q16 + ((second ? nx.n : 0) + lrow) * (2 * HH) + c8 * 8;
-        *reinterpret_cast<u32x4*>(qr) = q0;
-        *reinterpret_cast<u32x4*>(qr + HH) = q1;
-      }
-    }
-    if constexpr (SPLIT) {
-      u32x4* dl = dst + 2 * NKB * 64;  // two 32-row blocks further
-      dl[(c8 >> 1) * 64] = l0;
-      dl[(NKH + (c8 >> 1)) * 64] = l1;
-    }
-  }
+  const long long items = v4_build_items<HH, SPLIT>(nx);
+  for (long long it = item0; it < items; it += stride) v4_build_item<SCORER, HH, SPLIT, WITH_Q16>(nx, it, qo);
 }
 
 template <int SCORER, int HH, int SPLIT>

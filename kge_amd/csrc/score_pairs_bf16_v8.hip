@@ -51,6 +51,7 @@
 #include "bf16_queries.hpp"
 #include <atomic>
 #include <cstdlib>
+#include <mutex>
 
 namespace kge {
 
@@ -74,7 +75,13 @@ struct V8Args {
   const u32x4* qf;
   unsigned long long* dbg;
   NextQ nx;
+  // the build of nx in CLAIMED slices: claim[0] = the next ticket, claim[1] = workgroups that are done; a
+  // slice = V8_SLICE items, one per thread; nullptr = a fixed 1 / gridDim.x of the items per workgroup
+  unsigned int* claim;
+  unsigned int nslices;
 };
+
+constexpr int V8_SLICE = 512;  // items of a claimed build slice: one per thread = 2,048 (split) / 1,024 fragment words
 
 #define KGE_V8_DMA(D, VO, P) \
   KGE_STALL(__LINE__ + 7000); \
@@ -120,7 +127,8 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
   // the slots in front of the barrier's and unit 2's pieces of slots 1 - 13
   constexpr int VMN_COLD = NST_LO + V8_PB + 4;
   static_assert(VMN_COLD == (M16 ? 22 : 25), "counted wait of the cold chain");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
+  // (16 bytes behind the ring: the ticket slots of the claimed build -- one array, so that the ring stays at LDS address 0)
+  __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM + 16];
   if (a.n < 0) smem[threadIdx.x] = 0;  // (never: keeps the allocation -- only asm names the array)
 
   const int b = blockIdx.x;
@@ -473,9 +481,55 @@ __global__ __launch_bounds__(512, 1) void pairs_bf16_v8_kernel(V8Args a) {
     }
 #endif
   }
-  // the NEXT group's query fragments: a slice per workgroup, behind its last unit
-  if (a.nx.qf != nullptr)
-    v4_build_queries<SCORER, HH, SPLIT>(a.nx, (long long)blockIdx.x * 512 + threadIdx.x, (long long)gridDim.x * 512);
+  // the NEXT group's query fragments, behind the workgroup's last unit
+  if (a.nx.qf != nullptr) {
+    unsigned int built = 0;
+    if (a.claim == nullptr) {
+      // fixed slices: 1 / gridDim.x of the items per workgroup (captured launches, a full counter table, V8_TAIL_FIXED)
+      v4_build_queries<SCORER, HH, SPLIT>(a.nx, (long long)blockIdx.x * 512 + threadIdx.x, (long long)gridDim.x * 512);
+    } else {
+      // CLAIMED slices: a workgroup that is done with its list takes slices of V8_SLICE items by ticket
+      // until the tickets run out -- the early finishers build, the last one finds nothing left.  It never waits for
+      // another workgroup: exactly one failing claim each, then the count of workgroups that are done; the one that
+      // completes it knows that nobody claims any more and sets both counters back to 0 for the stream's next launch.
+      // The ticket goes through two LDS slots behind the ring, used in turn: one barrier per round (slot i & 1 is
+      // written again in round i + 2, behind barrier i + 1, which a wave passes after it has read round i's ticket).
+      // (LDS by address in asm, as everywhere in this kernel: a C++ access through the array became a FLAT access, whose
+      // wait is vmcnt(0) -- every wave would stand behind its score stores before it builds)
+      const long long items = v4_build_items<HH, SPLIT>(a.nx);
+      for (int i = 0;; i ^= 1) {
+        const unsigned int slot = (unsigned int)(SMEM + 4 * i);
+        if (tid == 0) {
+          const unsigned int mine = atomicAdd(a.claim, 1u);
+          asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(slot), "v"(mine) : "memory");
+        }
+        KGE_BARRIER();
+        unsigned int got;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(got) : "v"(slot) : "memory");
+        const unsigned int ticket = __builtin_amdgcn_readfirstlane(got);
+        if (ticket >= a.nslices) break;
+        const long long it = (long long)ticket * V8_SLICE + tid;
+        if (it < items) v4_build_item<SCORER, HH, SPLIT>(a.nx, it);
+        ++built;
+      }
+      if (tid == 0 && atomicAdd(a.claim + 1, 1u) == gridDim.x - 1) {
+        atomicExch(a.claim, 0u);
+        atomicExch(a.claim + 1, 0u);
+      }
+    }
+#ifdef KGE_V8_PROBES
+    // PROBE build only (tools/v8_tail_probe.py): this workgroup's build is done -- wave 0's stores acknowledged.
+    // Slots 52 - 54 of the debug buffer: nothing reads them.
+    if (a.dbg != nullptr && tid == 0) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      a.dbg[(long long)blockIdx.x * 64 + 52] = __builtin_readcyclecounter();
+      a.dbg[(long long)blockIdx.x * 64 + 53] = wall_clock64();
+      a.dbg[(long long)blockIdx.x * 64 + 54] = built;
+    }
+#else
+    (void)built;
+#endif
+  }
 }
 
 void v6_set_stamps(unsigned long long* p);
@@ -499,9 +553,71 @@ static int v8_cu_count() {
   return v;
 }
 
-// launches issued by this process (kge_debug_launch_count): 0 = pairs_bf16_v8_kernel, 1 = pairs_bf16_v8_rank_kernel
-static int g_v8_launches[2] = {0, 0};
-int v8_launch_count(int which) { return (which == 0 || which == 1) ? __atomic_load_n(&g_v8_launches[which], __ATOMIC_RELAXED) : -1; }
+// launches issued by this process (kge_debug_launch_count): 0 = pairs_bf16_v8_kernel, 1 = pairs_bf16_v8_rank_kernel,
+// 2 = those of 0 that build the next group in claimed slices
+static int g_v8_launches[3] = {0, 0, 0};
+int v8_launch_count(int which) { return (which >= 0 && which <= 2) ? __atomic_load_n(&g_v8_launches[which], __ATOMIC_RELAXED) : -1; }
+
+// ---- the counter pairs of the claimed build -----------------------------------------------------------
+// One pair (next ticket, workgroups done) per (device, stream) the library has seen: launches of one stream are serial
+// and every launch leaves its pair at 0, launches of different streams may run side by side and never share one.
+// Allocated on first use and zeroed once, by a memset in front of that first launch on its stream.  nullptr = fixed
+// slices: the stream is being captured (a captured launch may be replayed on any stream, next to another replay), the
+// table is full, or the allocation failed.
+constexpr int V8_CLAIM_SLOTS = 64;
+struct V8ClaimSlot {
+  int dev;
+  hipStream_t st;
+  unsigned int* pair;
+};
+static V8ClaimSlot g_v8_claim[V8_CLAIM_SLOTS];
+static int g_v8_claim_n = 0;
+static std::mutex g_v8_claim_mu;
+
+static unsigned int* v8_claim_find(int dev, hipStream_t st) {  // (under the mutex)
+  for (int i = 0; i < g_v8_claim_n; ++i)
+    if (g_v8_claim[i].st == st && g_v8_claim[i].dev == dev) return g_v8_claim[i].pair;
+  return nullptr;
+}
+
+static unsigned int* v8_claim_pair(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+    (void)hipGetLastError();  // (e.g. the legacy stream while another stream captures: that launch fails on its own)
+    return nullptr;
+  }
+  if (cs != hipStreamCaptureStatusNone) return nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(g_v8_claim_mu);
+  if (unsigned int* p = v8_claim_find(dev, st)) return p;
+  if (g_v8_claim_n == V8_CLAIM_SLOTS) return nullptr;
+  unsigned int* p = nullptr;
+  if (hipMalloc((void**)&p, 256) != hipSuccess || hipMemsetAsync(p, 0, 256, st) != hipSuccess) {
+    (void)hipGetLastError();
+    if (p != nullptr) (void)hipFree(p);
+    return nullptr;
+  }
+  g_v8_claim[g_v8_claim_n++] = V8ClaimSlot{dev, st, p};
+  return p;
+}
+
+// kge_debug_v8_claim_counters: the pair of `st` on the current device read (get2) and / or overwritten (set2) behind
+// everything the device has been given; 1 = done, 0 = the stream has no pair (yet)
+int v8_claim_counters(hipStream_t st, const unsigned int* set2, unsigned int* get2) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return KGE_ERR_LAUNCH;
+  unsigned int* p;
+  {
+    std::lock_guard<std::mutex> lock(g_v8_claim_mu);
+    p = v8_claim_find(dev, st);
+  }
+  if (p == nullptr) return 0;
+  if (hipDeviceSynchronize() != hipSuccess) return KGE_ERR_LAUNCH;
+  if (get2 != nullptr && hipMemcpy(get2, p, 8, hipMemcpyDeviceToHost) != hipSuccess) return KGE_ERR_LAUNCH;
+  if (set2 != nullptr && hipMemcpy(p, set2, 8, hipMemcpyHostToDevice) != hipSuccess) return KGE_ERR_LAUNCH;
+  return 1;
+}
 
 template <int SCORER, int SPLIT>
 static int launch_v8(V8Args& a, int sc1, hipStream_t st) {
@@ -620,6 +736,16 @@ int run_pairs_bf16_v8(int scorer, bool split, const Operand& TG, bool two_sided,
                                               out2_off, pol, reserve_cus, st);
     if (rc == KGE_OK) __atomic_fetch_add(&g_v8_launches[0], 1, __ATOMIC_RELAXED);
     return rc;
+  }
+  // the next group's build in claimed slices (V8_TAIL_FIXED = 1: the fixed slice per workgroup; also whenever the
+  // stream has no counter pair -- v8_claim_pair)
+  if (nx.qf != nullptr && sw(SW_V8_TAIL_FIXED) != 1) {
+    const long long items = split ? v4_build_items<256, 1>(nx) : v4_build_items<256, 0>(nx);
+    const long long nslices = (items + V8_SLICE - 1) / V8_SLICE;
+    if (nslices < (1LL << 31) - 4096 && (a.claim = v8_claim_pair(st)) != nullptr) {
+      a.nslices = (unsigned int)nslices;
+      __atomic_fetch_add(&g_v8_launches[2], 1, __ATOMIC_RELAXED);
+    }
   }
 #define KGE_V8L(SC) return split ? launch_v8<SC, 1>(a, sc1, st) : launch_v8<SC, 0>(a, sc1, st)
   if (scorer == KGE_COMPLEX) { KGE_V8L(KGE_COMPLEX); }

@@ -27,6 +27,7 @@ enum Switch : int {
   SW_V8,                   // 0: the persistent store kernel declines everything; 1: takes single batches too
   SW_V8_VAR,               // probe builds (-DKGE_V8_PROBES)
   SW_V8_MFMA32,            // 1: the split d = 512 store chains on v_mfma_f32_32x32x16_bf16 (default: 16x16x32, the same bits)
+  SW_V8_TAIL_FIXED,        // 1: the d = 512 store kernel builds the next group in one fixed slice per workgroup (default: claimed slices)
   SW_V8R_PROBE,            // probe builds (-DKGE_V8_PROBES)
   SW_TRANSE_GENERIC,       // 1: TransE score_sp / score_po on the generic 4 x 4 kernel (the cross-check of pairs_transe_kernel)
   SW_TOPK_COL_TILES,       // column tiles a workgroup of topk_select_kernel walks (tests: several groups at small m)
