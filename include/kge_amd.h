@@ -1438,6 +1438,85 @@ int kge_sparse_adam_step_touched(float* param, int64_t param_ld, float* grad, in
                                  int64_t dim, kge_adam_clock* clock, double lr, double beta1, double beta2, float eps,
                                  void* bf16_copy, int64_t copy_ld, void* stream);
 
+/* ---- frequency-weighted penalties in the optimizer's pass (csrc/wpenalty.hip) -----------------
+ * LookupEmbedder.penalty with regularize_args.weighted: true (kge/model/embedder/lookup_embedder.py:148-173,
+ * lookup_embedder.yaml `regularize_args.weighted`), called with the batch's indexes (kge_model.py:607-634).  With
+ * m = len(indexes) and c_r = the occurrences of row r among them the term is
+ *   weight / p / m * sum_r c_r * sum_j |x_rj|^p        (n3, complex: |z|^3, |z| = sqrt(re^2 + im^2 + 1e-14))
+ * and its gradient (weight * c_r / m) * sign(x) |x|^(p-1)  (n3: (weight * c_r / m) * |z| * re, ... * im): a function of
+ * the element and its row's count.  kge_penalty_count builds the counts on the device; the four entries below are the
+ * existing updates with the term's gradient added in registers, the row factor being
+ *   f_r = weight * ((float)counts[r] / (float)m)      -- one IEEE float32 division, then one float32 product
+ * (counts[r] == m gives f_r == weight exactly).  A row whose count is 0 gets no penalty gradient -- nothing is added to
+ * its gradient -- and adds nothing to the value.
+ *
+ * Index block of kge_penalty_count: as kge_touched_mark -- element (i, j) of an [n, k] block is
+ * ids.ptr[(i * ld + j) * ids.stride], int32 or int64 (triples[:, 1]: k = 1, ld = 1, stride 3; two neighbouring columns of
+ * an [n, 3] matrix: k = 2, ld = 3, stride 1; the S and the O column of [n, 3] triples are not such a block: two calls
+ * on one count buffer, which is what a count of the concatenated vector is).  counts[id] += 1 per
+ * occurrence by integer atomic add (exact, order-free: the same counts on every run); bitmap != NULL: the row's bit of
+ * a touched-row bitmap is set as well.  An id outside [0, num_rows) does nothing.  Nothing is read on the host
+ * (capturable); n * k == 0: KGE_OK without a launch.
+ * KGE_ERR_INVALID_ARG: n, k or num_rows < 0, ld < k, a NULL or not 4-byte aligned counts, a NULL ids.ptr (n * k > 0), an
+ * ids.itype other than int32 / int64, ids.stride < 1, ids.start != 0. */
+int kge_penalty_count(kge_index ids, int64_t n, int64_t k, int64_t ld, int64_t num_rows, uint32_t* counts,
+                      uint32_t* bitmap /* or NULL */, void* stream);
+
+/* The weighted term of one table.  kind, p, row_dim: as kge_penalty_seg (0: none; 1: lp with p in 1..3; 2: n3 on a
+ * complex space, row_dim % 8 == 0), but row_dim is needed for every kind != 0: it is what makes rows of the elements.
+ * `weight`: regularize_weight, NOT doubled for a shared entity embedder (kge_model.py:612-621 passes the subject and
+ * object indexes as one [n, 2] tensor).  `counts`: [num_rows] device words (kge_penalty_count), `m` = len(indexes) as
+ * the reference divides by it (lookup_embedder.py:171): n for triples[:, P] and ALSO n for the [n, 2] entity block,
+ * whose 2n entries are counted -- so a count may reach 2m.  A count of 2^24 or more (possible only with m >= 2^23
+ * under two-column counting) is rounded to nearest even by (float)counts[r]: f_r then carries a third rounding.  *value (a device double the caller zeroed) receives
+ *   sum_r counts[r] * sum_j |x_rj|^p    (n3: |z|^3)
+ * of the PRE-step parameters: |x|^p per element in float32, the product with the count and every sum in float64; the
+ * term the reference's trace shows is weight / p / m times it.
+ * Clearing: the kernel stores zero over every count word it has read.  The dense entries read all num_rows words; the
+ * touched-row entries the words of the marked rows -- `counts` must be zero outside the marked rows on entry, as the
+ * gradient buffer must (kge_penalty_count given the bitmap marks what it counts).  Either way the buffer is all zero
+ * after the step, ready for the next batch's counts. */
+typedef struct kge_wpenalty_seg {
+  int32_t kind, p;
+  float weight;
+  int64_t row_dim;
+  double* value;          /* [1] device, or NULL for kind 0 */
+  const uint32_t* counts; /* [count / row_dim] device (cleared by the step), or NULL for kind 0 */
+  int64_t m;
+} kge_wpenalty_seg;
+
+/* kge_adagrad_step_multi_penalty (train.py:417-436: the term is back-propagated between the batch and
+ * optimizer.step()) with weighted terms: per element exactly that entry's arithmetic with `weight` replaced by f_r of
+ * the element's row.  Argument checks: those of kge_adagrad_step_multi_penalty, and for kind != 0
+ * KGE_ERR_INVALID_ARG for row_dim <= 0, count % row_dim != 0, a NULL or not 4-byte aligned counts, m <= 0, a NULL pens;
+ * KGE_ERR_UNSUPPORTED for m >= 2^24 (the float32 quotient's operands must be exact), row_dim > 2^28. */
+int kge_adagrad_step_multi_wpenalty(const kge_adagrad_seg* segs, const kge_wpenalty_seg* pens, int num_segs,
+                                    void* stream);
+
+/* kge_adam_step_multi (device clock; optimizer.py:15-20 with train.optimizer.default.type: Adam) with weighted terms:
+ * the PEN path's arithmetic with `weight` replaced by f_r.  Argument checks: those of kge_adam_step_multi, and the
+ * weighted record's as above (pens must not be NULL).  Clocks advance as there. */
+int kge_adam_step_multi_wpenalty(const kge_adam_seg* segs, const kge_wpenalty_seg* pens, int num_segs, void* stream);
+
+/* kge_adagrad_step_touched (lookup_embedder.yaml:78-81's row-wise update) with g + f_r * ... in registers on the marked
+ * rows, both on the four-floats-per-lane and on the scalar path.  The same clearing contract for grad and bitmap, and
+ * the counts of the marked rows are cleared; rows whose bit is clear are neither read nor written, their count word
+ * included.  pen->row_dim must equal dim.  Argument checks: those of kge_adagrad_step_touched, the weighted record's as
+ * above, KGE_ERR_INVALID_ARG for a NULL pen or row_dim != dim (kind != 0). */
+int kge_adagrad_step_touched_wpenalty(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* state_sum,
+                                      int64_t sum_ld, uint32_t* bitmap, int64_t num_rows, int64_t dim, float minus_clr,
+                                      float eps, void* bf16_copy, int64_t copy_ld, const kge_wpenalty_seg* pen,
+                                      void* stream);
+
+/* kge_sparse_adam_step_touched (optimizer.py:15-20 with type: SparseAdam) with g + f_r * ... in registers on the marked
+ * rows; the clock, the clearing contract and the argument checks of that entry plus those of
+ * kge_adagrad_step_touched_wpenalty. */
+int kge_sparse_adam_step_touched_wpenalty(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* exp_avg,
+                                          int64_t avg_ld, float* exp_avg_sq, int64_t sq_ld, uint32_t* bitmap,
+                                          int64_t num_rows, int64_t dim, kge_adam_clock* clock, double lr, double beta1,
+                                          double beta2, float eps, void* bf16_copy, int64_t copy_ld,
+                                          const kge_wpenalty_seg* pen, void* stream);
+
 /* ---- backward (autograd twins) ------------------------------------------ */
 /* All gradients are f32 and OVERWRITTEN; tables/embeddings must be f32, except
  * kge_score_pairs_bwd for ComplEx/DistMult, which also takes bf16 tables (mixed-precision

@@ -71,6 +71,11 @@ class KgePenaltySeg(ctypes.Structure):
                 ("value", c_vp)]
 
 
+class KgeWPenaltySeg(ctypes.Structure):  # kge_wpenalty_seg
+    _fields_ = [("kind", ctypes.c_int32), ("p", ctypes.c_int32), ("weight", ctypes.c_float), ("row_dim", c_i64),
+                ("value", c_vp), ("counts", c_vp), ("m", c_i64)]
+
+
 class KgeAdamClock(ctypes.Structure):
     _fields_ = [("t", c_i64), ("beta1_pow", ctypes.c_double), ("beta2_pow", ctypes.c_double),
                 ("step_size", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float)]
@@ -264,6 +269,18 @@ PROTOTYPES = {
     "kge_sparse_adam_step_touched": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                                     c_i64, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                     ctypes.c_float, c_vp, c_i64, c_vp]),
+    "kge_penalty_count": (ctypes.c_int, [KgeIndex, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "kge_adagrad_step_multi_wpenalty": (ctypes.c_int, [ctypes.POINTER(KgeAdagradSeg), ctypes.POINTER(KgeWPenaltySeg),
+                                                       ctypes.c_int, c_vp]),
+    "kge_adam_step_multi_wpenalty": (ctypes.c_int, [ctypes.POINTER(KgeAdamSeg), ctypes.POINTER(KgeWPenaltySeg),
+                                                    ctypes.c_int, c_vp]),
+    "kge_adagrad_step_touched_wpenalty": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64,
+                                                         ctypes.c_float, ctypes.c_float, c_vp, c_i64,
+                                                         ctypes.POINTER(KgeWPenaltySeg), c_vp]),
+    "kge_sparse_adam_step_touched_wpenalty": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                                             c_i64, c_i64, c_vp, ctypes.c_double, ctypes.c_double,
+                                                             ctypes.c_double, ctypes.c_float, c_vp, c_i64,
+                                                             ctypes.POINTER(KgeWPenaltySeg), c_vp]),
     "kge_score_pairs_bwd": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, KgeIndex,
                                            c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                            c_i64, c_vp]),

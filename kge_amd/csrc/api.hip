@@ -275,6 +275,18 @@ int run_adam_multi(const kge_adam_seg* segs, const kge_penalty_seg* pens, int nu
 int run_adagrad_rows(float* param, long long param_ld, const float* grows, long long g_ld, float* sum, long long sum_ld,
                      const long long* rows, long long nrows, int dim, float minus_clr, float eps,
                      unsigned short* copy16, long long c_ld, hipStream_t st);
+int run_penalty_count(const Index& ids, long long n, long long k, long long ld, long long num_rows, unsigned int* counts,
+                      unsigned int* bitmap, bool merge, hipStream_t st);
+int run_adagrad_multi_wpen(const kge_adagrad_seg* segs, const kge_wpenalty_seg* pens, int num, hipStream_t st);
+int run_adam_multi_wpen(const kge_adam_seg* segs, const kge_wpenalty_seg* pens, int num, hipStream_t st);
+int run_adagrad_touched_wpen(float* param, long long param_ld, float* grad, long long grad_ld, float* sum,
+                             long long sum_ld, unsigned int* bitmap, long long num_rows, int dim, float minus_clr,
+                             float eps, unsigned short* copy16, long long c_ld, const kge_wpenalty_seg& pen,
+                             hipStream_t st);
+int run_sparse_adam_touched_wpen(float* param, long long param_ld, float* grad, long long grad_ld, float* m1,
+                                 long long m1_ld, float* m2, long long m2_ld, unsigned int* bitmap, long long num_rows,
+                                 int dim, kge_adam_clock* clock, double lr, double beta1, double beta2, float eps,
+                                 unsigned short* copy16, long long c_ld, const kge_wpenalty_seg& pen, hipStream_t st);
 int run_touched_mark(const Index& ids, long long n, long long k, long long ld, long long num_rows, unsigned int* bitmap,
                      hipStream_t st);
 int run_adagrad_touched(float* param, long long param_ld, float* grad, long long grad_ld, float* sum, long long sum_ld,
@@ -614,12 +626,13 @@ int pairs_entry(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t 
 
 // ---- measurement switches (switches.hpp, include/kge_amd_debug.h) ----
 namespace kge {
-static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-static_assert(SW_COUNT == 22, "g_switch's initialiser");
+static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(SW_COUNT == 23, "g_switch's initialiser");
 static const char* const g_switch_name[SW_COUNT] = {
     "ONE_CALL_PREPARED", "ONE_CALL_V8", "ONE_CALL_V8_MIN_ROWS", "V8_RANK", "RANK_FUSED_FRONT", "BWD_GEMM_LIB",
     "CE_V3", "CE_V8", "V4_OWN_BUILD", "V4_INTERLEAVE", "V4_STORE_SC1", "V6", "V7", "V7_NOSTORE", "V7_PROBE", "V8",
-    "V8_VAR", "V8_MFMA32", "V8_TAIL_FIXED", "V8R_PROBE", "TRANSE_GENERIC", "TOPK_COL_TILES"};
+    "V8_VAR", "V8_MFMA32", "V8_TAIL_FIXED", "V8R_PROBE", "TRANSE_GENERIC", "TOPK_COL_TILES",
+    "PENALTY_COUNT_PLAIN"};
 long long sw(Switch s) { return __atomic_load_n(&g_switch[(int)s], __ATOMIC_RELAXED); }
 static int switch_index(const char* name) {
   if (name == nullptr) return -1;
@@ -2764,6 +2777,102 @@ int kge_sparse_adam_step_touched(float* param, int64_t param_ld, float* grad, in
   return run_sparse_adam_touched(param, param_ld, grad, grad_ld, exp_avg, avg_ld, exp_avg_sq, sq_ld, bitmap, num_rows,
                                  (int)dim, clock, lr, beta1, beta2, eps, (unsigned short*)bf16_copy, copy_ld,
                                  (hipStream_t)stream);
+}
+
+// ---- frequency-weighted penalties (wpenalty.hip) ----
+int kge_penalty_count(kge_index ids, int64_t n, int64_t k, int64_t ld, int64_t num_rows, uint32_t* counts,
+                      uint32_t* bitmap, void* stream) {
+  KGE_RANGE();
+  if (n < 0 || k < 0 || num_rows < 0 || ld < k) return KGE_ERR_INVALID_ARG;
+  if (!counts || ((uintptr_t)counts & 3)) return KGE_ERR_INVALID_ARG;
+  if (n * k == 0) return KGE_OK;
+  int rc = check_index(ids, false, n * k);
+  if (rc) return rc;
+  if (!ids.ptr) return KGE_ERR_INVALID_ARG;
+  return run_penalty_count(make_index(ids), n, k, ld, num_rows, counts, bitmap, sw(SW_PENALTY_COUNT_PLAIN) != 1,
+                           (hipStream_t)stream);
+}
+
+// The checks of one weighted record against its table of `count` elements (kind 0: nothing to check).
+static int check_wpenalty(const kge_wpenalty_seg& q, int64_t count) {
+  if (q.kind < 0 || q.kind > 2) return KGE_ERR_INVALID_ARG;
+  if (q.kind == 0) return KGE_OK;
+  if (!q.value || ((uintptr_t)q.value & 7)) return KGE_ERR_INVALID_ARG;
+  if (!q.counts || ((uintptr_t)q.counts & 3)) return KGE_ERR_INVALID_ARG;
+  if (q.row_dim <= 0 || count % q.row_dim != 0 || q.m <= 0) return KGE_ERR_INVALID_ARG;
+  if (q.kind == 2 && q.row_dim % 8 != 0) return KGE_ERR_INVALID_ARG;
+  if (q.kind == 1 && (q.p < 1 || q.p > 3)) return KGE_ERR_UNSUPPORTED;
+  if (q.m >= (1LL << 24) || q.row_dim > (1LL << 28)) return KGE_ERR_UNSUPPORTED;
+  return KGE_OK;
+}
+
+int kge_adagrad_step_multi_wpenalty(const kge_adagrad_seg* segs, const kge_wpenalty_seg* pens, int num_segs,
+                                    void* stream) {
+  KGE_RANGE();
+  if (num_segs < 0 || num_segs > KGE_ADAGRAD_MAX_SEGS || (num_segs > 0 && (!segs || !pens))) return KGE_ERR_INVALID_ARG;
+  for (int j = 0; j < num_segs; ++j) {
+    const kge_adagrad_seg& g = segs[j];
+    if (g.count < 0 || (g.count > 0 && (!g.param || !g.grad || !g.state_sum))) return KGE_ERR_INVALID_ARG;
+    if (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.state_sum) & 15) return KGE_ERR_INVALID_ARG;
+    if (g.bf16_copy && ((uintptr_t)g.bf16_copy & 7)) return KGE_ERR_INVALID_ARG;
+    const int rc = check_wpenalty(pens[j], g.count);
+    if (rc) return rc;
+  }
+  return run_adagrad_multi_wpen(segs, pens, num_segs, (hipStream_t)stream);
+}
+
+int kge_adam_step_multi_wpenalty(const kge_adam_seg* segs, const kge_wpenalty_seg* pens, int num_segs, void* stream) {
+  KGE_RANGE();
+  if (num_segs < 0 || num_segs > KGE_ADAM_MAX_SEGS || (num_segs > 0 && (!segs || !pens))) return KGE_ERR_INVALID_ARG;
+  for (int j = 0; j < num_segs; ++j) {
+    const kge_adam_seg& g = segs[j];
+    if (g.count < 0 || (g.count > 0 && (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq || !g.clock)))
+      return KGE_ERR_INVALID_ARG;
+    if (((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15)
+      return KGE_ERR_INVALID_ARG;
+    if (((uintptr_t)g.bf16_copy | (uintptr_t)g.clock) & 7) return KGE_ERR_INVALID_ARG;
+    if (!(g.beta1 >= 0.0 && g.beta1 < 1.0 && g.beta2 >= 0.0 && g.beta2 < 1.0)) return KGE_ERR_INVALID_ARG;
+    for (int i = 0; i < j; ++i)  // a record shared by two segments would be advanced twice
+      if (g.count > 0 && segs[i].count > 0 && segs[i].clock == g.clock) return KGE_ERR_INVALID_ARG;
+    const int rc = check_wpenalty(pens[j], g.count);
+    if (rc) return rc;
+  }
+  return run_adam_multi_wpen(segs, pens, num_segs, (hipStream_t)stream);
+}
+
+int kge_adagrad_step_touched_wpenalty(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* state_sum,
+                                      int64_t sum_ld, uint32_t* bitmap, int64_t num_rows, int64_t dim, float minus_clr,
+                                      float eps, void* bf16_copy, int64_t copy_ld, const kge_wpenalty_seg* pen,
+                                      void* stream) {
+  KGE_RANGE();
+  if (num_rows < 0 || dim < 0 || dim > 0x7fffffff) return KGE_ERR_INVALID_ARG;
+  if (num_rows > 0 && (!param || !grad || !state_sum || !bitmap)) return KGE_ERR_INVALID_ARG;
+  if (param_ld < dim || grad_ld < dim || sum_ld < dim || (bf16_copy && copy_ld < dim)) return KGE_ERR_INVALID_ARG;
+  if (!pen || (pen->kind != 0 && pen->row_dim != dim)) return KGE_ERR_INVALID_ARG;
+  const int rc = check_wpenalty(*pen, dim);
+  if (rc) return rc;
+  return run_adagrad_touched_wpen(param, param_ld, grad, grad_ld, state_sum, sum_ld, bitmap, num_rows, (int)dim,
+                                  minus_clr, eps, (unsigned short*)bf16_copy, copy_ld, *pen, (hipStream_t)stream);
+}
+
+int kge_sparse_adam_step_touched_wpenalty(float* param, int64_t param_ld, float* grad, int64_t grad_ld, float* exp_avg,
+                                          int64_t avg_ld, float* exp_avg_sq, int64_t sq_ld, uint32_t* bitmap,
+                                          int64_t num_rows, int64_t dim, kge_adam_clock* clock, double lr, double beta1,
+                                          double beta2, float eps, void* bf16_copy, int64_t copy_ld,
+                                          const kge_wpenalty_seg* pen, void* stream) {
+  KGE_RANGE();
+  if (num_rows < 0 || dim < 0 || dim > 0x7fffffff) return KGE_ERR_INVALID_ARG;
+  if (num_rows > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !bitmap)) return KGE_ERR_INVALID_ARG;
+  if (param_ld < dim || grad_ld < dim || avg_ld < dim || sq_ld < dim || (bf16_copy && copy_ld < dim))
+    return KGE_ERR_INVALID_ARG;
+  if (!clock || ((uintptr_t)clock & 7)) return KGE_ERR_INVALID_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return KGE_ERR_INVALID_ARG;
+  if (!pen || (pen->kind != 0 && pen->row_dim != dim)) return KGE_ERR_INVALID_ARG;
+  const int rc = check_wpenalty(*pen, dim);
+  if (rc) return rc;
+  return run_sparse_adam_touched_wpen(param, param_ld, grad, grad_ld, exp_avg, avg_ld, exp_avg_sq, sq_ld, bitmap,
+                                      num_rows, (int)dim, clock, lr, beta1, beta2, eps, (unsigned short*)bf16_copy,
+                                      copy_ld, *pen, (hipStream_t)stream);
 }
 
 int kge_bce_fwd(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, const int64_t* lbl_rowptr,

@@ -556,6 +556,21 @@ int run_adam_multi(const kge_adam_seg* segs, const kge_penalty_seg* pens, int nu
   return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
 }
 
+// adam_clock_kernel for `num` records: the clock launch of kge_adam_step_multi_wpenalty (wpenalty.hip)
+int run_adam_clocks(kge_adam_clock* const* clocks, const double* lr, const double* beta1, const double* beta2, int num,
+                    hipStream_t st) {
+  AdamClocks c{};
+  for (int j = 0; j < num; ++j) {
+    c.clock[j] = clocks[j];
+    c.lr[j] = lr[j];
+    c.beta1[j] = beta1[j];
+    c.beta2[j] = beta2[j];
+  }
+  c.num = num;
+  hipLaunchKernelGGL(adam_clock_kernel, dim3(1), dim3(64), 0, st, c);
+  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+}
+
 // ---- row-sparse Adagrad (lookup_embedder.yaml:78-81 `sparse: True` -> torch.optim.Adagrad's sparse
 // path): only the `nrows` listed rows of the table have a gradient (coalesced: unique row ids, one
 // [dim] value row each).  One wave per listed row:

@@ -31,6 +31,7 @@ enum Switch : int {
   SW_V8R_PROBE,            // probe builds (-DKGE_V8_PROBES)
   SW_TRANSE_GENERIC,       // 1: TransE score_sp / score_po on the generic 4 x 4 kernel (the cross-check of pairs_transe_kernel)
   SW_TOPK_COL_TILES,       // column tiles a workgroup of topk_select_kernel walks (tests: several groups at small m)
+  SW_PENALTY_COUNT_PLAIN,  // 1: kge_penalty_count sends one atomic per lane (default: duplicates merged inside a wave first)
   SW_COUNT
 };
 

@@ -237,6 +237,12 @@ __global__ __launch_bounds__(64) void sparse_adam_clock_kernel(kge_adam_clock* k
   k->bias_correction2_sqrt = (float)root;
 }
 
+// sparse_adam_clock_kernel on its own: the clock launch of kge_sparse_adam_step_touched_wpenalty (wpenalty.hip)
+int run_sparse_adam_clock(kge_adam_clock* clock, double lr, double beta1, double beta2, hipStream_t st) {
+  hipLaunchKernelGGL(sparse_adam_clock_kernel, dim3(1), dim3(64), 0, st, clock, lr, beta1, beta2);
+  return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
+}
+
 template <bool VEC, int GROUP>
 __global__ __launch_bounds__(256) void sparse_adam_touched_kernel(
     float* __restrict__ param, long long param_ld, float* __restrict__ grad, long long grad_ld, float* __restrict__ m1,

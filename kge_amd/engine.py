@@ -1514,6 +1514,129 @@ def sparse_adam_step_touched(param: torch.Tensor, grad: torch.Tensor, exp_avg: t
             0 if bf16_copy is None else ld(bf16_copy), _stream_handle(device)), "kge_sparse_adam_step_touched")
 
 
+# ---- frequency-weighted penalties in the optimizer's pass (csrc/wpenalty.hip) ------------------
+WPENALTY_MAX_M = 1 << 24   # the row factor's float32 quotient needs exact operands
+
+
+def penalty_counts(num_rows: int, device) -> torch.Tensor:
+    """A zero count buffer for a table of `num_rows` rows: int32 words (read as uint32 by the kernels)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"kge_amd: the penalty count buffer lives on a GPU, not on '{device}' (no CPU path)")
+    return torch.zeros(max(int(num_rows), 1), dtype=torch.int32, device=device)
+
+
+def _counts_ok(counts, num_rows, device, what):
+    if not (torch.is_tensor(counts) and counts.device == device and counts.dtype == torch.int32
+            and counts.dim() == 1 and counts.is_contiguous() and counts.numel() >= num_rows):
+        raise ValueError(f"kge_amd: {what}: the counts are a contiguous int32 vector of at least num_rows words on "
+                         f"{device}")
+
+
+def penalty_count(ids: torch.Tensor, counts: torch.Tensor, num_rows: int, bitmap: torch.Tensor = None) -> None:
+    """counts[id] += 1 for every id in `ids` (kge_penalty_count): an int32 / int64 index vector of any positive stride
+    (triples[:, 1]) or an [n, k] block (a slice of a wider matrix is fine), as touched_mark takes them.  `bitmap`: the
+    touched-row bitmap whose bits are set for the same rows.  Ids outside [0, num_rows) do nothing; nothing is read on
+    the host."""
+    device = counts.device if torch.is_tensor(counts) else None
+    if device is None or device.type != "cuda":
+        raise RuntimeError("kge_amd: penalty_count counts on a GPU (no CPU path)")
+    _counts_ok(counts, int(num_rows), device, "penalty_count")
+    if bitmap is not None:
+        _bitmap_ok(bitmap, int(num_rows), device, "penalty_count")
+    if not torch.is_tensor(ids) or ids.device != device:
+        raise RuntimeError(f"kge_amd: penalty_count: ids and counts must be on the same GPU ({device})")
+    if ids.dtype not in (torch.int32, torch.int64):
+        ids = ids.long()
+    if ids.dim() == 2:
+        n, k = ids.shape
+        s0, s1 = ids.stride()
+        if n * k > 0 and (s1 < 1 or (n > 1 and (s0 < k * s1 or s0 % s1 != 0))):
+            ids = ids.contiguous()
+            s0, s1 = ids.stride()
+        stride, ld = (max(s1, 1), s0 // max(s1, 1)) if n > 1 else (max(s1, 1), max(k, 1))
+    else:
+        if ids.dim() != 1:
+            ids = ids.reshape(-1)
+        n, k, ld = ids.numel(), 1, 1
+        stride = ids.stride(0) if n > 1 else 1
+        if stride < 1:
+            ids, stride = ids.contiguous(), 1
+    if n * k == 0:
+        return
+    ix = KgeIndex(ids.data_ptr(), I32 if ids.dtype == torch.int32 else I64, 0, stride)
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_penalty_count(ix, n, k, ld, int(num_rows), counts.data_ptr(),
+                                                None if bitmap is None else bitmap.data_ptr(),
+                                                _stream_handle(device)), "kge_penalty_count")
+
+
+def wpenalty_seg(kind: int, p: int, weight: float, row_dim: int, value_ptr, counts: torch.Tensor, m: int):
+    """A kge_wpenalty_seg record (kind 0: every other field is ignored)."""
+    if kind == 0:
+        return _lib.KgeWPenaltySeg(0, 0, 0.0, 0, None, None, 0)
+    return _lib.KgeWPenaltySeg(int(kind), int(p), float(weight), int(row_dim), value_ptr, counts.data_ptr(), int(m))
+
+
+def _touched_tables_ok(name, device, E, d, tables, bf16_copy):
+    for t, what in tables:
+        if not (t.device == device and t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (E, d)
+                and (d <= 1 or t.stride(1) == 1) and (E <= 1 or t.stride(0) >= d)):
+            raise ValueError(f"kge_amd: {name}: {what} is float32 [E, d] with unit inner stride on {device}")
+    if bf16_copy is not None and not (bf16_copy.device == device and bf16_copy.element_size() == 2
+                                      and tuple(bf16_copy.shape) == (E, d) and (d <= 1 or bf16_copy.stride(1) == 1)
+                                      and (E <= 1 or bf16_copy.stride(0) >= d)):
+        raise ValueError(f"kge_amd: {name}: bf16_copy is a 2-byte [E, d] tensor with unit inner stride")
+
+
+def adagrad_step_touched_wpenalty(param: torch.Tensor, grad: torch.Tensor, state_sum: torch.Tensor,
+                                  bitmap: torch.Tensor, minus_clr: float, eps: float, pen,
+                                  bf16_copy: torch.Tensor = None) -> None:
+    """adagrad_step_touched with a weighted penalty term added to the marked rows' gradients in registers
+    (kge_adagrad_step_touched_wpenalty); `pen`: a wpenalty_seg record whose counts are cleared with the bitmap."""
+    device = param.device
+    if device.type != "cuda":
+        raise RuntimeError(f"kge_amd: adagrad_step_touched_wpenalty steps on a GPU, not on '{device}' (no CPU path)")
+    E, d = param.shape
+    _touched_tables_ok("adagrad_step_touched_wpenalty", device, E, d,
+                       ((param, "param"), (grad, "grad"), (state_sum, "state_sum")), bf16_copy)
+    _bitmap_ok(bitmap, E, device, "adagrad_step_touched_wpenalty")
+    ld = lambda t: t.stride(0) if E > 1 else max(d, 1)
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_adagrad_step_touched_wpenalty(
+            param.data_ptr(), ld(param), grad.data_ptr(), ld(grad), state_sum.data_ptr(), ld(state_sum),
+            bitmap.data_ptr(), E, d, float(minus_clr), float(eps), None if bf16_copy is None else bf16_copy.data_ptr(),
+            0 if bf16_copy is None else ld(bf16_copy), ctypes.byref(pen), _stream_handle(device)),
+            "kge_adagrad_step_touched_wpenalty")
+
+
+def sparse_adam_step_touched_wpenalty(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor,
+                                      exp_avg_sq: torch.Tensor, bitmap: torch.Tensor, clock: torch.Tensor, lr: float,
+                                      beta1: float, beta2: float, eps: float, pen,
+                                      bf16_copy: torch.Tensor = None) -> None:
+    """sparse_adam_step_touched with a weighted penalty term added to the marked rows' gradients in registers
+    (kge_sparse_adam_step_touched_wpenalty); `pen`: a wpenalty_seg record whose counts are cleared with the bitmap."""
+    device = param.device
+    if device.type != "cuda":
+        raise RuntimeError(f"kge_amd: sparse_adam_step_touched_wpenalty steps on a GPU, not on '{device}' (no CPU path)")
+    E, d = param.shape
+    _touched_tables_ok("sparse_adam_step_touched_wpenalty", device, E, d,
+                       ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")), bf16_copy)
+    if not (torch.is_tensor(clock) and clock.device == device and clock.dtype == torch.int64 and clock.numel() == 4
+            and clock.is_contiguous()):
+        raise ValueError(f"kge_amd: sparse_adam_step_touched_wpenalty: the clock record is a contiguous int64 [4] on "
+                         f"{device}")
+    _bitmap_ok(bitmap, E, device, "sparse_adam_step_touched_wpenalty")
+    ld = lambda t: t.stride(0) if E > 1 else max(d, 1)
+    with _on_device(device):
+        _lib.check(_lib.lib().kge_sparse_adam_step_touched_wpenalty(
+            param.data_ptr(), ld(param), grad.data_ptr(), ld(grad), exp_avg.data_ptr(), ld(exp_avg),
+            exp_avg_sq.data_ptr(), ld(exp_avg_sq), bitmap.data_ptr(), E, d, clock.data_ptr(), float(lr), float(beta1),
+            float(beta2), float(eps), None if bf16_copy is None else bf16_copy.data_ptr(),
+            0 if bf16_copy is None else ld(bf16_copy), ctypes.byref(pen), _stream_handle(device)),
+            "kge_sparse_adam_step_touched_wpenalty")
+
+
 KVSALL_COLLATE_MAX_N = _lib.KVSALL_COLLATE_MAX_N
 
 

@@ -174,6 +174,35 @@ def _no_penalty(job, batch_index, batch) -> bool:
         return False
 
 
+def _fold_weighted_option(job) -> bool:
+    """`<train.type>.fold_weighted_penalties` of the hip_1vsAll and hip_negative_sampling jobs (hip_KvsAll has the key
+    too, but its captured step has no fixed `triples`: weighted terms stay eager there)."""
+    try:
+        kind = job.config.get("train.type")
+        if kind not in ("hip_1vsAll", "hip_negative_sampling"):
+            return False
+        return bool(job.config.get_default(f"{kind}.fold_weighted_penalties"))
+    except Exception:
+        return False
+
+
+def _count_weighted(job, triples):
+    """The count launches of the folded WEIGHTED terms, in front of the step that reads them (inside the GraphedStep's
+    function, so inside the capture, on its static `triples`): the relation embedder sees triples[:, P], the shared
+    entity embedder the S and the O column (kge_model.py:607-634), both with m = len(indexes) = n -- the [n, 2] block
+    the reference concatenates has len() n, so its 2n entries are divided by n (lookup_embedder.py:171).  Under
+    touched_rows the same launch marks the rows."""
+    for w, cols in getattr(job, "_weighted_penalties", None) or ():
+        for c in cols:
+            job.optimizer.count_penalty(w, triples[:, c], len(triples))
+
+
+def _set_weighted_m(job, n):
+    """What penalty_value divides by, for a step a replay takes (its count launches do not pass the host)."""
+    for w, _cols in getattr(job, "_weighted_penalties", ()):
+        job.optimizer.set_penalty_m(w, n)
+
+
 def _fold_penalties(job) -> bool:
     """The embedders' UNWEIGHTED Lp / N3 penalty terms (lookup_embedder.py:122-147 through KgeModel.penalty,
     kge_model.py:603-649) folded into the pass of an optimizer that offers the penalty interface -- HipAdagrad, or a
@@ -186,7 +215,12 @@ def _fold_penalties(job) -> bool:
     optimizer skips its folded ones for that step.
 
     -> True if every term of this model is folded (the job may capture its step), False if the model has no foldable
-    shape (weighted terms, other embedders, other regularizers, another optimizer): nothing is changed then."""
+    shape (weighted terms, other embedders, other regularizers, another optimizer): nothing is changed then.
+
+    `fold_weighted_penalties: true` (hip_1vsAll, hip_negative_sampling): WEIGHTED lp / n3 terms
+    (lookup_embedder.py:148-173) are planned too -- their gradient is a function of the element and its row's count in
+    the batch, which _count_weighted builds on the device in front of the step.  Declined: a
+    model whose subject and object embedders differ, a model that mixes weighted and unweighted terms."""
     from kge.model import KgeModel, LookupEmbedder
     from ..optim import Adagrad as HipAdagrad, Adam as HipAdam
     model, opt = job.model, job.optimizer
@@ -198,14 +232,23 @@ def _fold_penalties(job) -> bool:
     if not folds or type(model).penalty not in (KgeModel.penalty, _FusedScoring.penalty):
         return False
     pe, se, oe = model.get_p_embedder(), model.get_s_embedder(), model.get_o_embedder()
-    plan = []
+    plan, weighted = [], []
+    fold_weighted = _fold_weighted_option(job)
     for emb, times in ((pe, 1.0),) + (((se, 2.0),) if se is oe else ((se, 1.0), (oe, 1.0))):
         if type(emb).penalty is not LookupEmbedder.penalty:
             return False
         if emb.regularize == "" or emb.get_option("regularize_weight") == 0.0:
             continue
-        if emb.regularize not in ("lp", "n3") or emb.get_option("regularize_args.weighted"):
+        is_weighted = bool(emb.get_option("regularize_args.weighted"))
+        if emb.regularize not in ("lp", "n3") or (is_weighted and not fold_weighted):
             return False
+        if is_weighted:
+            if emb.regularize == "n3" and emb.space != "complex":
+                return False  # (the reference's weighted n3 on a real space is the SIGNED x ** 3: lookup_embedder.py:158)
+            if se is not oe:
+                return False  # (two entity embedders: each sees one column; not planned)
+            times = 1.0       # (the S and O indexes are one vector: kge_model.py:612-621)
+            weighted.append((emb._embeddings.weight, (P,) if emb is pe else (S, O)))
         if emb.regularize == "n3":
             p, kind = 3, ("n3_complex" if emb.space == "complex" else "lp")
         else:
@@ -223,9 +266,16 @@ def _fold_penalties(job) -> bool:
         plan.append((emb, w, kind, int(p), float(emb._get_regularize_weight()), times))
     if not plan:
         return False  # (nothing to fold: _no_penalty's own check decides)
+    if weighted and len(weighted) != len(plan):
+        return False  # (weighted and unweighted terms in one model: not planned)
+    is_w = {id(w) for w, _cols in weighted}
     for emb, w, kind, p, weight, times in plan:
-        opt.set_penalty(w, kind, p, weight, times)
+        if id(w) in is_w:
+            opt.set_penalty(w, kind, p, weight, times, weighted=True)
+        else:
+            opt.set_penalty(w, kind, p, weight, times)
     job._folded_penalties = plan
+    job._weighted_penalties = weighted
     reference_penalty = model.penalty
 
     def penalty(**kwargs):
@@ -319,10 +369,13 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
             if ok:
                 # the batch goes in as ONE tensor (one copy into the static buffer per replay, not three); the captured
                 # batches all have the size of the first (another size runs eagerly), so 1 / batch size is a constant
-                self._graph_step = _graphed_step_of(
-                    self, (lambda t: self.model.loss_sp_po_sum(t[:, 0], t[:, 1], t[:, 2], 1.0 / len(t)))
-                    if hasattr(self.model, "loss_sp_po_sum")
-                    else (lambda t: self.model.loss_sp_po(t[:, 0], t[:, 1], t[:, 2]).sum() / len(t)))
+                loss = ((lambda t: self.model.loss_sp_po_sum(t[:, 0], t[:, 1], t[:, 2], 1.0 / len(t)))
+                        if hasattr(self.model, "loss_sp_po_sum")
+                        else (lambda t: self.model.loss_sp_po(t[:, 0], t[:, 1], t[:, 2]).sum() / len(t)))
+                if getattr(self, "_weighted_penalties", None):  # (fold_weighted_penalties: the counts, then the step)
+                    plain = loss
+                    loss = lambda t: (_count_weighted(self, t), plain(t))[1]
+                self._graph_step = _graphed_step_of(self, loss)
         if not self._graph_step_ok:
             return None
         n = len(batch["triples"])
@@ -377,6 +430,7 @@ class HipTrainingJob1vsAll(_CudaOomText, TrainingJob1vsAll):
                 result.forward_time -= time.time()
                 # the batch as the loader made it (a host tensor): GraphedStep copies it host-to-device straight into the
                 # captured step's input buffer -- no device-side hop in front of the replay
+                _set_weighted_m(self, len(batch["triples"][subbatch_slice]))
                 loss_value = gs(batch["triples"][subbatch_slice])  # (whole batch: len(triples) == batch_size)
                 self._skip_optimizer_step = True  # (eager or replayed: the step is taken)
                 result.avg_loss += loss_value.item()
@@ -949,6 +1003,7 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         self.graph_batches = 0        # batches that went through the GraphedStep (replayed or eager)
         self._skip_optimizer_step = False
         self.touched_rows = None           # hip_negative_sampling.touched_rows: decided at the first batch
+        self._touched_weighted = False     # ... with a folded weighted term on the entity table (fold_weighted_penalties)
         self.touched_rows_declined = None  # why the dense path runs although the option is on
         if self.__class__ == HipTrainingJobNegativeSampling:
             for f in Job.job_created_hooks:
@@ -1059,6 +1114,7 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         negs, inv = args[:-1], args[-1]
         s, p, o = triples[:, S], triples[:, P], triples[:, O]
         n = triples.shape[0]
+        _count_weighted(self, triples)  # (fold_weighted_penalties: the counts -- and row marks -- the step reads)
         total = None
         by_slot = dict(zip(self._graph_slots, negs))
         blocks = None
@@ -1115,7 +1171,15 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         if type(emb) is not LookupEmbedder or emb.dropout.p > 0:
             return "the entity embedder is not a plain LookupEmbedder without dropout"
         if not (emb.regularize == "" or emb.get_option("regularize_weight") == 0.0):
-            return "regularize_weight > 0 on the entity embedder (a penalty term touches every row)"
+            # a WEIGHTED term touches the batch's rows only: with fold_weighted_penalties it rides in the row step --
+            # provided the step of EVERY batch is the GraphedStep's (whose function counts and marks the rows): the
+            # captured step was decided on (before this question is asked), and the batch is never cut into subbatches
+            planned = any(q is w for q, _cols in getattr(self, "_weighted_penalties", None) or ())
+            sub = self.config.get("train.subbatch_size")
+            whole = (sub < 1 or sub >= self.config.get("train.batch_size")) \
+                and not self.config.get("train.subbatch_auto_tune")
+            if not (isinstance(opt, HipAdagrad) and planned and self._graph_step_ok is True and whole):
+                return "regularize_weight > 0 on the entity embedder (a penalty term touches every row)"
         if isinstance(opt, HipSparseAdam):  # the relation table goes through a bitmap too: the same conditions
             rel = model.get_p_embedder()
             if not any(q is rel._embeddings.weight for g in opt.param_groups for q in g["params"]):
@@ -1164,17 +1228,22 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
         else:
             self.model.set_touched_rows(pair)
         self.touched_rows = True
+        w = self.model.get_s_embedder()._embeddings.weight
+        self._touched_weighted = any(q is w for q, _cols in getattr(self, "_weighted_penalties", None) or ())
 
     def _process_subbatch(self, batch_index, batch, subbatch_slice, result):
+        gs = self._graph_step_for(batch_index, batch, subbatch_slice)  # (decided first: touched_rows asks about it)
         if self.touched_rows is None:
             self._decide_touched_rows(batch)
-        gs = self._graph_step_for(batch_index, batch, subbatch_slice)
-        if gs is not None and gs.enabled:
+        # (a weighted term on the touched-row step is counted and marked by the GraphedStep's function alone: if the
+        # capture failed and the GraphedStep switched itself off, its eager form still takes the step)
+        if gs is not None and (gs.enabled or self._touched_weighted):
             batch_size = result.size
             result.prepare_time -= time.time()
             triples = batch["triples"]
             negs = [batch["negative_samples"][slot].samples() for slot in self._graph_slots]
             inv = torch.full((), 1.0 / batch_size, device=triples.device)
+            _set_weighted_m(self, len(triples))
             result.prepare_time += time.time()
             result.forward_time -= time.time()
             loss_value = gs(triples, *negs, inv)

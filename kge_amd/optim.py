@@ -42,18 +42,27 @@ class _FoldedPenalties:
         self._pen_acc = {}         # device -> float64 accumulators, one per parameter with a penalty
         self._pen_slot = {}        # parameter -> index into its device's accumulators
         self._pen_off_once = False
+        self._wpen = {}            # parameter with a WEIGHTED term -> [count buffer [V] (zero between steps), m]
 
-    def set_penalty(self, param, kind: str, p: int, weight: float, times: float = 1.0):
+    def set_penalty(self, param, kind: str, p: int, weight: float, times: float = 1.0, weighted: bool = False):
         """From now on every step() adds to `param`'s gradient the gradient of
             times * weight / p * sum |x|^p                      kind "lp", p in (1, 2, 3)
             times * weight / 3 * sum |z|^3 over complex coordinates   kind "n3_complex" (z = row[c] + i row[c + dim / 2])
         (LookupEmbedder.penalty unweighted, lookup_embedder.py:122-147; `times` = 2 for an entity embedder that serves the
         subject and the object slot, kge_model.py:620-625) inside the update's own pass, and `penalty_value(param)`
         holds the term's value at the parameters the step started from.  The caller must then NOT back-propagate the
-        term itself.  kind None removes it."""
+        term itself.  kind None removes it.
+
+        weighted=True: the frequency-weighted form (lookup_embedder.py:148-173),
+            weight / p / m * sum_r c_r * sum_j |x_rj|^p,  c_r = the occurrences of row r among the batch's m indexes.
+        The parameter then owns a zero [rows] count buffer; before every step() the caller counts the batch's indexes
+        into it with `count_penalty(param, ids, m)`, and step() leaves it zero again.  `times` must be 1: a shared
+        entity embedder gets the subject and object indexes as one [n, 2] tensor (kge_model.py:612-621) whose 2n
+        entries are counted and whose len(), n, is the m the reference divides by (lookup_embedder.py:171)."""
         name = f"kge_amd.optim.{type(self).__name__}"
         if kind is None:
             self._penalties.pop(param, None)
+            self._wpen.pop(param, None)
         else:
             if kind not in ("lp", "n3_complex") or (kind == "lp" and p not in (1, 2, 3)):
                 raise ValueError(f"{name}: no fused form of penalty {kind} p={p}")
@@ -63,6 +72,15 @@ class _FoldedPenalties:
                 p = 3
                 if param.dim() != 2 or param.shape[1] % 8 != 0:
                     raise ValueError(f"{name}: n3_complex needs a [*, dim] table with dim % 8 == 0")
+            if weighted:
+                if param.dim() != 2:
+                    raise ValueError(f"{name}: a weighted penalty needs a [rows, dim] table")
+                if float(times) != 1.0:
+                    raise ValueError(f"{name}: a weighted penalty is not doubled (count both slots' indexes instead)")
+                if param not in self._wpen or self._wpen[param][0].numel() < param.shape[0]:
+                    self._wpen[param] = [engine.penalty_counts(param.shape[0], param.device), 0]
+            else:
+                self._wpen.pop(param, None)
             self._penalties[param] = (1 if kind == "lp" else 2, int(p), float(times) * float(weight),
                                       int(param.shape[-1]), float(times) * float(weight) / float(p))
         self._pen_acc, self._pen_slot = {}, {}
@@ -75,25 +93,78 @@ class _FoldedPenalties:
         return bool(self._penalties)
 
     def skip_penalties_once(self):
-        """The next step() is the plain update (the caller back-propagated the terms itself for that batch)."""
+        """The next step() is the plain update (the caller back-propagated the terms itself for that batch); the count
+        buffers of weighted terms are zeroed by it all the same."""
         self._pen_off_once = True
+
+    def is_weighted(self, param) -> bool:
+        return param in self._wpen
+
+    def penalty_counts(self, param) -> torch.Tensor:
+        """The [rows] int32 count buffer of a weighted term (zero between steps)."""
+        return self._wpen[param][0]
+
+    def count_penalty(self, param, ids: torch.Tensor, m: int):
+        """Counts `ids` (an index vector or [n, k] block, any stride: engine.penalty_count) into the weighted term's
+        buffer for the next step().  `m` is len(indexes) as the reference's term divides by it: the same in every call
+        of one step (the subject and the object column of a batch of n triples are two calls, BOTH with m = n: the
+        reference passes them as one [n, 2] tensor, whose len() is n).  A parameter on the touched-row step has the
+        rows marked too, and a SparseAdam pair is set `pending`: the next step() visits the rows and clears the counts
+        whether or not a backward ran."""
+        rec = self._wpen[param]
+        if not 0 < int(m) < engine.WPENALTY_MAX_M:
+            raise ValueError(f"kge_amd.optim.{type(self).__name__}: a weighted penalty needs 0 < m < 2^24 indexes")
+        rec[1] = int(m)
+        pair = getattr(self, "_touched", {}).get(param)
+        engine.penalty_count(ids, rec[0], param.shape[0], None if pair is None else pair[1])
+        if isinstance(pair, _TouchedRows):
+            pair.pending = True
+
+    def set_penalty_m(self, param, m: int):
+        """The length of the index vector of the step about to be REPLAYED (its captured count launches do not pass
+        the host): what penalty_value divides by."""
+        self._wpen[param][1] = int(m)
 
     def penalty_value(self, param) -> torch.Tensor:
         """0-d float32 device tensor: the term's value the LAST step() saw (pre-step parameters)."""
         spec = self._penalties[param]
-        return (self._pen_acc[param.device][self._pen_slot[param]] * spec[4]).to(torch.float32)
+        factor = spec[4] / self._wpen[param][1] if param in self._wpen else spec[4]
+        return (self._pen_acc[param.device][self._pen_slot[param]] * factor).to(torch.float32)
 
-    def _fold_this_step(self) -> bool:
-        """Whether this step() carries the terms; if so their accumulators are cleared.  Ends a skip_penalties_once."""
+    def _begin_fold(self) -> bool:
+        """Whether this step() carries the terms; if so their accumulators are cleared, if not the count buffers of
+        the weighted ones are (a skipped step must leave them zero as well)."""
         fold = bool(self._penalties) and not self._pen_off_once
-        self._pen_off_once = False
         if fold:
             for acc in self._pen_acc.values():
                 acc.zero_()  # (a fill kernel: captured with the step)
+        else:
+            for rec in self._wpen.values():
+                rec[0].zero_()
         return fold
+
+    def _fold_this_step(self) -> bool:
+        """_begin_fold, and ends a skip_penalties_once."""
+        fold = self._begin_fold()
+        self._pen_off_once = False
+        return fold
+
+    def _wpenalty_seg(self, q):
+        """The kge_wpenalty_seg record of parameter `q` (kind 0 if it has no weighted term)."""
+        rec = self._wpen.get(q)
+        if rec is None:
+            return engine.wpenalty_seg(0, 0, 0.0, 0, None, None, 0)
+        if rec[1] <= 0:
+            raise RuntimeError(f"kge_amd.optim.{type(self).__name__}: a weighted penalty was never counted "
+                               "(count_penalty before step())")
+        spec = self._penalties[q]
+        return engine.wpenalty_seg(spec[0], spec[1], spec[2], spec[3],
+                                   self._pen_acc[q.device].data_ptr() + 8 * self._pen_slot[q], rec[0], rec[1])
 
     def _penalty_segs(self, params, device):
         """The kge_penalty_seg array of one launch over `params`, or None if none of them has a term."""
+        if any(q in self._wpen for q in params):
+            raise RuntimeError("kge_amd.optim: a weighted term in an unweighted penalty launch")
         if not any(q in self._penalties for q in params):
             return None
         pens = []
@@ -166,11 +237,11 @@ class Adagrad(_FoldedPenalties, _TorchAdagrad):
         touched-row parameters, whose gradient never reaches `.grad`)."""
         return list(self._stepped)
 
-    def _step_touched(self, p, group):
+    def _step_touched(self, p, group, fold=False):
         if p.grad is not None:
             raise RuntimeError("kge_amd.optim.Adagrad: a dense gradient reached a parameter switched to the touched-row "
                                "step (a backward route that does not know its gradient buffer)")
-        if p in self._penalties:
+        if p in self._penalties and p not in self._wpen:
             raise RuntimeError("kge_amd.optim.Adagrad: a fused penalty on a parameter switched to the touched-row step "
                                "(an unweighted term touches every row)")
         if group["weight_decay"] != 0:
@@ -191,7 +262,11 @@ class Adagrad(_FoldedPenalties, _TorchAdagrad):
                     copy.copy_(p.detach())
                 else:
                     copy = p.detach().to(torch.bfloat16)
-        engine.adagrad_step_touched(p.detach(), grad, state["sum"], bitmap, minus_clr, float(group["eps"]), copy)
+        if fold and p in self._wpen:
+            engine.adagrad_step_touched_wpenalty(p.detach(), grad, state["sum"], bitmap, minus_clr, float(group["eps"]),
+                                                 self._wpenalty_seg(p), copy)
+        else:
+            engine.adagrad_step_touched(p.detach(), grad, state["sum"], bitmap, minus_clr, float(group["eps"]), copy)
         torch.autograd.graph.increment_version(p)
         if copy is not None:
             setattr(p, BF16_ATTR, (copy, p._version, p.data_ptr()))
@@ -258,13 +333,15 @@ class Adagrad(_FoldedPenalties, _TorchAdagrad):
                 loss = closure()
         dense = {}  # device -> [(p, copy, segment)]: every dense table of a device in ONE launch (kge_adagrad_step_multi)
         stepped = self._stepped = []
+        # (with a weighted term on a touched-row parameter the accumulators must be clear before the first launch)
+        fold_touched = self._begin_fold() if self._wpen and self._touched else False
         for group in self.param_groups:
             if group.get("maximize") or group.get("differentiable"):
                 raise NotImplementedError("kge_amd.optim.Adagrad: maximize / differentiable are not supported")
             rest = []
             for p in group["params"]:
                 if self._touched and p in self._touched:
-                    self._step_touched(p, group)
+                    self._step_touched(p, group, fold_touched)
                     stepped.append(p)
                     continue
                 if p.grad is None:
@@ -299,11 +376,26 @@ class Adagrad(_FoldedPenalties, _TorchAdagrad):
                 _functional_adagrad(rest, grads, sums, steps, has_sparse_grad=any(g.is_sparse for g in grads),
                                     foreach=False, lr=group["lr"], weight_decay=group["weight_decay"],
                                     lr_decay=group["lr_decay"], eps=group["eps"], maximize=False)
-        with_pen = self._fold_this_step()
+        if self._wpen and self._touched:
+            with_pen, self._pen_off_once = fold_touched, False
+        else:
+            with_pen = self._fold_this_step()
         for device, items in dense.items():
             with torch.cuda.device(device):
-                for i in range(0, len(items), _lib.ADAGRAD_MAX_SEGS):
-                    chunk = items[i:i + _lib.ADAGRAD_MAX_SEGS]
+                if with_pen and self._wpen:  # the tables with a weighted term: launches of their own
+                    heavy = [c for c in items if c[0] in self._wpen]
+                    for i in range(0, len(heavy), _lib.ADAGRAD_MAX_SEGS):
+                        chunk = heavy[i:i + _lib.ADAGRAD_MAX_SEGS]
+                        segs = (_lib.KgeAdagradSeg * len(chunk))(*(c[2] for c in chunk))
+                        pens = (_lib.KgeWPenaltySeg * len(chunk))(*(self._wpenalty_seg(c[0]) for c in chunk))
+                        _lib.check(_lib.lib().kge_adagrad_step_multi_wpenalty(segs, pens, len(chunk),
+                                                                              engine._stream(device)),
+                                   "kge_adagrad_step_multi_wpenalty")
+                    items_here = [c for c in items if c[0] not in self._wpen]
+                else:
+                    items_here = items
+                for i in range(0, len(items_here), _lib.ADAGRAD_MAX_SEGS):
+                    chunk = items_here[i:i + _lib.ADAGRAD_MAX_SEGS]
                     segs = (_lib.KgeAdagradSeg * len(chunk))(*(c[2] for c in chunk))
                     pens = self._penalty_segs([c[0] for c in chunk], device) if with_pen else None
                     if pens is not None:
@@ -355,10 +447,10 @@ class Adam(_FoldedPenalties, torch.optim.Adam):
         if self.device_step:
             self.graph_capturable = True
 
-    def set_penalty(self, param, kind, p, weight, times=1.0):
+    def set_penalty(self, param, kind, p, weight, times=1.0, weighted=False):
         if not self.device_step:
             raise ValueError("kge_amd.optim.Adam: fused penalties need device_step=True (kge_adam_step_multi)")
-        super().set_penalty(param, kind, p, weight, times)
+        super().set_penalty(param, kind, p, weight, times, weighted)
 
     def after_graph_replay(self, params):
         """`params`: the parameters the captured step() updated.  The replayed clock kernel advanced their device
@@ -432,8 +524,20 @@ class Adam(_FoldedPenalties, torch.optim.Adam):
         with_pen = self._fold_this_step()
         for device, items in dense.items():
             with torch.cuda.device(device):
-                for i in range(0, len(items), _lib.ADAM_MAX_SEGS):
-                    chunk = items[i:i + _lib.ADAM_MAX_SEGS]
+                if with_pen and self._wpen:  # the tables with a weighted term: launches of their own
+                    heavy = [c for c in items if c[0] in self._wpen]
+                    for i in range(0, len(heavy), _lib.ADAM_MAX_SEGS):
+                        chunk = heavy[i:i + _lib.ADAM_MAX_SEGS]
+                        segs = (_lib.KgeAdamSeg * len(chunk))(*(c[2] for c in chunk))
+                        pens = (_lib.KgeWPenaltySeg * len(chunk))(*(self._wpenalty_seg(c[0]) for c in chunk))
+                        _lib.check(_lib.lib().kge_adam_step_multi_wpenalty(segs, pens, len(chunk),
+                                                                           engine._stream(device)),
+                                   "kge_adam_step_multi_wpenalty")
+                    items_here = [c for c in items if c[0] not in self._wpen]
+                else:
+                    items_here = items
+                for i in range(0, len(items_here), _lib.ADAM_MAX_SEGS):
+                    chunk = items_here[i:i + _lib.ADAM_MAX_SEGS]
                     segs = (_lib.KgeAdamSeg * len(chunk))(*(c[2] for c in chunk))
                     pens = self._penalty_segs([c[0] for c in chunk], device) if with_pen else None
                     _lib.check(_lib.lib().kge_adam_step_multi(segs, pens, len(chunk), engine._stream(device)),
@@ -513,7 +617,7 @@ class _TouchedRows(tuple):
     pending = False
 
 
-class SparseAdam(torch.optim.SparseAdam):
+class SparseAdam(_FoldedPenalties, torch.optim.SparseAdam):
     """torch.optim.SparseAdam (same constructor arguments and `state_dict`: "step", "exp_avg", "exp_avg_sq"; a
     checkpoint of either class loads into the other) for tables whose backward marks the rows it touched
     (`enable_touched_rows`, as kge_amd.optim.Adagrad): kge_sparse_adam_step_touched applies torch's row-wise update to
@@ -534,6 +638,19 @@ class SparseAdam(torch.optim.SparseAdam):
         self.bf16_copies = bool(bf16_copies)
         self._touched = {}   # parameter -> _TouchedRows(persistent dense gradient [rows, d], bitmap)
         self._stepped = []   # the parameters the last step() updated: stepped_params
+        self._init_penalties()
+
+    def set_penalty(self, param, kind, p, weight, times=1.0, weighted=False):
+        """A WEIGHTED penalty term on a touched-row parameter inside the row update (kge_amd.optim.Adagrad.set_penalty
+        describes the arguments; kge_sparse_adam_step_touched_wpenalty).  An unweighted term touches every row:
+        SparseAdam has no step for it."""
+        if kind is not None and not weighted:
+            raise ValueError("kge_amd.optim.SparseAdam: an unweighted penalty touches every row; only weighted=True "
+                             "has a kernel")
+        if kind is not None and param not in self._touched:
+            raise ValueError("kge_amd.optim.SparseAdam: fused penalties are for touched-row parameters "
+                             "(enable_touched_rows first)")
+        super().set_penalty(param, kind, p, weight, times, weighted)
 
     def enable_touched_rows(self, param):
         """From now on `param` -- a 2-D contiguous float32 GPU table -- is stepped on the rows its backward MARKED:
@@ -585,7 +702,7 @@ class SparseAdam(torch.optim.SparseAdam):
         for st in self.state.values():
             st.pop("clock", None)  # seeded again from the restored state["step"] by the next step()
 
-    def _step_touched(self, p, group):
+    def _step_touched(self, p, group, fold=False):
         name = "kge_amd.optim.SparseAdam"
         if p.grad is not None:
             raise RuntimeError(f"{name}: a gradient reached `.grad` of a parameter switched to the touched-row step (a "
@@ -626,8 +743,13 @@ class SparseAdam(torch.optim.SparseAdam):
                     copy.copy_(p.detach())
                 else:
                     copy = p.detach().to(torch.bfloat16)
-        engine.sparse_adam_step_touched(p.detach(), grad, state["exp_avg"], state["exp_avg_sq"], bitmap, clock,
-                                        float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), copy)
+        if fold and p in self._wpen:
+            engine.sparse_adam_step_touched_wpenalty(p.detach(), grad, state["exp_avg"], state["exp_avg_sq"], bitmap,
+                                                     clock, float(group["lr"]), float(beta1), float(beta2),
+                                                     float(group["eps"]), self._wpenalty_seg(p), copy)
+        else:
+            engine.sparse_adam_step_touched(p.detach(), grad, state["exp_avg"], state["exp_avg_sq"], bitmap, clock,
+                                            float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), copy)
         torch.autograd.graph.increment_version(p)
         if copy is not None:
             setattr(p, BF16_ATTR, (copy, p._version, p.data_ptr()))
@@ -650,9 +772,10 @@ class SparseAdam(torch.optim.SparseAdam):
                 self._step_touched(p, None)  # raises: a gradient in `.grad`
         torch.optim.SparseAdam.step(self)
         if self._touched:
+            fold = self._fold_this_step() if self._penalties else False
             for group in self.param_groups:
                 for p in group["params"]:
-                    if p in self._touched and self._step_touched(p, group):
+                    if p in self._touched and self._step_touched(p, group, fold):
                         stepped.append(p)
         self._stepped = stepped
         return loss
