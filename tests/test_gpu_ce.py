@@ -70,6 +70,9 @@ CASES = [
 
 @pytest.mark.parametrize("model,d,E,R,n,scale", CASES)
 def test_ce_fwd(eng, model, d, E, R, n, scale):
+    """Tolerances on random, near-uniform rows (module docstring).  The elementwise claim -- lse and loss_rows inside a
+    bound counted from the epilogues, on rows whose max rises late, spikes, ties and |score| >= 100 -- is asserted in
+    tests/test_gpu_ce16_bound.py."""
     ent, rel, s, p, o = _case(d + n, model, d, E, R, n, scale)
     T = _tables(eng, model, ent, rel)
     O = ko.Tables(model, ko.f32_to_bf16(ent), ko.f32_to_bf16(rel), 1.0)
@@ -130,8 +133,9 @@ def _grads64(model, ent16, rel16, a, p, lab, direction, g):
 @pytest.mark.parametrize("model,d,E,R,n,scale", CASES[:2] + CASES[4:5] + CASES[6:8])
 def test_ce_bwd(eng, model, d, E, R, n, scale):
     """kge_ce_bwd against float64 autograd (norm-wise) and against the unfused mixed-precision backward,
-    score_pairs_bwd on bf16 tables -- a yardstick that is itself asserted elementwise against float64, inside a derived
-    bound, in tests/test_gpu_pairs_bwd16.py."""
+    score_pairs_bwd on bf16 tables.  Both are coarse: the ELEMENTWISE claim -- G16 as the V3_DS epilogues write it (not
+    the cast of a given gout that tests/test_gpu_pairs_bwd16.py feeds) and the three gradients, against float64 inside a
+    derived bound on planted inputs -- is asserted in tests/test_gpu_ce16_bound.py."""
     ent, rel, s, p, o = _case(3 * d + n, model, d, E, R, n, scale)
     T = _tables(eng, model, ent, rel)
     rng = np.random.default_rng(1)
