@@ -134,6 +134,9 @@ typedef enum kge_flags {
  * fragments instead of building them again (one launch less per step).  Without the promise kept the backward reads
  * stale fragments: set it on BOTH calls or on neither. */
 #define KGE_FLAG_CE_KEEP_QUERIES (1 << 16)
+/* The relation-grouped RESCAL entries only ("RESCAL, relation-grouped" below): the tables opt in to that route.  Without
+ * the bit those entries answer KGE_ERR_UNSUPPORTED for a RESCAL table like every entry outside the RESCAL list. */
+#define KGE_FLAG_RESCAL_GROUPED (1 << 17)
 #define KGE_FLAG_RESERVE_CUS_SHIFT 8
 #define KGE_FLAG_RESERVE_CUS(n) (((n) & 255) << KGE_FLAG_RESERVE_CUS_SHIFT)
 
@@ -191,7 +194,8 @@ typedef struct kge_index {
  * Entry points that take KGE_RESCAL: kge_score_spo, kge_score_sp, kge_score_po, kge_score_sp_po, kge_score_neg,
  * kge_score_pairs_bwd (no float atomics: two runs give the same bits; g_p is [n, dim * dim]), kge_score_spo_bwd,
  * kge_score_spo_bwd_accum, kge_score_neg_bwd_accum (grad_rel is [num_rel, dim * dim]; float atomics), and
- * kge_rescal_queries.  `scores` of the backward entries is not read and may be NULL.  Every other entry point that
+ * kge_rescal_queries, and the relation-grouped entries ("RESCAL, relation-grouped" below).  `scores` of the backward
+ * entries is not read and may be NULL.  Every other entry point that
  * takes kge_tables returns KGE_ERR_UNSUPPORTED for a RESCAL table and launches nothing (its *_bytes query returns 0). */
 #define KGE_RESCAL_MAX_DIM 256
 
@@ -350,6 +354,64 @@ int64_t kge_score_workspace_bytes(const kge_tables* t, int64_t n);
 int64_t kge_rescal_queries_bytes(const kge_tables* t, int64_t n);
 int kge_rescal_queries(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, float* q, int64_t q_ld,
                        void* stream);
+
+/* ---- RESCAL, relation-grouped (csrc/rescal_grouped.hip, csrc/rescal_grouped_device.hpp) -----------------------------
+ * An opt-in second route beside the entries above, which stay as they are.  The rows of a batch that share a relation
+ * are brought together and the d^2 work of a relation runs as matrix products on the f32 matrix cores
+ * (v_mfma_f32_16x16x4_f32, tiles of 16 rows of one relation): M_p is read once per row tile instead of once per row,
+ * and the relation gradient has ONE owner per output tile -- no float atomics into grad_rel, the same bits on every run.
+ * Gate (before any launch; the *_bytes query answers 0): every scorer but KGE_RESCAL, bf16 tables,
+ * dim > KGE_RESCAL_MAX_DIM, tables whose flags lack KGE_FLAG_RESCAL_GROUPED (the opt-in: a plain RESCAL table is
+ * declined here as by every entry outside the RESCAL list), n > KGE_RESCAL_GROUPED_MAX_N or num_rel >= 2^31:
+ * KGE_ERR_UNSUPPORTED.  Every dim >= 1 works
+ * (padded in LDS, never in the tables).  Invalid arguments are reported by the rules of the ungrouped entries.
+ * Workspace: kge_rescal_grouped_workspace_bytes(t, n) bytes, 16-byte aligned, one size for the three entries; the
+ * library allocates nothing and nothing in it needs zeroing; NULL or too small with work to do: KGE_ERR_WORKSPACE;
+ * n == 0: KGE_OK, nothing touched.  No entry waits for the host (capturable).  Sections, each on a 16-byte boundary,
+ * with a16(x) = x rounded up to 16:
+ *   +0                               int32 perm[n]
+ *   +a16(4 n)                        int32 group_rel[n]        (the first G are written)
+ *   +2 a16(4 n)                      int32 group_begin[n + 1]  (the first G + 1 are written)
+ *   +2 a16(4 n) + a16(4 (n + 1))     int32 G, then three private words
+ *   behind them                      private: the counting arrays, Q [n, dim] and g_Q [n, dim]
+ *
+ * kge_rescal_group: perm = the batch positions in ascending relation id p[i], positions ASCENDING inside a relation (a
+ * stable order: kge_neg_order promises "any order among equal ids" and is not used); G = the number of distinct
+ * relations; group g is relation group_rel[g] (ascending) and the positions perm[group_begin[g] .. group_begin[g + 1]).
+ * By counting (every position counts the keys below it and the equal keys in front of it: n^2 comparisons, no atomics).
+ *
+ * kge_rescal_queries_grouped: kge_rescal_queries -- the same dense q [n, dim] in BATCH order, both directions (replaces
+ * the bmm of rescal.py:28-31 / 37-40 / 45-46) -- with another rounding of the same real number: ONE chain per element,
+ *   acc = +0;  for k0 = 0, 4, 8, ... < dim rounded up to 4:  acc = mfma_16x16x4(x[k0 .. k0 + 3], M[k0 .. k0 + 3], acc)
+ * -- one v_mfma_f32_16x16x4_f32 per four k, issued in ascending k; the instruction adds the four products of its
+ * k0 .. k0 + 3 to the accumulator in the hardware's order, the same for every row and launch; coordinates >= dim are
+ * +0 on both sides (sp_: M[k] = M[k][b], _po: M[k] = M[a][k]).  NOT the REDUCE8
+ * chain of kge_rescal_queries: not bit-equal to it, inside the same float64 bound.  A query row is a pure function of
+ * its entity row and its matrix -- it meets the other rows of its tile only as the M index of the MFMA --: the same
+ * bits whatever n, its batch position, the rows that share its group, the index type or stride, the table pitches and
+ * the launch.
+ *
+ * kge_score_neg_bwd_accum_grouped: kge_score_neg_bwd_accum (sampler.py:263-306 backward; lookup_embedder.py:96-105) for
+ * a KGE_RESCAL table, slots 0 and 2 (anything else: KGE_ERR_INVALID_ARG, as there); `scores` is not read.  Grouping, the
+ * grouped build of Q, then per positive g_q = sum_k gout[i, k] x_neg[i, k] (fma chains in registers, a fixed order) as a
+ * dense row and gout[i, k] q_i into grad_ent[neg[i, k]] by float atomics; per relation group
+ * g_M_p = S_p^T Gq_p (slot 2) / Gq_p^T O_p (slot 0) over the group's rows in perm order, zero-padded to the
+ * instruction's K = 4, one chain from +0, and ONE plain load-add-store per element of grad_rel[p]; the fixed rows'
+ * g_S_p = Gq_p M_p^T / g_O_p = Gq_p M_p by the build kernel, added to grad_ent by float atomics (an entity can sit in
+ * several groups).  grad_rel: the same bits on every run, and under a permutation of the batch that keeps every
+ * relation's rows in their relative order.  kge_score_spo_bwd_accum is this entry with slot 2 and neg = o seen as
+ * [n, 1] (neg_ld = o's stride, gout's pitch 1). */
+#define KGE_RESCAL_GROUPED_MAX_N 65536
+int64_t kge_rescal_grouped_workspace_bytes(const kge_tables* t, int64_t n);
+int kge_rescal_group(const kge_tables* t, kge_index p, int64_t n, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int kge_rescal_queries_grouped(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, float* q, int64_t q_ld,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int kge_score_neg_bwd_accum_grouped(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                                    const void* neg, int32_t neg_itype, int64_t neg_ld, int64_t num_neg,
+                                    const float* gout, int64_t ldg, const float* scores, int64_t lds, float* grad_ent,
+                                    int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
 
 /* out[i] = score(s[i], p[i], o[i]), i < n.        KgeModel.score_spo */
 int kge_score_spo(const kge_tables* t, kge_index s, kge_index p, kge_index o,

@@ -25,6 +25,7 @@ I32, I64 = 0, 1
 SPO, SP_, PO_ = 0, 1, 2
 FLAG_EXACT, FLAG_NO_MFMA, FLAG_BF16_V3 = 1, 2, 16
 FLAG_SPLIT_QUERY = 32
+FLAG_RESCAL_GROUPED = 1 << 17  # KGE_FLAG_RESCAL_GROUPED: the tables opt in to the relation-grouped RESCAL entries
 SP_PO = 3
 
 c_i64 = ctypes.c_int64
@@ -117,6 +118,7 @@ class KgeKvsallTyped(ctypes.Structure):
 KVSALL_COLLATE_MAX_N = 1 << 20  # KGE_KVSALL_COLLATE_MAX_N
 TOPK_MAX = 128  # KGE_TOPK_MAX
 RESCAL_MAX_DIM = 256  # KGE_RESCAL_MAX_DIM
+RESCAL_GROUPED_MAX_N = 65536  # KGE_RESCAL_GROUPED_MAX_N
 TUCKER3_MAX_BASE_DIM = 1024  # KGE_TUCKER3_MAX_BASE_DIM
 
 
@@ -156,6 +158,13 @@ PROTOTYPES = {
     "kge_score_sp_po": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_rescal_queries_bytes": (c_i64, [_PT, c_i64]),
     "kge_rescal_queries": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
+    "kge_rescal_grouped_workspace_bytes": (c_i64, [_PT, c_i64]),
+    "kge_rescal_group": (ctypes.c_int, [_PT, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
+    "kge_rescal_queries_grouped": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                                  c_vp]),
+    "kge_score_neg_bwd_accum_grouped": (ctypes.c_int, [_PT, KgeIndex, KgeIndex, KgeIndex, c_i64, ctypes.c_int, c_vp,
+                                                       ctypes.c_int32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                                       c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "kge_tucker3_project_bytes": (c_i64, [ctypes.POINTER(KgeTucker3), c_i64]),
     "kge_tucker3_project": (ctypes.c_int, [ctypes.POINTER(KgeTucker3), KgeIndex, c_i64, c_vp, c_i64, c_vp]),
     "kge_tucker3_project_bwd_workspace_bytes": (c_i64, [ctypes.POINTER(KgeTucker3), c_i64]),

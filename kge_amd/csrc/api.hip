@@ -50,6 +50,15 @@ int run_rescal_spo_bwd(const Operand& S, const Operand& R, const Operand& O, int
 int run_rescal_neg_bwd_accum(const Operand& S, const Operand& R, const Operand& O, int d, long long n, int slot,
                              const void* neg, int neg_itype, long long neg_ld, long long K, const float* gout,
                              long long ldg, float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st);
+// rescal_grouped.hip
+long long rescal_grouped_workspace_bytes(int d, long long n);
+int run_rescal_group_ws(const Index& P, long long n, int d, void* ws, hipStream_t st);
+int run_rescal_queries_grouped(const Operand& A, const Operand& R, int dir, int d, long long n, long long num_rel,
+                               float* q, long long q_ld, void* ws, hipStream_t st);
+int run_rescal_neg_bwd_accum_grouped(const Operand& S, const Operand& R, const Operand& O, int d, long long n,
+                                     long long num_rel, int slot, const void* neg, int neg_itype, long long neg_ld,
+                                     long long K, const float* gout, long long ldg, float* ge, long long ge_ld, float* gr,
+                                     long long gr_ld, void* ws, hipStream_t st);
 // transh.hip
 int run_transh_pairs(const Operand& A, const Operand& R, const Operand& TG, int dir, int d, long long n, long long m,
                      float lp, float* out, long long ldo, hipStream_t st);
@@ -752,6 +761,70 @@ int kge_rescal_queries(const kge_tables* t, int dir, kge_index a, kge_index p, i
   if ((rc = check_index(a, false)) || (rc = check_index(p, false))) return rc;
   return run_rescal_queries(ent_op(t, a), nullptr, rel_op(t, p), dir, (int)t->dim, n, q, nullptr, q_ld, nullptr,
                             (hipStream_t)stream);
+}
+
+// ---- RESCAL, relation-grouped (rescal_grouped.hip) ----------------------------------------------------------------------
+// the gate of the grouped entries behind check_tables: what only they decline
+static int rescal_grouped_gate(const kge_tables* t, int64_t n) {
+  if (t->scorer != KGE_RESCAL || !(t->flags & KGE_FLAG_RESCAL_GROUPED)) return KGE_ERR_UNSUPPORTED;
+  if (n > KGE_RESCAL_GROUPED_MAX_N || t->num_rel >= (1LL << 31)) return KGE_ERR_UNSUPPORTED;
+  return KGE_OK;
+}
+
+int64_t kge_rescal_grouped_workspace_bytes(const kge_tables* t, int64_t n) {
+  if (!t || n <= 0 || check_tables(t, false, false, /*rescal_ok=*/true) != KGE_OK || rescal_grouped_gate(t, n) != KGE_OK)
+    return 0;
+  return rescal_grouped_workspace_bytes((int)t->dim, n);
+}
+
+int kge_rescal_group(const kge_tables* t, kge_index p, int64_t n, void* workspace, int64_t workspace_bytes,
+                     void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true, false, /*rescal_ok=*/true);
+  if (rc) return rc;
+  if ((rc = rescal_grouped_gate(t, n))) return rc;
+  if (n < 0) return KGE_ERR_INVALID_ARG;
+  if (n == 0) return KGE_OK;
+  if ((rc = check_index(p, false))) return rc;
+  if (!workspace || workspace_bytes < rescal_grouped_workspace_bytes((int)t->dim, n)) return KGE_ERR_WORKSPACE;
+  return run_rescal_group_ws(make_index(p), n, (int)t->dim, workspace, (hipStream_t)stream);
+}
+
+int kge_rescal_queries_grouped(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, float* q, int64_t q_ld,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true, false, /*rescal_ok=*/true);
+  if (rc) return rc;
+  if ((rc = rescal_grouped_gate(t, n))) return rc;
+  if (dir != KGE_SP_ && dir != KGE_PO_) return KGE_ERR_INVALID_ARG;
+  if (n < 0 || (n > 0 && !q) || q_ld < t->dim) return KGE_ERR_INVALID_ARG;
+  if (n == 0) return KGE_OK;
+  if ((rc = check_index(a, false)) || (rc = check_index(p, false))) return rc;
+  if (!workspace || workspace_bytes < rescal_grouped_workspace_bytes((int)t->dim, n)) return KGE_ERR_WORKSPACE;
+  return run_rescal_queries_grouped(ent_op(t, a), rel_op(t, p), dir, (int)t->dim, n, t->num_rel, q, q_ld, workspace,
+                                    (hipStream_t)stream);
+}
+
+int kge_score_neg_bwd_accum_grouped(const kge_tables* t, kge_index s, kge_index p, kge_index o, int64_t n, int slot,
+                                    const void* neg, int32_t neg_itype, int64_t neg_ld, int64_t num_neg,
+                                    const float* gout, int64_t ldg, const float* scores, int64_t lds, float* grad_ent,
+                                    int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  KGE_RANGE();
+  int rc = check_tables(t, true, false, /*rescal_ok=*/true);
+  if (rc) return rc;
+  if ((rc = rescal_grouped_gate(t, n))) return rc;
+  if (n < 0 || num_neg < 0 || (slot != 0 && slot != 2)) return KGE_ERR_INVALID_ARG;
+  if (n * num_neg > 0 && (!gout || !neg || !grad_ent || !grad_rel)) return KGE_ERR_INVALID_ARG;
+  if (neg_ld < num_neg || ldg < num_neg || (scores && lds < num_neg)) return KGE_ERR_INVALID_ARG;
+  if (neg_itype != KGE_I32 && neg_itype != KGE_I64) return KGE_ERR_INVALID_ARG;
+  if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
+  if ((rc = check_index(s, false)) || (rc = check_index(p, false)) || (rc = check_index(o, false))) return rc;
+  if (n == 0 || num_neg == 0) return KGE_OK;
+  if (!workspace || workspace_bytes < rescal_grouped_workspace_bytes((int)t->dim, n)) return KGE_ERR_WORKSPACE;
+  return run_rescal_neg_bwd_accum_grouped(ent_op(t, s), rel_op(t, p), ent_op(t, o), (int)t->dim, n, t->num_rel, slot, neg,
+                                          neg_itype, neg_ld, num_neg, gout, ldg, grad_ent, grad_ent_ld, grad_rel,
+                                          grad_rel_ld, workspace, (hipStream_t)stream);
 }
 
 // ---- Relational Tucker3 (tucker3.hip): the gate of the four entries, and the base-row index (a range or a vector) ------

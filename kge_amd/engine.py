@@ -22,7 +22,8 @@ import torch
 
 from . import _lib
 from ._lib import (BF16, F32, FLAG_BF16_V3, FLAG_EXACT, FLAG_NO_MFMA, FLAG_SPLIT_QUERY, I32, I64, PO_,
-                   RESCAL_MAX_DIM, SCORERS, TUCKER3_MAX_BASE_DIM, SP_, SP_PO, SPO, KgeIndex, KgeNextQueries, KgeTables)
+                   RESCAL_GROUPED_MAX_N, RESCAL_MAX_DIM, SCORERS, TUCKER3_MAX_BASE_DIM, SP_, SP_PO, SPO, KgeIndex,
+                   KgeNextQueries, KgeTables)
 
 __all__ = ["Tables", "score_spo", "score_sp", "score_po", "score_sp_po", "score_neg", "score_neg_shared", "score_so", "shared_samples",
            "score_emb", "embed", "shard_gather", "shard_pick", "ns_bce_loss", "ns_loss", "ns_loss_parts", "NS_LOSS_KINDS", "neg_sample", "kvsall_collate", "rank_counts", "score_pitch", "eval_batch", "FLAG_EXACT", "FLAG_NO_MFMA", "FLAG_BF16_V3",
@@ -359,9 +360,57 @@ def score_sp_po(t: Tables, s, p, o, entity_subset=None, flags=None) -> torch.Ten
     return out
 
 
-def rescal_queries(t: Tables, direction: str, a, p, out=None) -> torch.Tensor:
+_RG_WORKSPACES = {}
+
+
+def _grouped_tables(t: Tables) -> KgeTables:
+    """the C view of the tables with KGE_FLAG_RESCAL_GROUPED: the opt-in the grouped entries ask for"""
+    return t.c(t.flags | _lib.FLAG_RESCAL_GROUPED)
+
+
+def _rescal_grouped_workspace(t: Tables, n: int) -> torch.Tensor:
+    """The per-(device, stream) workspace of the relation-grouped RESCAL entries (kge_rescal_grouped_workspace_bytes;
+    nothing in it needs zeroing), grown on demand; raises where the grouped route does not take the tables or n."""
+    need = _lib.lib().kge_rescal_grouped_workspace_bytes(ctypes.byref(_grouped_tables(t)), n)
+    if need <= 0:
+        raise ValueError("kge_amd: the relation-grouped RESCAL route takes float32 'rescal' tables, dim <= {} and "
+                         "1 <= n <= {}".format(RESCAL_MAX_DIM, _lib.RESCAL_GROUPED_MAX_N))
+    key = (t.device.index, _stream_handle(t.device))
+    buf = _RG_WORKSPACES.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _RG_WORKSPACES[key] = _empty((max(need, 1 << 16),), t.device, torch.uint8)
+    return buf
+
+
+def rescal_group(t: Tables, p):
+    """(perm [n], G [1], group_rel [n], group_begin [n + 1]), int32 on the device (kge_rescal_group): the batch positions
+    in ascending relation id, ascending position inside a relation (a stable order); the number of distinct relations;
+    group g < G is relation group_rel[g] and the positions perm[group_begin[g] : group_begin[g + 1]].  No host wait: G
+    stays on the device, the entries behind G are not written."""
+    keep = []
+    pi = _index(p, t.device, keep)
+    n = keep[0].numel()
+    if n == 0:
+        z = torch.zeros(1, dtype=torch.int32, device=t.device)
+        return z[:0], z, z[:0], z.clone()
+    with _on_device(t.device):
+        ws = _rescal_grouped_workspace(t, n)
+        _lib.check(_lib.lib().kge_rescal_group(ctypes.byref(_grouped_tables(t)), pi, n, ws.data_ptr(), ws.numel(),
+                                               _stream(t.device)), "kge_rescal_group")
+    a16 = lambda b: (b + 15) & ~15  # the public sections of the workspace (include/kge_amd.h)
+    o1, o2 = a16(4 * n), 2 * a16(4 * n)
+    o3 = o2 + a16(4 * (n + 1))
+    view = lambda off, cnt: ws[off:off + 4 * cnt].view(torch.int32).clone()
+    return view(0, n), view(o3, 1), view(o1, n), view(o2, n + 1)
+
+
+def rescal_queries(t: Tables, direction: str, a, p, out=None, grouped: bool = False) -> torch.Tensor:
     """[n, d] dense RESCAL queries (kge_rescal_queries): q_i = M_{p_i}^T ent[a_i] (direction "sp_") or M_{p_i} ent[a_i]
-    ("_po") -- the rows kge_score_sp / kge_score_po contract with the targets, in the same bits."""
+    ("_po") -- the rows kge_score_sp / kge_score_po contract with the targets, in the same bits.  grouped=True:
+    kge_rescal_queries_grouped -- the rows of a relation built together on the matrix cores, M_p read once per tile of
+    16 rows; the same real numbers in the MFMA's rounding (not bit-equal to the default)."""
+    if grouped:
+        return _rescal_queries_grouped(t, direction, a, p, out)
     if direction not in ("sp_", "_po"):
         raise ValueError("kge_amd: rescal_queries: direction is 'sp_' or '_po'")
     keep = []
@@ -377,6 +426,65 @@ def rescal_queries(t: Tables, direction: str, a, p, out=None) -> torch.Tensor:
                                                  out.data_ptr(), out.stride(0) if n > 1 else d, _stream(t.device)),
                    "kge_rescal_queries")
     return out
+
+
+def _rescal_queries_grouped(t: Tables, direction: str, a, p, out=None) -> torch.Tensor:
+    if direction not in ("sp_", "_po"):
+        raise ValueError("kge_amd: rescal_queries: direction is 'sp_' or '_po'")
+    keep = []
+    ai, pi = _index(a, t.device, keep), _index(p, t.device, keep)
+    n = _same_len(keep[:2], "rescal_queries")
+    d = t.ent.shape[1]
+    if out is None:
+        out = _empty((n, d), t.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape != (n, d) or out.stride(1) != 1 or out.device != t.device:
+        raise ValueError("kge_amd: rescal_queries: out must be a float32 [n, d] tensor with unit inner stride")
+    if n == 0:
+        return out
+    with _on_device(t.device):
+        ws = _rescal_grouped_workspace(t, n)
+        _lib.check(_lib.lib().kge_rescal_queries_grouped(
+            ctypes.byref(_grouped_tables(t)), SP_ if direction == "sp_" else PO_, ai, pi, n, out.data_ptr(),
+            out.stride(0) if n > 1 else d, ws.data_ptr(), ws.numel(), _stream(t.device)), "kge_rescal_queries_grouped")
+    return out
+
+
+def score_neg_bwd_accum_grouped(t: Tables, s, p, o, slot: int, neg: torch.Tensor, gout, scores, grad_ent, grad_rel):
+    """score_neg_bwd_accum on the relation-grouped RESCAL route (kge_score_neg_bwd_accum_grouped): `grad_rel` gets plain
+    adds from one owner per tile -- no float atomics, the same bits on every run; `grad_ent` float atomics.  `scores` is
+    not read.  False where the entry declines the tables or n (KGE_ERR_UNSUPPORTED).  The positives' backward is this
+    call with slot 2 and neg = o viewed as [n, 1]."""
+    keep = []
+    si, pi, oi = (_index(x, t.device, keep) for x in (s, p, o))
+    n = _same_len(keep[:3], "score_neg_bwd_accum_grouped")
+    if neg.dtype not in (torch.int32, torch.int64):
+        neg = neg.long()
+    if neg.dim() != 2 or neg.shape[0] != n:
+        raise ValueError("kge_amd: neg must be [n, K]")
+    K = neg.shape[1]
+    if (neg.stride(1) != 1 and K > 1) or (n > 1 and neg.stride(0) < K):
+        neg = neg.contiguous()
+    gout = gout.to(device=t.device, dtype=torch.float32)
+    if gout.dim() != 2 or (gout.stride(1) != 1 and K > 1) or (n > 1 and gout.stride(0) < K):  # (an expanded scalar)
+        gout = gout.contiguous().view(n, K)
+    if n * K == 0:
+        return True
+    with _on_device(t.device):
+        tc = _grouped_tables(t)
+        need = _lib.lib().kge_rescal_grouped_workspace_bytes(ctypes.byref(tc), n)
+        if need <= 0:
+            return False
+        ws = _rescal_grouped_workspace(t, n)
+        rc = _lib.lib().kge_score_neg_bwd_accum_grouped(
+            ctypes.byref(tc), si, pi, oi, n, int(slot), neg.data_ptr(), I32 if neg.dtype == torch.int32 else I64,
+            neg.stride(0) if n > 1 else K, K, gout.data_ptr(), gout.stride(0) if n > 1 else K, None, 0,
+            grad_ent.data_ptr(), grad_ent.stride(0), grad_rel.data_ptr(), grad_rel.stride(0), ws.data_ptr(), ws.numel(),
+            _stream_handle(t.device))
+    if rc == _lib.KGE_ERR_UNSUPPORTED:
+        return False
+    if rc:
+        _lib.check(rc, "kge_score_neg_bwd_accum_grouped")
+    return True
 
 
 class ConveNet:

@@ -166,6 +166,17 @@ class _FusedScoring:
     def _touched_pair(self):
         return getattr(self, "_touched_rows", None) if self.training else None
 
+    def set_rescal_grouped(self, on: bool):
+        """hip_negative_sampling.rescal_grouped (hip_rescal, hip_relational_tucker3): the backward of score_spo / score_neg /
+        score_neg_blocks on the relation-grouped entry kge_score_neg_bwd_accum_grouped"""
+        if on and self._scorer.name != "rescal":
+            raise ValueError("hip_negative_sampling.rescal_grouped is an option of hip_rescal and "
+                             "hip_relational_tucker3")
+        self._rescal_grouped = bool(on)
+
+    def _grouped(self) -> bool:
+        return bool(getattr(self, "_rescal_grouped", False))
+
     def penalty(self, **kwargs):
         """KgeModel.penalty (kge_model.py:603-640) first copies the batch's triples to the device -- a blocking
         host-to-device copy in every batch -- and then asks the embedders, which answer with nothing when their
@@ -204,7 +215,8 @@ class _FusedScoring:
                                               self._next_dropout(probs), self._touched_pair())
             return super().score_spo(s, p, o, direction)
         ent, rel = self._w()
-        return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, self._touched_pair())
+        return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, self._touched_pair(),
+                               self._grouped())
 
     def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor) -> Tensor:
         """[n, K] scores of the positives with slot (0 = s, 2 = o) replaced by neg[i, k]: what
@@ -224,7 +236,7 @@ class _FusedScoring:
         if not ent.is_cuda:
             return None
         return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), neg,
-                               self._touched_pair())
+                               self._touched_pair(), self._grouped())
 
     def score_neg_shared(self, s: Tensor, p: Tensor, o: Tensor, slot: int, unique: Tensor, drop: Tensor = None,
                          repeat: Tensor = None):
@@ -250,7 +262,7 @@ class _FusedScoring:
         if not neg_blocks_fusable(ent, rel):
             return None
         return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o,
-                                     self._touched_pair())
+                                     self._touched_pair(), self._grouped())
 
     def _padded(self) -> bool:
         """`padded_scores` (hip_*.yaml, default true): where no gradient is recorded -- evaluation, scoring under
@@ -697,21 +709,22 @@ class HipRelationalTucker3(Tucker3Routes, _FusedScoring, _RefRelationalTucker3):
         if not self._fused():
             return super().score_spo(s, p, o, direction)
         rel, p2, rows = self._rel(p)
-        return _ScoreSPO.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, None)
+        return _ScoreSPO.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, None,
+                               self._grouped())
 
     def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor):
         if not self._fused() or slot not in (0, 2):
             return None
         rel, p2, rows = self._rel(p)
         return _ScoreNeg.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, int(slot), neg,
-                               None)
+                               None, self._grouped())
 
     def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None):
         if not self._fused():
             return None
         rel, p2, rows = self._rel(p)
         return _ScoreNegBlocks.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, neg_s,
-                                     neg_o, None)
+                                     neg_o, None, self._grouped())
 
     def _table_call(self, p: Tensor) -> bool:
         """_FusedScoring's calls on `_w()` (the cached table, range targets, padded rows): no fused gather, or no gradient

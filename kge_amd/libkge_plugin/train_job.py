@@ -987,6 +987,16 @@ class HipTrainingJobNegativeSampling(_CudaOomText, TrainingJobNegativeSampling):
             fused_dropout = False
         if hasattr(self.model, "set_fused_dropout"):
             self.model.set_fused_dropout(fused_dropout and str(self.device).startswith("cuda"))
+        # hip_rescal / hip_relational_tucker3: the backward on the relation-grouped RESCAL entry (false by default)
+        try:
+            rescal_grouped = bool(config.get("hip_negative_sampling.rescal_grouped"))
+        except KeyError:
+            rescal_grouped = False
+        if rescal_grouped:
+            if not hasattr(self.model, "set_rescal_grouped"):
+                raise ValueError("hip_negative_sampling.rescal_grouped is an option of hip_rescal and "
+                                 "hip_relational_tucker3")
+            self.model.set_rescal_grouped(str(self.device).startswith("cuda"))
         # the samples of the subject / object slot drawn on the device (hip_negative_sampling.device_sampler, false by
         # default: every slot's samples come from the reference's sampler on the host)
         try:

@@ -184,8 +184,18 @@ class KgeModel(torch.nn.Module):
     def __init__(self, num_entities: int, num_relations: int, dim: int, l_norm: float = 1.0,
                  dtype=torch.float32, device=None, entity_args=None, relation_args=None,
                  score_dtype=None, fused_dist_loss: bool = False, fused_f32_loss: bool = False, scorer_args=None,
-                 fused_dropout: bool = False):
+                 fused_dropout: bool = False, grouped: bool = False):
         super().__init__()
+        # grouped=True (Rescal / RelationalTucker3): the backward of score_spo, score_neg and score_neg_blocks takes the
+        # relation-grouped entry kge_score_neg_bwd_accum_grouped -- the d^2 work of a relation on the matrix cores, a
+        # relation gradient without float atomics (the same bits on every run); off by default
+        self.grouped = bool(grouped)
+        if self.grouped:
+            if self.scorer_cls is not RescalScorer:
+                raise ValueError("{}: grouped is a route of the RESCAL kernels (rescal, relational_tucker3)".format(
+                    type(self).__name__))
+            if fused_dropout:
+                raise ValueError("{}: grouped: fused_dropout is not supported".format(type(self).__name__))
         # fused_dropout=True (ComplEx / DistMult / TransE / RotatE, float32 parameters on a GPU, dim <= 1024): in training
         # mode with embedder dropout, score_spo and score_neg stay on the fused kernels -- the masks are computed inside
         # them (kge_score_spo_dropout / kge_score_neg_dropout and their backward) from `dropout_seed` (taken from
@@ -249,7 +259,8 @@ class KgeModel(torch.nn.Module):
         `rel_pair` = kge_amd.optim.SparseAdam.enable_touched_rows(relation table): the relation gradient goes the same
         way, the batch's `p` rows marked; None: a fresh dense relation gradient per node."""
         if pair is not None and self.scorer_cls in (TransHScorer, RescalScorer):
-            raise ValueError("{}: touched_rows is not supported".format(type(self).__name__))
+            raise ValueError("{}: {}touched_rows is not supported".format(type(self).__name__,
+                                                                          "grouped: " if self.grouped else ""))
         if pair is None and rel_pair is not None:
             raise ValueError("{}: the relation table's touched rows need the entity table's".format(type(self).__name__))
         self._touched_rows = pair if rel_pair is None else (pair, rel_pair)
@@ -306,7 +317,7 @@ class KgeModel(torch.nn.Module):
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
         if self._fused():
             return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                   self._relation_embedder.weight, s, p, o, self._touched_rows)
+                                   self._relation_embedder.weight, s, p, o, self._touched_rows, self.grouped)
         dp = self._dropout_triple()
         if dp is not None:
             return _ScoreSPODropout.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
@@ -320,7 +331,8 @@ class KgeModel(torch.nn.Module):
         BatchNegativeSample.score with implementation "triple" (kge/util/sampler.py:291-306)."""
         if self._fused() and slot in (0, 2):
             return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                   self._relation_embedder.weight, s, p, o, int(slot), neg, self._touched_rows)
+                                   self._relation_embedder.weight, s, p, o, int(slot), neg, self._touched_rows,
+                                   self.grouped)
         dp = self._dropout_triple() if slot in (0, 2) else None
         if dp is not None:
             return _ScoreNegDropout.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
@@ -337,7 +349,8 @@ class KgeModel(torch.nn.Module):
         NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score (kge/util/sampler.py:428-463, 537-578);
         equals score_neg on engine.shared_samples(unique, drop, repeat, n)."""
         if self.scorer_cls is RescalScorer:  # no kge_score_neg_shared kernel, and none composed in its place
-            raise ValueError("Rescal: shared negative samples (score_neg_shared) are not supported; use score_neg")
+            raise ValueError("Rescal: {}shared negative samples (score_neg_shared) are not supported; use "
+                             "score_neg".format("grouped: " if self.grouped else ""))
         if self._fused() and slot in (0, 2) and self._scorer.name not in _COMPOSED_ONLY and \
                 neg_shared_fusable(self._entity_embedder.weight, s.numel()):
             return _ScoreNegShared.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
@@ -351,7 +364,7 @@ class KgeModel(torch.nn.Module):
         ent, rel = self._entity_embedder.weight, self._relation_embedder.weight
         if self._fused() and neg_blocks_fusable(ent, rel):
             return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o,
-                                         self._touched_rows)
+                                         self._touched_rows, self.grouped)
         pos = self.score_spo(s, p, o)
         return (pos, None if neg_s is None else self.score_neg(s, p, o, 0, neg_s),
                 None if neg_o is None else self.score_neg(s, p, o, 2, neg_o))
@@ -762,13 +775,14 @@ class RelationalTucker3(Tucker3Routes, KgeModel):
         if not self._fused():
             return super().score_spo(s, p, o, direction)
         rel, p2, rows = self._rel(p, project)
-        return _ScoreSPO.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, None)
+        return _ScoreSPO.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, None, self.grouped)
 
     def score_neg(self, s, p, o, slot, neg, project=None):
         if not (self._fused() and slot in (0, 2)):
             return super().score_neg(s, p, o, slot, neg)
         rel, p2, rows = self._rel(p, project)
-        return _ScoreNeg.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, int(slot), neg, None)
+        return _ScoreNeg.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, int(slot), neg, None,
+                               self.grouped)
 
     def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
         raise ValueError("RelationalTucker3: shared negative samples (score_neg_shared) are not supported; use "
@@ -778,7 +792,7 @@ class RelationalTucker3(Tucker3Routes, KgeModel):
         ent = self._entity_embedder.weight
         if self._fused() and ent.is_cuda and ent.dtype == torch.float32:
             rel, p2, rows = self._rel(p, project)
-            return _ScoreNegBlocks.apply("rescal", 1.0, ent, rel, s, p2, o, neg_s, neg_o, None)
+            return _ScoreNegBlocks.apply("rescal", 1.0, ent, rel, s, p2, o, neg_s, neg_o, None, self.grouped)
         return super().score_neg_blocks(s, p, o, neg_s, neg_o)
 
     def score_sp(self, s, p, o=None, project=None):
@@ -1169,12 +1183,35 @@ def _touched_buffers(t, touched, p, *ent_ids):
     return ent[0], rel[0], True
 
 
+def _grouped_route(name, grouped, touched) -> bool:
+    """Does a node's backward take the relation-grouped RESCAL entry (create(..., grouped=True))?"""
+    if not grouped:
+        return False
+    if name != "rescal":
+        raise ValueError("kge_amd: grouped is a route of the 'rescal' scorer (got {!r})".format(name))
+    if touched is not None:
+        raise ValueError("kge_amd: grouped: touched_rows is not supported")
+    return True
+
+
+def _grouped_neg_bwd(t, s, p, o, slot, neg, gout, ge, gr):
+    if not engine.score_neg_bwd_accum_grouped(t, s, p, o, slot, neg, gout, None, ge, gr):
+        raise RuntimeError("kge_amd: kge_score_neg_bwd_accum_grouped declined the batch (float32 tables, dim <= {}, "
+                           "n <= {})".format(engine.RESCAL_MAX_DIM, engine.RESCAL_GROUPED_MAX_N))
+
+
+def _grouped_spo_bwd(t, s, p, o, gout, ge, gr):
+    o1 = o.reshape(-1)
+    _grouped_neg_bwd(t, s, p, o, 2, o1.view(o1.numel(), 1), gout.reshape(-1, 1), ge, gr)
+
+
 class _ScoreSPO(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, name, l_norm, ent, rel, s, p, o, touched=None):
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, touched=None, grouped=False):
         t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
         ctx.t, ctx.idx = t, (s, p, o)
         ctx.touched = None if touched is None else _touched_pair(t, touched)
+        ctx.grouped = _grouped_route(name, grouped, touched)
         out = engine.score_spo(t, s, p, o)
         ctx.save_for_backward(out)
         return out
@@ -1183,11 +1220,15 @@ class _ScoreSPO(torch.autograd.Function):
     def backward(ctx, gout):
         s, p, o = ctx.idx
         (scores,) = ctx.saved_tensors
+        if ctx.grouped:  # the relation-grouped RESCAL route: score_spo is score_neg, slot 2, with neg = o as [n, 1]
+            ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
+            _grouped_spo_bwd(ctx.t, s, p, o, gout, ge, gr)
+            return None, None, ge, gr, None, None, None, None, None
         if ctx.touched is not None:  # the accumulate route on the persistent buffer, or nothing
             ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o)
             if not engine.score_spo_bwd_accum(ctx.t, s, p, o, gout.contiguous(), scores, ge, gr):
                 raise RuntimeError("kge_amd: kge_score_spo_bwd_accum declined a shape the touched-row step admitted")
-            return None, None, None, None if rel_kept else gr, None, None, None, None
+            return None, None, None, None if rel_kept else gr, None, None, None, None, None
         ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
         # one kernel: row gradients accumulated into the table gradients (runs of equal s / p
         # summed in registers first); fallback: row gradients + three scatter-adds
@@ -1196,7 +1237,7 @@ class _ScoreSPO(torch.autograd.Function):
             _scatter_rows(ge, s, g_s)
             _scatter_rows(ge, o, g_o)
             _scatter_rows(gr, p, g_p)
-        return None, None, ge, gr, None, None, None, None
+        return None, None, ge, gr, None, None, None, None, None
 
 
 class _ScoreNeg(torch.autograd.Function):
@@ -1206,11 +1247,12 @@ class _ScoreNeg(torch.autograd.Function):
     tensor and no [n*K, d] gathered rows in either pass)."""
 
     @staticmethod
-    def forward(ctx, name, l_norm, ent, rel, s, p, o, slot, neg, touched=None):
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, slot, neg, touched=None, grouped=False):
         t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
         out = engine.score_neg(t, s, p, o, slot, neg)
         ctx.t, ctx.idx, ctx.slot = t, (s, p, o, neg), slot
         ctx.touched = None if touched is None else _touched_pair(t, touched)
+        ctx.grouped = _grouped_route(name, grouped, touched)
         ctx.save_for_backward(out)
         return out
 
@@ -1218,11 +1260,15 @@ class _ScoreNeg(torch.autograd.Function):
     def backward(ctx, gout):
         s, p, o, neg = ctx.idx
         (scores,) = ctx.saved_tensors
+        if ctx.grouped:
+            ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
+            _grouped_neg_bwd(ctx.t, s, p, o, ctx.slot, neg, gout, ge, gr)
+            return None, None, ge, gr, None, None, None, None, None, None, None
         if ctx.touched is not None:  # the accumulate kernel on the persistent buffer, or nothing
             ge, gr, rel_kept = _touched_buffers(ctx.t, ctx.touched, p, s, o, neg)
             if not engine.score_neg_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr):
                 raise RuntimeError("kge_amd: kge_score_neg_bwd_accum declined a shape the touched-row step admitted")
-            return None, None, None, None if rel_kept else gr, None, None, None, None, None, None
+            return None, None, None, None if rel_kept else gr, None, None, None, None, None, None, None
         ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
         if not engine.score_neg_bwd_accum(ctx.t, s, p, o, ctx.slot, neg, gout, scores, ge, gr):
             # shapes the accumulate kernel does not take (bf16 parameters, d > 1024): expanded triples
@@ -1236,7 +1282,7 @@ class _ScoreNeg(torch.autograd.Function):
             _scatter_rows(ge, tr[2], g_o)
             _scatter_rows(gr, tr[1], g_p)
             ge, gr = ge.to(ctx.t.ent.dtype), gr.to(ctx.t.rel.dtype)
-        return None, None, ge, gr, None, None, None, None, None, None
+        return None, None, ge, gr, None, None, None, None, None, None, None
 
 
 # ---- embedder dropout inside the triple-wise kernels (include/kge_amd.h "Embedder dropout") ----------------
@@ -1412,13 +1458,14 @@ class _ScoreNegBlocks(torch.autograd.Function):
     (the accumulate kernels' domain; the caller checks)."""
 
     @staticmethod
-    def forward(ctx, name, l_norm, ent, rel, s, p, o, neg_s, neg_o, touched=None):
+    def forward(ctx, name, l_norm, ent, rel, s, p, o, neg_s, neg_o, touched=None, grouped=False):
         t = engine.Tables(name, ent.detach(), rel.detach(), l_norm)
         pos = engine.score_spo(t, s, p, o)
         sc_s = engine.score_neg(t, s, p, o, 0, neg_s) if neg_s is not None else None
         sc_o = engine.score_neg(t, s, p, o, 2, neg_o) if neg_o is not None else None
         ctx.t, ctx.idx = t, (s, p, o, neg_s, neg_o)
         ctx.touched = None if touched is None else _touched_pair(t, touched)
+        ctx.grouped = _grouped_route(name, grouped, touched)
         ctx.save_for_backward(pos, sc_s, sc_o)
         return pos, sc_s, sc_o
 
@@ -1433,6 +1480,13 @@ class _ScoreNegBlocks(torch.autograd.Function):
                                                 neg_o if g_o is not None else None)
         else:
             ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
+        if ctx.grouped:  # the relation-grouped RESCAL route, all three blocks into the one pair of gradients
+            if g_pos is not None:
+                _grouped_spo_bwd(ctx.t, s, p, o, g_pos, ge, gr)
+            for slot, neg, g in ((0, neg_s, g_s), (2, neg_o, g_o)):
+                if neg is not None and g is not None:
+                    _grouped_neg_bwd(ctx.t, s, p, o, slot, neg, g, ge, gr)
+            return None, None, ge, gr, None, None, None, None, None, None, None
         if g_pos is not None and not engine.score_spo_bwd_accum(ctx.t, s, p, o, g_pos.contiguous(), pos, ge, gr):
             raise RuntimeError("kge_amd: kge_score_spo_bwd_accum declined a shape score_neg_blocks admitted")
         for slot, neg, g, sc in ((0, neg_s, g_s, sc_s), (2, neg_o, g_o, sc_o)):
@@ -1440,7 +1494,7 @@ class _ScoreNegBlocks(torch.autograd.Function):
                 if not engine.score_neg_bwd_accum(ctx.t, s, p, o, slot, neg, g, sc, ge, gr):
                     raise RuntimeError("kge_amd: kge_score_neg_bwd_accum declined a shape score_neg_blocks admitted")
         return (None, None, None if ctx.touched is not None else ge, None if rel_kept else gr, None, None, None, None,
-                None, None)
+                None, None, None)
 
 
 def neg_shared_fusable(ent: torch.Tensor, n: int) -> bool:
