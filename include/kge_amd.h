@@ -763,13 +763,18 @@ int kge_rank_hist(const int64_t* rank, const int64_t* ties, int num_rankings, in
  *               else.  A row with fewer than k columns left is padded with (-inf, -1) BEHIND its real columns (a real
  *               column whose score is -inf or NaN is listed, as -inf, in its id order, ahead of the padding);
  *   workspace   >= kge_topk_workspace_bytes(t, n, m, k, num_filters) bytes, 16-byte aligned, contents irrelevant: the
- *               call zeroes the filter bits it uses itself and leaves nothing the caller has to preserve.
+ *               call zeroes the filter bits it uses itself and leaves nothing the caller has to preserve.  Beside the
+ *               filter bits it holds the column groups' lists: n x groups x k keys of 8 bytes up to k = 128 where the
+ *               call takes the narrow kernels; n x groups x (2 k keys + 4 bytes) on the wide kernels (every k > 128,
+ *               and the smaller k the library routes there), groups <= 512 chosen by the call so that a group sees
+ *               about 4 k columns.  Ask kge_topk_workspace_bytes with the arguments of the call;
+ *   k           1 <= k <= KGE_TOPK_MAX = 1024, the same contract over the whole range;
  * The result is a pure function of the arguments: it does not depend on how the launch cuts the columns into groups.
  * Stream-ordered, no host wait.  KGE_ERR_INVALID_ARG: k < 1, k > KGE_TOPK_MAX, ld < k, NULL outputs with n > 0,
  * m >= 2^32, a slice outside the table, a missing filter pointer; KGE_ERR_WORKSPACE: workspace too small or misaligned;
  * KGE_ERR_UNSUPPORTED: KGE_FLAG_SPLIT_QUERY / KGE_FLAG_BF16_V3 in the tables' flags, num_filters > 2.  n == 0 or
  * m == 0: KGE_OK (m == 0: every row is padding). */
-enum { KGE_TOPK_MAX = 128 };
+enum { KGE_TOPK_MAX = 1024 };
 int64_t kge_topk_workspace_bytes(const kge_tables* t, int64_t n, int64_t m, int k, int num_filters);
 int kge_topk(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t n, int64_t col_begin, int64_t m, int k,
              int num_filters, const int64_t* const* f_begin, const int64_t* const* f_end,

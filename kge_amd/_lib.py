@@ -116,7 +116,7 @@ class KgeKvsallTyped(ctypes.Structure):
 
 
 KVSALL_COLLATE_MAX_N = 1 << 20  # KGE_KVSALL_COLLATE_MAX_N
-TOPK_MAX = 128  # KGE_TOPK_MAX
+TOPK_MAX = 1024  # KGE_TOPK_MAX
 RESCAL_MAX_DIM = 256  # KGE_RESCAL_MAX_DIM
 RESCAL_GROUPED_MAX_N = 65536  # KGE_RESCAL_GROUPED_MAX_N
 TUCKER3_MAX_BASE_DIM = 1024  # KGE_TUCKER3_MAX_BASE_DIM

@@ -218,7 +218,7 @@ int run_eval_end(const EvalLists& L, long long n, long long m, long long rs, lon
 int run_rank_bits(int lists, const long long* const* begin, const long long* const* end, const long long* const* col,
                   const Index* keep, unsigned int* const* bits, long long n, long long col_begin, long long m,
                   long long rs, long long us, int set, hipStream_t st);
-long long topk_groups(long long n, long long m, int* col_tiles);
+long long topk_part_bytes(long long n, long long m, int k);
 int run_topk(int scorer, int dtype, bool use_mfma, const Operand& A, const Operand& R, const Operand& TG, int dir, int d,
              int dr, long long n, long long m, float lp, int k, int nfilt, const unsigned int* const* bits,
              long long bits_rs, long long bits_us, unsigned long long* part, long long col_begin, float* out_val,
@@ -635,13 +635,13 @@ int pairs_entry(const kge_tables* t, int dir, kge_index a, kge_index p, int64_t 
 
 // ---- measurement switches (switches.hpp, include/kge_amd_debug.h) ----
 namespace kge {
-static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-static_assert(SW_COUNT == 23, "g_switch's initialiser");
+static long long g_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(SW_COUNT == 24, "g_switch's initialiser");
 static const char* const g_switch_name[SW_COUNT] = {
     "ONE_CALL_PREPARED", "ONE_CALL_V8", "ONE_CALL_V8_MIN_ROWS", "V8_RANK", "RANK_FUSED_FRONT", "BWD_GEMM_LIB",
     "CE_V3", "CE_V8", "V4_OWN_BUILD", "V4_INTERLEAVE", "V4_STORE_SC1", "V6", "V7", "V7_NOSTORE", "V7_PROBE", "V8",
     "V8_VAR", "V8_MFMA32", "V8_TAIL_FIXED", "V8R_PROBE", "TRANSE_GENERIC", "TOPK_COL_TILES",
-    "PENALTY_COUNT_PLAIN"};
+    "PENALTY_COUNT_PLAIN", "TOPK_WIDE"};
 long long sw(Switch s) { return __atomic_load_n(&g_switch[(int)s], __ATOMIC_RELAXED); }
 static int switch_index(const char* name) {
   if (name == nullptr) return -1;
@@ -1801,7 +1801,8 @@ int kge_score_rank_sp_po(const kge_tables* t, kge_index s, kge_index p, kge_inde
 // ---- filtered top-k prediction (topk.hip): KgeModel.score_sp / score_po + the masking of
 // EntityRankingJob._filter_and_rank + torch.topk, without the score matrix.  Workspace: [0, 256) the "no exception"
 // keep id (-1) that run_rank_bits reads when the caller gives none; then the filter bits (the one-sided layout of
-// rank_bits_layout), zeroed by the call; then the groups' lists [n][groups][k].
+// rank_bits_layout), zeroed by the call; then the groups' lists: [n][groups][k] keys for the narrow pair, [n][groups][2][k]
+// keys and [n][groups] list states for the wide pair (topk_part_bytes: the pair the call takes).
 namespace {
 struct TopkLayout {
   RankBitsLayout bl;
@@ -1813,7 +1814,7 @@ TopkLayout topk_layout(int64_t n, int64_t m, int k, int num_filters) {
   L.bits_off = 256;
   L.bits_bytes = num_filters > 0 ? (L.bl.words * 4 + 255) / 256 * 256 : 0;
   L.part_off = L.bits_off + L.bits_bytes;
-  L.total = L.part_off + n * kge::topk_groups(n, m, nullptr) * (int64_t)k * 8;
+  L.total = L.part_off + kge::topk_part_bytes(n, m, k);
   return L;
 }
 }  // namespace

@@ -8,34 +8,17 @@
 //                       (as pairs_kernel's counting epilogue does) and is consumed there: each of the workgroup's 64
 //                       rows keeps a sorted list of its k best 64-bit keys in LDS.  The lists leave the workgroup once.
 //   topk_merge_kernel   one wave per row merges the `groups` sorted lists into the best k and unpacks them.
+// This pair serves k <= 128 (TOPK_NARROW_MAX: the lists are 64 x k keys of LDS); run_topk hands k > 128, and the
+// smaller k from TOPK_WIDE_K0 on, to the wide pair of topk_wide.hip (topk_takes_wide).
 //
 // Key: high word = the order-preserving unsigned image of the canonical score (NaN -> -inf, -0.0 -> +0.0),
 // low word = 0xFFFFFFFF - j (j = the column inside the scored slice).  A larger key is better; equal scores order by
 // ascending entity id; every real column has a non-zero key (j <= 2^32 - 2) and 0 means "empty".  The keys of a row are
 // pairwise distinct, so the best k of their union is one fixed set in one fixed order: the result does not depend on
 // how the columns were cut into groups, on col_tiles or on which workgroup ran first.
-#include "common.hpp"
-#include "pairs_device.hpp"
-#include "switches.hpp"
+#include "topk_device.hpp"
 
 namespace kge {
-
-struct TopkArgs {
-  int nfilt;                     // <= 2
-  const unsigned int* bits[2];   // the filter bits of RankArgs (common.hpp): bit (j & 31) of word [i * rs + (j >> 5) * us]
-  long long bits_rs, bits_us;
-  int col_tiles;                 // column tiles a workgroup walks
-  int k;                         // <= KGE_TOPK_MAX
-  unsigned long long* part;      // [n][groups][k] keys, groups = gridDim.x
-};
-
-__device__ __forceinline__ unsigned long long topk_key(float s, unsigned int j) {
-  if (s != s) s = -__builtin_inff();  // count_one's NaN rule (common.hpp)
-  if (s == 0.0f) s = 0.0f;            // -0.0 -> +0.0
-  const unsigned int u = __float_as_uint(s);
-  const unsigned int hi = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)hi << 32) | (unsigned long long)(0xFFFFFFFFu - j);
-}
 
 extern __shared__ __attribute__((aligned(16))) unsigned long long topk_lists[];  // [k][64]: position-major, row fastest
 
@@ -239,8 +222,6 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Operand A, Operand R, 
 
 // One wave per row: lane l owns the lists l, l + 64, ... and keeps the largest of their heads; per output position the
 // wave takes the largest of the lanes' keys, and the lane that held it moves that list's head on.
-constexpr int TOPK_MAX_GROUPS = 512;
-
 __global__ __launch_bounds__(256) void topk_merge_kernel(const unsigned long long* __restrict__ part, int groups, int k,
                                                          long long n, long long col_begin, float* __restrict__ out_val,
                                                          long long* __restrict__ out_idx, long long ld) {
@@ -290,19 +271,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const unsigned long lon
 }
 
 // ---- host ---------------------------------------------------------------------------------
-static inline bool topk_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// (the conditions of score_pairs.hip's vector loads)
-static bool topk_vec_ok(int dtype, int d, int dr, int scorer, const Operand& A, const Operand& R, const Operand& TG) {
-  if (d % 8) return false;
-  if (scorer == KGE_ROTATE && dr != d / 2) return false;
-  const int es = dtype == KGE_BF16 ? 2 : 4;
-  const int al = dtype == KGE_BF16 ? 8 : 16;
-  if (!topk_aligned16(A.base) || !topk_aligned16(R.base) || !topk_aligned16(TG.base)) return false;
-  if ((A.ld * es) % al || (R.ld * es) % al || (TG.ld * es) % al) return false;
-  return true;
-}
-
 // column tiles per workgroup and column groups of a launch: enough groups that the row blocks x groups fill the CUs
 // twice over, at least four tiles per workgroup where there are that many (the lists fill during the first tiles: the
 // more tiles follow, the less that costs), at most TOPK_MAX_GROUPS groups (topk_merge_kernel's head table).
@@ -326,6 +294,22 @@ long long topk_groups(long long n, long long m, int* col_tiles) {
   return (tiles + ctn - 1) / ctn;
 }
 
+// Which pair a call takes: k > TOPK_NARROW_MAX always the wide one (topk_wide.hip); below, the wide one from
+// TOPK_WIDE_K0 on.  SW_TOPK_WIDE: 1 = the wide pair for every k, 2 = the narrow pair for every k it can serve.
+bool topk_takes_wide(int k) {
+  if (k > TOPK_NARROW_MAX) return true;
+  const long long forced = sw(SW_TOPK_WIDE);
+  if (forced == 1) return true;
+  if (forced == 2) return false;
+  return k >= TOPK_WIDE_K0;
+}
+
+// bytes of the groups' lists in the workspace of the pair the call takes
+long long topk_part_bytes(long long n, long long m, int k) {
+  if (topk_takes_wide(k)) return topk_wide_part_bytes(n, m, k);
+  return n * topk_groups(n, m, nullptr) * (long long)k * 8;
+}
+
 template <int SCORER, typename T, int NORM, bool VEC, bool MFMA>
 static int launch_topk(const Operand& A, const Operand& R, const Operand& TG, int dir, int d, int dr, long long n,
                        long long m, float lp, int round_q, const TopkArgs& ta, long long groups, hipStream_t st) {
@@ -333,7 +317,7 @@ static int launch_topk(const Operand& A, const Operand& R, const Operand& TG, in
   const size_t lds = (size_t)ta.k * PT_BM * sizeof(unsigned long long);
   if (lds > 32 * 1024) {  // (more dynamic LDS than a launch gets without asking)
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            KGE_TOPK_MAX * PT_BM * (int)sizeof(unsigned long long)) != hipSuccess) {
+                            TOPK_NARROW_MAX * PT_BM * (int)sizeof(unsigned long long)) != hipSuccess) {
       (void)hipGetLastError();
       return KGE_ERR_LAUNCH;
     }
@@ -369,6 +353,9 @@ int run_topk(int scorer, int dtype, bool use_mfma, const Operand& A, const Opera
              long long* out_idx, long long ld, hipStream_t st) {
   if (n == 0) return KGE_OK;
   if (n > 65535LL * PT_BM) return KGE_ERR_UNSUPPORTED;
+  if (topk_takes_wide(k))
+    return run_topk_wide(scorer, dtype, use_mfma, A, R, TG, dir, d, dr, n, m, lp, k, nfilt, bits, bits_rs, bits_us, part,
+                         col_begin, out_val, out_idx, ld, st);
   int col_tiles = 1;
   const long long groups = topk_groups(n, m, &col_tiles);
   int rc = KGE_OK;
