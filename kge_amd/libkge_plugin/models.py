@@ -17,11 +17,8 @@ from kge.model.transh import TransHScorer as _RefTransHScorer
 from kge.model.transh import transh_set_relation_embedder_dim
 
 from .. import engine
-from ..model import (BF16Shadow, _FusedCE2, _FusedCE2Sum, _FusedMultiLabel2, _ScoreEmb, _ScoreNeg, _ScoreNegBlocks, _ScoreNegShared,
-                     _ScorePairs, _ScoreSO, _ScoreSPO, _ScoreNegDropout, _ScoreSPODropout, DropoutClock,
-                     dropout_triple_fusable, ConveNetOps, ConveRoutes, Tucker3Routes, ce_fused_dropout,
-                     fused_loss_rows, neg_blocks_fusable, neg_shared_fusable, predict_filters, score_so_fusable,
-                     topk_composed)
+from ..model import (FAMILIES, BF16Shadow, _ScoreEmb, DropoutClock, FusedRoutes, dropout_triple_fusable, ConveNetOps,
+                     ConveRoutes, Tucker3Routes, ce_fused_dropout, predict_filters, topk_composed)
 
 
 class _HipScorer(RelationalScorer):
@@ -92,9 +89,17 @@ class HipRescalScorer(_RefRescalScorer):
     _norm = 1.0  # (the tables' l_norm: ignored by the RESCAL kernels)
 
 
-class _FusedScoring:
+class _FusedScoring(FusedRoutes):
     """Overrides of KgeModel.score_* (kge_model.py:663-789): fused gather + score when both
-    embedders are plain lookup tables (no active dropout, shared entity embedder)."""
+    embedders are plain lookup tables (no active dropout, shared entity embedder) -- the nodes of
+    kge_amd.model.FusedRoutes; where none applies, the reference's own method or None through to the job."""
+
+    def __setattr__(self, name, value):
+        # hip_1vsAll / hip_KvsAll switch their fused losses on by setting these attributes on the model
+        if name in ("_fused_dist_loss", "_fused_f32_loss") and value and "dense_loss" not in self.family.kernels:
+            raise ValueError("hip_{}: {} is not supported (no {} kernel behind the fused losses)".format(
+                self.family.name, name.lstrip("_"), self.family.kernel))
+        super().__setattr__(name, value)
 
     def _fused(self) -> bool:
         from kge.model import LookupEmbedder
@@ -161,6 +166,10 @@ class _FusedScoring:
         or None.  score_spo / score_neg / score_neg_blocks hand it to their autograd nodes while the model trains: the
         backward accumulates the entity gradient into the persistent buffer and marks the rows (kge_amd.model).
         `rel_pair` = HipSparseAdam.enable_touched_rows(relation table): the relation gradient goes the same way."""
+        if "touched" not in self.family.kernels:
+            if pair is not None:
+                raise ValueError("hip_{}: touched_rows is not supported".format(self.family.name))
+            rel_pair = None
         self._touched_rows = pair if rel_pair is None else (pair, rel_pair)
 
     def _touched_pair(self):
@@ -193,8 +202,10 @@ class _FusedScoring:
         """`score_dtype: bfloat16` (hip_complex.yaml / hip_distmult.yaml) with float32 parameters:
         sp_/_po scores come from the bf16 matrix-core kernel on bf16 copies of the tables (re-cast
         after every optimizer step), gradients are taken w.r.t. the float32 masters."""
+        if self._scorer.name not in ("complex", "distmult"):
+            return None
         ent, rel = self._w()
-        if self._scorer.name not in ("complex", "distmult") or ent.dtype != torch.float32:
+        if ent.dtype != torch.float32:
             return None
         try:
             want = self.get_option("score_dtype")
@@ -207,62 +218,30 @@ class _FusedScoring:
         return self._bf16_shadow.tables(self._scorer.name, ent, rel, self._scorer._norm)
 
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
-        if not self._fused():
-            probs = self._dropout_triple()
-            if probs is not None:
-                ent, rel = self._w()
-                return _ScoreSPODropout.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o,
-                                              self._next_dropout(probs), self._touched_pair())
-            return super().score_spo(s, p, o, direction)
-        ent, rel = self._w()
-        return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, self._touched_pair(),
-                               self._grouped())
+        out = self._route_spo(s, p, o)
+        return super().score_spo(s, p, o, direction) if out is None else out
 
     def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor) -> Tensor:
         """[n, K] scores of the positives with slot (0 = s, 2 = o) replaced by neg[i, k]: what
         BatchNegativeSample.score returns (kge/util/sampler.py:263-306), from kge_score_neg -- the
         positives' fixed rows are read once, only the corrupted rows stream; None if the fused
         path does not apply (HipTrainingJobNegativeSampling then calls the sampler's own score)."""
-        if slot not in (0, 2):
-            return None
-        if not self._fused():
-            probs = self._dropout_triple()
-            if probs is None:
-                return None
-            ent, rel = self._w()
-            return _ScoreNegDropout.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), neg,
-                                          self._next_dropout(probs), self._touched_pair())
-        ent, rel = self._w()
-        if not ent.is_cuda:
-            return None
-        return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), neg,
-                               self._touched_pair(), self._grouped())
+        return self._route_neg(s, p, o, slot, neg)
 
     def score_neg_shared(self, s: Tensor, p: Tensor, o: Tensor, slot: int, unique: Tensor, drop: Tensor = None,
                          repeat: Tensor = None):
         """[n, K] scores of the positives against a SHARED negative sample of slot 0 / 2 (unique ids, drop indexes or
         None, repeat columns): what NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score return
         (kge/util/sampler.py:428-463, 537-578), from kge_score_neg_shared -- the target rows staged once per workgroup
-        and shared by its positives; None if the fused path does not apply (the job then calls the sampler's score)."""
-        if not self._fused() or slot not in (0, 2):
-            return None
-        ent, rel = self._w()
-        if not ent.is_cuda or not neg_shared_fusable(ent, s.numel()):
-            return None
-        return _ScoreNegShared.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, int(slot), unique, drop,
-                                     repeat)
+        and shared by its positives; None if the fused path does not apply or the family has no such kernel (the job
+        then calls the sampler's own score)."""
+        return self._route_neg_shared(s, p, o, slot, unique, drop, repeat)
 
     def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None):
         """(positives [n], subject-slot block [n, K_s] or None, object-slot block [n, K_o] or None) as ONE autograd node
         whose backward fills one pair of table gradients (kge_amd.model._ScoreNegBlocks); None if the fused gather does
         not apply (the caller composes score_spo + score_neg)."""
-        if not self._fused():
-            return None
-        ent, rel = self._w()
-        if not neg_blocks_fusable(ent, rel):
-            return None
-        return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o,
-                                     self._touched_pair(), self._grouped())
+        return self._route_neg_blocks(s, p, o, neg_s, neg_o)
 
     def _padded(self) -> bool:
         """`padded_scores` (hip_*.yaml, default true): where no gradient is recorded -- evaluation, scoring under
@@ -320,45 +299,45 @@ class _FusedScoring:
             return subset
         return None if (first == 0 and m == E) else range(first, first + m)
 
-    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
+    def _table_call(self, p: Tensor) -> bool:
+        """No gradient is recorded and the relation table is at hand: the scoring calls then take `_no_grad_call` (range
+        targets, padded rows, split queries) instead of an autograd node.  (hip_relational_tucker3: on its "all" route.)"""
+        return not torch.is_grad_enabled()
+
+    def _pairs(self, direction: str, a: Tensor, p: Tensor, targets):
+        """score_sp ("sp": a = s) / score_po ("po": a = o) on the fused gather, or None"""
+        if not self._table_call(p):
+            return self._route_pairs(direction, a, p, targets)
         if not self._fused():
-            return super().score_sp(s, p, o)
-        ng = self._no_grad_call()
-        if ng is not None:
-            return engine.score_sp(ng[0], s, p, self._targets(o), flags=ng[1], padded=self._padded())
-        ent, rel = self._w()
-        return _ScorePairs.apply(self._scorer.name, self._scorer._norm, "sp", ent, rel, s, p, o,
-                                 self._fwd_tables(), self._padded())
+            return None
+        t, flags = self._no_grad_call()
+        if direction == "sp":
+            return engine.score_sp(t, a, p, self._targets(targets), flags=flags, padded=self._padded())
+        return engine.score_po(t, p, a, self._targets(targets), flags=flags, padded=self._padded())
+
+    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
+        out = self._pairs("sp", s, p, o)
+        return super().score_sp(s, p, o) if out is None else out
 
     def score_po(self, p: Tensor, o: Tensor, s: Tensor = None) -> Tensor:
-        if not self._fused():
-            return super().score_po(p, o, s)
-        ng = self._no_grad_call()
-        if ng is not None:
-            return engine.score_po(ng[0], p, o, self._targets(s), flags=ng[1], padded=self._padded())
-        ent, rel = self._w()
-        return _ScorePairs.apply(self._scorer.name, self._scorer._norm, "po", ent, rel, o, p, s,
-                                 self._fwd_tables(), self._padded())
+        out = self._pairs("po", o, p, s)
+        return super().score_po(p, o, s) if out is None else out
 
     def score_so(self, s: Tensor, o: Tensor, p: Tensor = None) -> Tensor:
         """KgeModel.score_so (kge_model.py:727-747) from kge_score_so: what hip_KvsAll calls for `s_o` queries and the
         reference sampler for the relation slot under `negative_sampling.implementation: batch`.  The reference's own
         composition (kge_model.py:202-209) wherever the kernel does not apply (other scorers, dropout, CPU, bf16 tables
         with a recorded gradient)."""
-        if not self._fused():
-            return super().score_so(s, o, p)
-        ent, rel = self._w()
-        if not score_so_fusable(self._scorer.name, ent, rel, s.numel()):
-            return super().score_so(s, o, p)
-        return _ScoreSO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, o, p,
-                              self._touched_pair() if torch.is_grad_enabled() else None)
+        out = self._route_so(s, o, p)
+        return super().score_so(s, o, p) if out is None else out
 
     # filtered top-k link prediction (kge_topk): score_sp / score_po + the masking of _filter_and_rank + torch.topk
     def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
         """`filters`: the sets of kge_amd.model.predict_filters (the reciprocal wrapper looks its subjects up under the
-        ORIGINAL relation and scores under the reciprocal one)."""
+        ORIGINAL relation and scores under the reciprocal one).  A family without kge_topk composes score_sp /
+        score_po with topk_composed."""
         with torch.no_grad():
-            if self._fused():
+            if "topk" in self.family.kernels and self._fused():
                 return engine.topk(self._rank_tables(), direction, a, p, k, filters, keep)
             scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
             return topk_composed(scores, k, filters, keep)
@@ -367,72 +346,33 @@ class _FusedScoring:
         """(values [n, k] float32, ids [n, k] int64): the k best objects of (s_i, p_i, ?), the known answers of
         `filter_index` (a kge_amd.eval.FilterIndex) left out except keep[i]; descending score, equal scores by
         ascending entity id, (-inf, -1) where fewer than k entities are left (kge_amd.model.KgeModel.predict_o)."""
-        return self._predict("sp_", s, p, k, predict_filters(filter_index, "sp_", s, p, self._w()[0].device), keep)
+        dev = self.get_s_embedder()._embeddings.weight.device
+        return self._predict("sp_", s, p, k, predict_filters(filter_index, "sp_", s, p, dev), keep)
 
     def predict_s(self, p: Tensor, o: Tensor, k: int, filter_index=None, keep: Tensor = None):
-        return self._predict("_po", o, p, k, predict_filters(filter_index, "_po", o, p, self._w()[0].device), keep)
+        dev = self.get_s_embedder()._embeddings.weight.device
+        return self._predict("_po", o, p, k, predict_filters(filter_index, "_po", o, p, dev), keep)
 
-    # 1vsAll loss fused with the scoring (HipTrainingJob1vsAll; kge_ce_fwd / kge_ce_bwd)
-    def _ce_tables(self):
-        if not self._fused() or self._scorer.name not in ("complex", "distmult"):
-            return None
-        ent, rel = self._w()
-        t = self._fwd_tables()
-        if t is None and ent.dtype == torch.bfloat16:
-            t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
-        return t if (t is not None and ent.is_cuda and engine.ce_supported(t)) else None
-
+    # The fused losses (kge_amd.model.FusedRoutes: _ce_tables, _ce_dist_tables, _ce_f32_tables) and their switches:
     # `hip_1vsAll.fused_dist_loss: true` (set by HipTrainingJob1vsAll; false by default): the 1vsAll loss of hip_transe /
     # hip_rotate on float32 tables without an [n, E] matrix (kge_ce_dist_fwd / kge_ce_dist_bwd).
     # `hip_KvsAll.fused_dist_loss: true` (set by HipTrainingJobKvsAll): the same for the KvsAll kl and bce losses without
     # label smoothing (kge_kl_dist_* / kge_bce_dist_*); also the bce loss under hip_1vsAll.
-    _fused_dist_loss = False
-
-    def _ce_dist_tables(self):
-        """float32 tables for the distance scorers' fused loss, or None (the composed path): the option on, TransE /
-        RotatE with l_norm 1 or 2, `_fused()` (plain lookup embedders, no active dropout, parameters on a GPU)."""
-        if not self._fused_dist_loss or not self._fused() or self._scorer.name not in ("transe", "rotate"):
-            return None
-        ent, rel = self._w()
-        if not ent.is_cuda or ent.dtype != torch.float32 or self._scorer._norm not in (1.0, 2.0):
-            return None
-        t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
-        return t if engine.ce_dist_supported(t) else None
-
     # `hip_1vsAll.fused_f32_loss: true` (set by HipTrainingJob1vsAll; false by default): the 1vsAll kl loss of hip_complex /
     # hip_distmult scoring in float32 without an [n, E] matrix (kge_ce_f32_fwd / kge_ce_f32_bwd).
     # `hip_KvsAll.fused_f32_loss: true` (set by HipTrainingJobKvsAll): the same for the KvsAll kl and bce losses, WITH
     # label smoothing -- these scores are linear in the target row (kge_kl_f32_* / kge_bce_f32_*).
-    _fused_f32_loss = False
-
-    def _ce_f32_tables(self):
-        """float32 tables for the fused loss of ComplEx / DistMult, or None (the composed path): the option on, float32
-        parameters scored in float32 (no `score_dtype: bfloat16` copies), `_fused()` (plain lookup embedders, no active
-        dropout, parameters on a GPU), a layout kge_ce_f32_workspace_bytes takes (dim % 8 == 0)."""
-        if not self._fused_f32_loss or not self._fused() or self._scorer.name not in ("complex", "distmult"):
-            return None
-        ent, rel = self._w()
-        if ent.dtype != torch.float32 or self._fwd_tables() is not None:  # (`_fused()`: the parameters are on a GPU)
-            return None
-        t = engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
-        return t if engine.ce_f32_supported(t) else None
 
     def _rank_tables(self):
         """The tables HipEntityRankingJob counts on (kge_score_rank_sp_po: scoring + _filter_and_rank counts in one
         kernel) -- the ones score_sp_po scores on under no_grad, so that fused and two-step counts agree bit for bit:
         the bf16 copies under `score_dtype: bfloat16`, else the parameters themselves (float32: every scorer).  None:
-        no fused gather (dropout active, embedders that are not plain lookup tables, job.device cpu)."""
-        if not self._fused():
+        no fused gather (dropout active, embedders that are not plain lookup tables, job.device cpu), or a family
+        without the counting kernel (hip_entity_ranking then takes the model's score_sp_po + kge_rank_counts_multi)."""
+        if "rank" not in self.family.kernels or not self._fused():
             return None
         ent, rel = self._w()
         return self._fwd_tables() or engine.Tables(self._scorer.name, ent.detach(), rel.detach(), self._scorer._norm)
-
-    def _fused_rows(self, kind: str, direction: str, a: Tensor, p: Tensor, labels: tuple, eps: float = 0.0, bf16=None):
-        """kge_amd.model.fused_loss_rows on this model's tables ("sp": a = s; "po": a = o): the loss rows, or None if no
-        fused path applies."""
-        scorer = self._scorer  # (one Module.__getattr__, not two)
-        return fused_loss_rows(kind, direction, scorer.name, scorer._norm, self._w, a, p, labels, eps,
-                               bf16 or self._ce_tables, self._ce_dist_tables, self._ce_f32_tables)
 
     def _ce_rows(self, direction: str, a: Tensor, p: Tensor, label: Tensor):
         t = self._ce_tables()
@@ -451,28 +391,25 @@ class _FusedScoring:
 
     def loss_sp_po(self, s: Tensor, p: Tensor, o: Tensor) -> Tensor:
         """[2n] loss_sp rows then loss_po rows from one pass over the batch; None if not applicable."""
-        t = self._ce_tables()
-        if t is None:
-            if self._dropout_only() is None:
-                if self._ce_dist_tables() is None and self._ce_f32_tables() is None:
-                    return None
-                return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))  # (float32 tables: one-sided calls)
-            # independent masks per direction, as the reference's two score_* calls draw them
-            return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))
-        ent, rel = self._w()
-        return _FusedCE2.apply(ent, rel, s, p, o, t)
+        rows = self._route_ce2(s, p, o)
+        if rows is not None:
+            return rows
+        if self._dropout_only() is None and self._ce_dist_tables() is None and self._ce_f32_tables() is None:
+            return None
+        # the one-sided calls: float32 tables, or dropout with independent masks per direction, as the reference's two
+        # score_* calls draw them
+        return torch.cat((self.loss_sp(s, p, o), self.loss_po(p, o, s)))
 
     def loss_sp_po_sum(self, s: Tensor, p: Tensor, o: Tensor, scale=None) -> Tensor:
         """0-d: scale * loss_sp_po(s, p, o).sum(), summed and back-propagated inside the library's launches
         (kge_amd.model._FusedCE2Sum; the step HipTrainingJob1vsAll captures); None if not applicable."""
-        t = self._ce_tables()
-        if t is None:
-            rows = self.loss_sp_po(s, p, o)
-            if rows is None:
-                return None
-            return rows.sum() if scale is None else rows.sum() * scale
-        ent, rel = self._w()
-        return _FusedCE2Sum.apply(ent, rel, s, p, o, t, scale)
+        total = self._route_ce2_sum(s, p, o, scale)
+        if total is not None:
+            return total
+        rows = self.loss_sp_po(s, p, o)
+        if rows is None:
+            return None
+        return rows.sum() if scale is None else rows.sum() * scale
 
     def kl_loss_sp(self, s: Tensor, p: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
                    label_smoothing: float = 0.0) -> Tensor:
@@ -501,19 +438,15 @@ class _FusedScoring:
         """(loss rows of the sp_ queries, loss rows of the _po queries) of a KvsAll subbatch -- or, with `sum_scale`,
         the 0-d sum_scale * (sum of all rows) -- with ONE backward for both types (kge_amd.model._FusedMultiLabel2: no
         label smoothing); None if the fused path does not apply."""
-        t = self._ce_tables()
-        if t is None:
-            return None
-        ent, rel = self._w()
-        return _FusedMultiLabel2.apply(kind, float(offset), ent, rel, s, p_sp, rowptr_sp, col_sp, o, p_po, rowptr_po,
-                                       col_po, t, sum_scale)
+        return self._route_multilabel2(kind, offset, (s, p_sp, rowptr_sp, col_sp), (o, p_po, rowptr_po, col_po),
+                                       sum_scale)
 
     def score_sp_po(self, s: Tensor, p: Tensor, o: Tensor, entity_subset: Tensor = None) -> Tensor:
         if not self._fused():
             return super().score_sp_po(s, p, o, entity_subset)
-        ng = self._no_grad_call()
-        if ng is not None:
-            return engine.score_sp_po(ng[0], s, p, o, self._targets(entity_subset), flags=ng[1])
+        if self._table_call(p):
+            t, flags = self._no_grad_call()
+            return engine.score_sp_po(t, s, p, o, self._targets(entity_subset), flags=flags)
         return torch.cat((self.score_sp(s, p, entity_subset), self.score_po(p, o, entity_subset)), dim=1)
 
 
@@ -545,7 +478,9 @@ class HipTransH(_FusedScoring, _RefTransH):
     transh.py:88-106 with the HIP scorer; `penalty` (the soft constraints, transh.py:108-142) is the reference's.
     float32 tables, l_norm 1 or 2.  Entry points without a TransH kernel are never taken: predict_o / predict_s compose
     score_sp / score_po with topk_composed, shared negative samples go back to the sampler's own score, the evaluation
-    job counts on the stored score matrix, and the options that select such a kernel are refused by name."""
+    job counts on the stored score matrix, and the options that select such a kernel are refused by name
+    (kge_amd.model.FAMILIES says which kernels a family has; _FusedScoring acts on it)."""
+    family = FAMILIES["transh"]
 
     def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
         self._init_configuration(config, configuration_key)
@@ -561,29 +496,6 @@ class HipTransH(_FusedScoring, _RefTransH):
     def _fused(self) -> bool:
         return super()._fused() and self._w()[0].dtype == torch.float32
 
-    def __setattr__(self, name, value):
-        # hip_1vsAll / hip_KvsAll switch their fused losses on by setting these attributes on the model
-        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
-            raise ValueError("hip_transh: {} is not supported (no TransH kernel behind the fused losses)".format(
-                name.lstrip("_")))
-        super().__setattr__(name, value)
-
-    def set_touched_rows(self, pair, rel_pair=None):
-        if pair is not None:
-            raise ValueError("hip_transh: touched_rows is not supported")
-        self._touched_rows = None
-
-    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
-        return None  # (no kge_score_neg_shared kernel: the job calls the sampler's own score)
-
-    def _rank_tables(self):
-        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
-
-    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
-        with torch.no_grad():
-            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
-            return topk_composed(scores, k, filters, keep)
-
 
 class HipRescal(_FusedScoring, _RefRescal):
     """`model: hip_rescal`: kge/model/rescal.py with score_spo / score_sp / score_po / score_sp_po and the negative-
@@ -592,6 +504,7 @@ class HipRescal(_FusedScoring, _RefRescal):
     tables, entity dim <= 256.  Entry points without a RESCAL kernel are never taken: predict_o / predict_s compose
     score_sp / score_po with topk_composed, shared negative samples go back to the sampler's own score, the evaluation
     job counts on the stored score matrix, and the options that select such a kernel are refused by name."""
+    family = FAMILIES["rescal"]
 
     def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
         self._init_configuration(config, configuration_key)
@@ -602,29 +515,6 @@ class HipRescal(_FusedScoring, _RefRescal):
         w = self._w()[0]
         return super()._fused() and w.dtype == torch.float32 and w.shape[1] <= engine.RESCAL_MAX_DIM
 
-    def __setattr__(self, name, value):
-        # hip_1vsAll / hip_KvsAll switch their fused losses on by setting these attributes on the model
-        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
-            raise ValueError("hip_rescal: {} is not supported (no RESCAL kernel behind the fused losses)".format(
-                name.lstrip("_")))
-        super().__setattr__(name, value)
-
-    def set_touched_rows(self, pair, rel_pair=None):
-        if pair is not None:
-            raise ValueError("hip_rescal: touched_rows is not supported")
-        self._touched_rows = None
-
-    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
-        return None  # (no kge_score_neg_shared kernel: the job calls the sampler's own score)
-
-    def _rank_tables(self):
-        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
-
-    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
-        with torch.no_grad():
-            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
-            return topk_composed(scores, k, filters, keep)
-
 
 class HipRelationalTucker3(Tucker3Routes, _FusedScoring, _RefRelationalTucker3):
     """`model: hip_relational_tucker3`: kge/model/relational_tucker3.py -- RESCAL whose mixing matrices are projected
@@ -634,6 +524,7 @@ class HipRelationalTucker3(Tucker3Routes, _FusedScoring, _RefRelationalTucker3):
     classes (checkpoints and `penalty` are the reference's).  With a recorded gradient the relation rows come by the
     routes of kge_amd.model.Tucker3Routes ("all" when R <= n, else "batch"); without one the projected table is cached
     until a parameter changes, unless it exceeds `projected_table_max_bytes` (then the batch's rows are projected).  Entry points without a RESCAL kernel are never taken, as for hip_rescal."""
+    family = FAMILIES["relational_tucker3"]
 
     def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
         from kge.misc import round_to_points
@@ -674,81 +565,9 @@ class HipRelationalTucker3(Tucker3Routes, _FusedScoring, _RefRelationalTucker3):
         """(entity table, projected relation table [R, d^2]): what the RESCAL paths of _FusedScoring take."""
         return self.get_s_embedder()._embeddings.weight, self.projected_table()
 
-    def __setattr__(self, name, value):
-        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
-            raise ValueError("hip_relational_tucker3: {} is not supported (no RESCAL kernel behind the fused "
-                             "losses)".format(name.lstrip("_")))
-        super().__setattr__(name, value)
-
-    def set_touched_rows(self, pair, rel_pair=None):
-        if pair is not None:
-            raise ValueError("hip_relational_tucker3: touched_rows is not supported")
-        self._touched_rows = None
-
-    def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
-        return None  # (no kge_score_neg_shared kernel: the job calls the sampler's own score)
-
-    def _rank_tables(self):
-        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
-
-    def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
-        with torch.no_grad():
-            scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
-            return topk_composed(scores, k, filters, keep)
-
-    def predict_o(self, s: Tensor, p: Tensor, k: int, filter_index=None, keep: Tensor = None):
-        dev = self.get_s_embedder()._embeddings.weight.device
-        return self._predict("sp_", s, p, k, predict_filters(filter_index, "sp_", s, p, dev), keep)
-
-    def predict_s(self, p: Tensor, o: Tensor, k: int, filter_index=None, keep: Tensor = None):
-        dev = self.get_s_embedder()._embeddings.weight.device
-        return self._predict("_po", o, p, k, predict_filters(filter_index, "_po", o, p, dev), keep)
-
-    # -- with a recorded gradient: the routes (without one, _FusedScoring's calls on `_w()`: the cached table)
-    def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
-        if not self._fused():
-            return super().score_spo(s, p, o, direction)
-        rel, p2, rows = self._rel(p)
-        return _ScoreSPO.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, None,
-                               self._grouped())
-
-    def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor):
-        if not self._fused() or slot not in (0, 2):
-            return None
-        rel, p2, rows = self._rel(p)
-        return _ScoreNeg.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, int(slot), neg,
-                               None, self._grouped())
-
-    def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None):
-        if not self._fused():
-            return None
-        rel, p2, rows = self._rel(p)
-        return _ScoreNegBlocks.apply("rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, s, p2, o, neg_s,
-                                     neg_o, None, self._grouped())
-
     def _table_call(self, p: Tensor) -> bool:
-        """_FusedScoring's calls on `_w()` (the cached table, range targets, padded rows): no fused gather, or no gradient
-        recorded and the "all" route (the table within `projected_table_max_bytes`)"""
-        return not self._fused() or (not torch.is_grad_enabled() and self.route(p.numel()) == "all")
-
-    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
-        if self._table_call(p):
-            return super().score_sp(s, p, o)
-        rel, p2, rows = self._rel(p)
-        return _ScorePairs.apply("rescal", 1.0, "sp", self.get_s_embedder()._embeddings.weight, rel, s, p2, o, None,
-                                 self._padded(), rows)
-
-    def score_po(self, p: Tensor, o: Tensor, s: Tensor = None) -> Tensor:
-        if self._table_call(p):
-            return super().score_po(p, o, s)
-        rel, p2, rows = self._rel(p)
-        return _ScorePairs.apply("rescal", 1.0, "po", self.get_s_embedder()._embeddings.weight, rel, o, p2, s, None,
-                                 self._padded(), rows)
-
-    def score_sp_po(self, s: Tensor, p: Tensor, o: Tensor, entity_subset: Tensor = None) -> Tensor:
-        if self._table_call(p):
-            return super().score_sp_po(s, p, o, entity_subset)
-        return torch.cat((self.score_sp(s, p, entity_subset), self.score_po(p, o, entity_subset)), dim=1)
+        """the cached table: no gradient recorded and the "all" route (the table within `projected_table_max_bytes`)"""
+        return not torch.is_grad_enabled() and (not self._fused() or self.route(p.numel()) == "all")
 
 
 class HipConvEScorer(ConveNetOps, _RefConvEScorer):
@@ -766,6 +585,7 @@ class HipConvE(ConveRoutes, _FusedScoring, _RefConvE):
     gradient, torch operations with autograd otherwise.  The constructor repeats conve.py:107-135 (the +1 dimension
     hack) with the HIP scorer.  Use it as hip_reciprocal_relations_model.base_model.type: score_po, score_sp_po and the
     other directions raise the reference's errors.  Options without a ConvE kernel are refused by name."""
+    family = FAMILIES["conve"]
 
     def __init__(self, config: Config, dataset: Dataset, configuration_key=None, init_for_load_only=False):
         self._init_configuration(config, configuration_key)
@@ -817,18 +637,6 @@ class HipConvE(ConveRoutes, _FusedScoring, _RefConvE):
     def score_sp_po(self, s: Tensor, p: Tensor, o: Tensor, entity_subset: Tensor = None) -> Tensor:
         return KgeModel.score_sp_po(self, s, p, o, entity_subset)  # (likewise)
 
-    def __setattr__(self, name, value):
-        # hip_1vsAll / hip_KvsAll switch their fused losses on by setting these attributes on the model
-        if name in ("_fused_dist_loss", "_fused_f32_loss") and value:
-            raise ValueError("hip_conve: {} is not supported (no ConvE kernel behind the fused losses)".format(
-                name.lstrip("_")))
-        super().__setattr__(name, value)
-
-    def set_touched_rows(self, pair, rel_pair=None):
-        if pair is not None:
-            raise ValueError("hip_conve: touched_rows is not supported")
-        self._touched_rows = None
-
     def score_neg(self, s, p, o, slot, neg):
         raise ValueError("hip_conve: negative-sampling blocks (hip_negative_sampling's score_neg) are not supported; "
                          "use train.type: negative_sampling")
@@ -840,21 +648,6 @@ class HipConvE(ConveRoutes, _FusedScoring, _RefConvE):
     def score_neg_blocks(self, s, p, o, neg_s=None, neg_o=None):
         raise ValueError("hip_conve: negative-sampling blocks (hip_negative_sampling's score_neg_blocks) are not "
                          "supported; use train.type: negative_sampling")
-
-    def _ce_tables(self):
-        return None
-
-    def _ce_dist_tables(self):
-        return None
-
-    def _ce_f32_tables(self):
-        return None
-
-    def _dropout_only(self):
-        return None
-
-    def _rank_tables(self):
-        return None  # (no counting kernel: hip_entity_ranking takes the model's score_sp_po + kge_rank_counts_multi)
 
     def _predict(self, direction: str, a: Tensor, p: Tensor, k: int, filters, keep):
         if direction != "sp_":

@@ -10,6 +10,7 @@ torch.nn.Modules; `kge_amd.libkge_plugin` wraps the same kernels in subclasses o
 Parameter names/shapes equal the reference's (`_entity_embedder._embeddings.weight` [E,d],
 `_relation_embedder._embeddings.weight` [R,d_r]) so state_dicts / checkpoints interoperate.
 """
+import collections
 import math
 
 import torch
@@ -171,13 +172,168 @@ class RescalScorer(RelationalScorer):
         return out.view(n, -1)
 
 
-# scorers whose predictions, shared samples and evaluation take the composed paths (no kge_topk / kge_score_neg_shared /
-# fused-loss kernel behind them)
-_COMPOSED_ONLY = ("transh", "rescal", "conve")
+# Which optional kernels a model family has next to its scoring kernels: the one statement that the classes below and
+# the plugin's hip_* models both read (`family`).  An entry point whose kernel is missing is composed, handed back or
+# refused by name -- where, and in which words, is each surface's own.
+#   neg_shared      kge_score_neg_shared behind score_neg_shared
+#   shared_samples  score_neg on engine.shared_samples stands in where kge_score_neg_shared does not apply
+#   topk            kge_topk behind predict_o / predict_s
+#   rank            kge_score_rank_sp_po behind the plugin's `_rank_tables`
+#   touched         the touched-row backward behind set_touched_rows
+#   dense_loss      the dense-row losses behind fused_dist_loss / fused_f32_loss
+# name: the family's key in MODELS ("hip_" + name: the plugin's model); kernel: what messages call its kernels
+Family = collections.namedtuple("Family", "name kernel kernels")
+ALL_KERNELS = frozenset(("neg_shared", "shared_samples", "topk", "rank", "touched", "dense_loss"))
+FAMILIES = {"transh": Family("transh", "TransH", frozenset(("shared_samples",))),
+            "rescal": Family("rescal", "RESCAL", frozenset()),
+            "relational_tucker3": Family("relational_tucker3", "RESCAL", frozenset()),
+            "conve": Family("conve", "ConvE", frozenset())}
 
 
-class KgeModel(torch.nn.Module):
-    """Index-level API of kge/model/kge_model.py:587-789 on the fused kernels."""
+class FusedRoutes:
+    """Which fused autograd node a model call takes: the one definition for KgeModel below and for the plugin's
+    _FusedScoring.  Every `_route_*` returns the node's result, or None where no fused route applies -- KgeModel then
+    composes the result in torch, the plugin calls the reference's method or hands the None to its job.  The host class
+    says where the tensors live and what its options are:
+      _w()                (entity weight, relation weight)
+      _fused()            both embedders are lookups the kernels may gather from
+      _touched_pair()     what set_touched_rows left for the backward, or None
+      _grouped()          the relation-grouped RESCAL backward is on
+      _dropout_triple()   (p_entity, p_relation) where embedder dropout goes inside the triple-wise kernels, else None
+      _next_dropout(probs)  the engine.Dropout record of the next such call
+      _fwd_tables()       the bf16 copies that float32 parameters are scored on, or None
+      _padded()           score_sp / score_po return the view of a matrix with sector-aligned rows
+      _fused_dist_loss, _fused_f32_loss  the switches of the float32 dense-row losses"""
+    family = Family(None, None, ALL_KERNELS)
+    _fused_dist_loss = False
+    _fused_f32_loss = False
+
+    def _operands(self, p: Tensor, project: str = None):
+        """(scorer name, l_norm, entity table, relation table, relation index, rel_rows, touched pair) of a node for the
+        batch's relations p (Tucker3Routes puts the projected rows in the relation table's place)."""
+        ent, rel = self._w()
+        scorer = self._scorer  # (one Module.__getattr__, not two)
+        return scorer.name, scorer._norm, ent, rel, p, False, self._touched_pair()
+
+    def _route_spo(self, s, p, o, project=None):
+        if self._fused():
+            name, norm, ent, rel, p, _, touched = self._operands(p, project)
+            return _ScoreSPO.apply(name, norm, ent, rel, s, p, o, touched, self._grouped())
+        probs = self._dropout_triple()
+        if probs is None:
+            return None
+        name, norm, ent, rel, p, _, touched = self._operands(p, project)
+        return _ScoreSPODropout.apply(name, norm, ent, rel, s, p, o, self._next_dropout(probs), touched)
+
+    def _route_neg(self, s, p, o, slot, neg, project=None):
+        if slot not in (0, 2):
+            return None
+        if self._fused():
+            name, norm, ent, rel, p, _, touched = self._operands(p, project)
+            return _ScoreNeg.apply(name, norm, ent, rel, s, p, o, int(slot), neg, touched, self._grouped())
+        probs = self._dropout_triple()
+        if probs is None:
+            return None
+        name, norm, ent, rel, p, _, touched = self._operands(p, project)
+        return _ScoreNegDropout.apply(name, norm, ent, rel, s, p, o, int(slot), neg, self._next_dropout(probs), touched)
+
+    def _route_neg_shared(self, s, p, o, slot, unique, drop, repeat):
+        if "neg_shared" not in self.family.kernels or slot not in (0, 2) or not self._fused():
+            return None
+        ent, rel = self._w()
+        if not neg_shared_fusable(ent, s.numel()):
+            return None
+        scorer = self._scorer
+        return _ScoreNegShared.apply(scorer.name, scorer._norm, ent, rel, s, p, o, int(slot), unique, drop, repeat)
+
+    def _route_neg_blocks(self, s, p, o, neg_s, neg_o, project=None):
+        if not self._fused():
+            return None
+        name, norm, ent, rel, p, _, touched = self._operands(p, project)
+        if not neg_blocks_fusable(ent, rel):
+            return None
+        return _ScoreNegBlocks.apply(name, norm, ent, rel, s, p, o, neg_s, neg_o, touched, self._grouped())
+
+    def _route_pairs(self, direction: str, a, p, targets, project=None):
+        """score_sp ("sp": a = s) / score_po ("po": a = o) against `targets` (None: all entities)"""
+        if not self._fused():
+            return None
+        name, norm, ent, rel, p, rel_rows, _ = self._operands(p, project)
+        return _ScorePairs.apply(name, norm, direction, ent, rel, a, p, targets, self._fwd_tables(), self._padded(),
+                                 rel_rows)
+
+    def _route_so(self, s, o, p):
+        if not self._fused():
+            return None
+        ent, rel = self._w()
+        scorer = self._scorer
+        if not score_so_fusable(scorer.name, ent, rel, s.numel()):
+            return None
+        return _ScoreSO.apply(scorer.name, scorer._norm, ent, rel, s, o, p,
+                              self._touched_pair() if torch.is_grad_enabled() else None)
+
+    # -- the tables of the three families of fused losses, or None (then the loss is composed from score_sp / score_po)
+    def _ce_tables(self):
+        """bf16 tables (ComplEx / DistMult: the parameters, or their bf16 copies in mixed precision), pure lookups, on a
+        GPU, a layout kge_ce_workspace_bytes takes."""
+        scorer = self._scorer
+        if not self._fused() or scorer.name not in ("complex", "distmult"):
+            return None
+        ent, rel = self._w()
+        t = self._fwd_tables()
+        if t is None and ent.dtype == torch.bfloat16:
+            t = engine.Tables(scorer.name, ent.detach(), rel.detach(), scorer._norm)
+        return t if (t is not None and ent.is_cuda and engine.ce_supported(t)) else None
+
+    def _ce_dist_tables(self):
+        """float32 tables for the distance scorers' fused loss (`_fused_dist_loss`): TransE / RotatE, l_norm 1 or 2, pure
+        lookups, parameters on a GPU."""
+        scorer = self._scorer
+        if not self._fused_dist_loss or not self._fused() or scorer.name not in ("transe", "rotate"):
+            return None
+        ent, rel = self._w()
+        if not ent.is_cuda or ent.dtype != torch.float32 or scorer._norm not in (1.0, 2.0):
+            return None
+        t = engine.Tables(scorer.name, ent.detach(), rel.detach(), scorer._norm)
+        return t if engine.ce_dist_supported(t) else None
+
+    def _ce_f32_tables(self):
+        """float32 tables for the fused loss of ComplEx / DistMult (`_fused_f32_loss`): float32 parameters scored in
+        float32 (no bf16 copies), pure lookups on a GPU (`_fused()` says so in the plugin, KgeModel asks the table), a
+        layout kge_ce_f32_workspace_bytes takes (dim % 8 == 0)."""
+        scorer = self._scorer
+        if not self._fused_f32_loss or not self._fused() or scorer.name not in ("complex", "distmult"):
+            return None
+        ent, rel = self._w()
+        if ent.dtype != torch.float32 or self._fwd_tables() is not None:
+            return None
+        t = engine.Tables(scorer.name, ent.detach(), rel.detach(), scorer._norm)
+        return t if engine.ce_f32_supported(t) else None
+
+    def _fused_rows(self, kind: str, direction: str, a: Tensor, p: Tensor, labels: tuple, eps: float = 0.0, bf16=None):
+        """fused_loss_rows on this model's tables ("sp": a = s; "po": a = o): the loss rows, or None if no family of fused
+        losses applies.  bf16: what to ask in `_ce_tables`' place (a caller that has asked it already)."""
+        scorer = self._scorer  # (one Module.__getattr__, not two)
+        return fused_loss_rows(kind, direction, scorer.name, scorer._norm, self._w, a, p, labels, eps,
+                               bf16 or self._ce_tables, self._ce_dist_tables, self._ce_f32_tables)
+
+    def _route_ce2(self, s, p, o):
+        t = self._ce_tables()
+        return None if t is None else _FusedCE2.apply(*self._w(), s, p, o, t)
+
+    def _route_ce2_sum(self, s, p, o, scale):
+        t = self._ce_tables()
+        return None if t is None else _FusedCE2Sum.apply(*self._w(), s, p, o, t, scale)
+
+    def _route_multilabel2(self, kind, offset, sp: tuple, po: tuple, sum_scale):
+        """sp = (s, p_sp, rowptr_sp, col_sp), po = (o, p_po, rowptr_po, col_po); no label smoothing"""
+        t = self._ce_tables()
+        return None if t is None else _FusedMultiLabel2.apply(kind, float(offset), *self._w(), *sp, *po, t, sum_scale)
+
+
+class KgeModel(FusedRoutes, torch.nn.Module):
+    """Index-level API of kge/model/kge_model.py:587-789 on the fused kernels: FusedRoutes' nodes, and where none
+    applies the same result composed from the embedders and the scorer."""
 
     scorer_cls = None
 
@@ -258,7 +414,7 @@ class KgeModel(torch.nn.Module):
         (DESIGN.md section 25).  Shared samples (score_neg_shared) keep the dense gradient: do not mix them with it.
         `rel_pair` = kge_amd.optim.SparseAdam.enable_touched_rows(relation table): the relation gradient goes the same
         way, the batch's `p` rows marked; None: a fresh dense relation gradient per node."""
-        if pair is not None and self.scorer_cls in (TransHScorer, RescalScorer):
+        if pair is not None and "touched" not in self.family.kernels:
             raise ValueError("{}: {}touched_rows is not supported".format(type(self).__name__,
                                                                           "grouped: " if self.grouped else ""))
         if pair is None and rel_pair is not None:
@@ -291,8 +447,32 @@ class KgeModel(torch.nn.Module):
         return self._shadow.tables(self._scorer.name, self._entity_embedder.weight,
                                    self._relation_embedder.weight, self._scorer._norm)
 
+    # -- FusedRoutes' hooks
+    def _w(self):
+        return self._entity_embedder.weight, self._relation_embedder.weight
+
     def _fused(self) -> bool:
         return self._entity_embedder.fused_ok() and self._relation_embedder.fused_ok()
+
+    def _touched_pair(self):
+        return self._touched_rows
+
+    def _grouped(self) -> bool:
+        return self.grouped
+
+    def _next_dropout(self, probs):
+        return self._dropout_clock.next(*probs)
+
+    def _padded(self) -> bool:
+        return self.padded_scores and not torch.is_grad_enabled()
+
+    def _ce_f32_tables(self):
+        return super()._ce_f32_tables() if self._entity_embedder.weight.is_cuda else None
+
+    fused_dist_loss = property(lambda self: self._fused_dist_loss,
+                               lambda self, on: setattr(self, "_fused_dist_loss", bool(on)))
+    fused_f32_loss = property(lambda self: self._fused_f32_loss,
+                              lambda self, on: setattr(self, "_fused_f32_loss", bool(on)))
 
     @property
     def dropout_seed(self) -> int:
@@ -313,31 +493,20 @@ class KgeModel(torch.nn.Module):
             return None
         return pe, pr
 
-    # -- scoring
-    def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
-        if self._fused():
-            return _ScoreSPO.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                   self._relation_embedder.weight, s, p, o, self._touched_rows, self.grouped)
-        dp = self._dropout_triple()
-        if dp is not None:
-            return _ScoreSPODropout.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                          self._relation_embedder.weight, s, p, o, self._dropout_clock.next(*dp),
-                                          self._touched_rows)
+    # -- scoring (`project`: RelationalTucker3's route, per call)
+    def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None, project=None) -> Tensor:
+        out = self._route_spo(s, p, o, project)
+        if out is not None:
+            return out
         se, pe, oe = self._entity_embedder.embed(s), self._relation_embedder.embed(p), self._entity_embedder.embed(o)
         return self._scorer.score_emb(se, pe, oe, combine="spo").view(-1)
 
-    def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor) -> Tensor:
+    def score_neg(self, s: Tensor, p: Tensor, o: Tensor, slot: int, neg: Tensor, project=None) -> Tensor:
         """[n, K]: score of triple i with slot (0 = s, 2 = o) replaced by neg[i, k]; equals
         BatchNegativeSample.score with implementation "triple" (kge/util/sampler.py:291-306)."""
-        if self._fused() and slot in (0, 2):
-            return _ScoreNeg.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                   self._relation_embedder.weight, s, p, o, int(slot), neg, self._touched_rows,
-                                   self.grouped)
-        dp = self._dropout_triple() if slot in (0, 2) else None
-        if dp is not None:
-            return _ScoreNegDropout.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                          self._relation_embedder.weight, s, p, o, int(slot), neg,
-                                          self._dropout_clock.next(*dp), self._touched_rows)
+        out = self._route_neg(s, p, o, slot, neg, project)
+        if out is not None:
+            return out
         K = neg.shape[1]
         tr = [x.reshape(-1).long().repeat_interleave(K) for x in (s, p, o)]
         tr[slot] = neg.reshape(-1).long()
@@ -348,23 +517,22 @@ class KgeModel(torch.nn.Module):
         """[n, K]: score of triple i with slot (0 = s, 2 = o) replaced by the shared sample (unique, drop, repeat) --
         NaiveSharedNegativeSample.score / DefaultSharedNegativeSample.score (kge/util/sampler.py:428-463, 537-578);
         equals score_neg on engine.shared_samples(unique, drop, repeat, n)."""
-        if self.scorer_cls is RescalScorer:  # no kge_score_neg_shared kernel, and none composed in its place
-            raise ValueError("Rescal: {}shared negative samples (score_neg_shared) are not supported; use "
-                             "score_neg".format("grouped: " if self.grouped else ""))
-        if self._fused() and slot in (0, 2) and self._scorer.name not in _COMPOSED_ONLY and \
-                neg_shared_fusable(self._entity_embedder.weight, s.numel()):
-            return _ScoreNegShared.apply(self._scorer.name, self._scorer._norm, self._entity_embedder.weight,
-                                         self._relation_embedder.weight, s, p, o, int(slot), unique, drop, repeat)
+        if "shared_samples" not in self.family.kernels:  # no kge_score_neg_shared kernel, and none composed in its place
+            raise ValueError("{}: {}shared negative samples (score_neg_shared) are not supported; use "
+                             "score_neg".format(type(self).__name__, "grouped: " if self.grouped else ""))
+        out = self._route_neg_shared(s, p, o, slot, unique, drop, repeat)
+        if out is not None:
+            return out
         return self.score_neg(s, p, o, slot, engine.shared_samples(unique, drop, repeat, s.reshape(-1).numel()))
 
-    def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None):
+    def score_neg_blocks(self, s: Tensor, p: Tensor, o: Tensor, neg_s: Tensor = None, neg_o: Tensor = None,
+                         project=None):
         """(positives [n], [n, K_s] scores with the subject replaced by neg_s[i, k] or None, [n, K_o] with the object
         replaced or None): score_spo + score_neg per slot as ONE autograd node (one pair of table gradients in the
         backward); composed from the single calls where the fused node does not apply."""
-        ent, rel = self._entity_embedder.weight, self._relation_embedder.weight
-        if self._fused() and neg_blocks_fusable(ent, rel):
-            return _ScoreNegBlocks.apply(self._scorer.name, self._scorer._norm, ent, rel, s, p, o, neg_s, neg_o,
-                                         self._touched_rows, self.grouped)
+        out = self._route_neg_blocks(s, p, o, neg_s, neg_o, project)
+        if out is not None:
+            return out
         pos = self.score_spo(s, p, o)
         return (pos, None if neg_s is None else self.score_neg(s, p, o, 0, neg_s),
                 None if neg_o is None else self.score_neg(s, p, o, 2, neg_o))
@@ -373,22 +541,18 @@ class KgeModel(torch.nn.Module):
     # (engine.score_pitch) instead of a contiguous tensor: see the plugin's `padded_scores` option
     padded_scores = True
 
-    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None) -> Tensor:
-        if self._fused():
-            return _ScorePairs.apply(self._scorer.name, self._scorer._norm, "sp",
-                                     self._entity_embedder.weight,
-                                     self._relation_embedder.weight, s, p, o, self._fwd_tables(),
-                                     self.padded_scores and not torch.is_grad_enabled())
+    def score_sp(self, s: Tensor, p: Tensor, o: Tensor = None, project=None) -> Tensor:
+        out = self._route_pairs("sp", s, p, o, project)
+        if out is not None:
+            return out
         se, pe = self._entity_embedder.embed(s), self._relation_embedder.embed(p)
         oe = self._entity_embedder.embed_all() if o is None else self._entity_embedder.embed(o)
         return self._scorer.score_emb(se, pe, oe, combine="sp_")
 
-    def score_po(self, p: Tensor, o: Tensor, s: Tensor = None) -> Tensor:
-        if self._fused():
-            return _ScorePairs.apply(self._scorer.name, self._scorer._norm, "po",
-                                     self._entity_embedder.weight,
-                                     self._relation_embedder.weight, o, p, s, self._fwd_tables(),
-                                     self.padded_scores and not torch.is_grad_enabled())
+    def score_po(self, p: Tensor, o: Tensor, s: Tensor = None, project=None) -> Tensor:
+        out = self._route_pairs("po", o, p, s, project)
+        if out is not None:
+            return out
         se = self._entity_embedder.embed_all() if s is None else self._entity_embedder.embed(s)
         oe, pe = self._entity_embedder.embed(o), self._relation_embedder.embed(p)
         return self._scorer.score_emb(se, pe, oe, combine="_po")
@@ -398,9 +562,9 @@ class KgeModel(torch.nn.Module):
         with torch.no_grad():
             dev = self._entity_embedder.weight.device
             filters = predict_filters(filter_index, direction, a, p, dev)
-            if self._fused() and dev.type == "cuda" and self._scorer.name not in _COMPOSED_ONLY:
+            if self._fused() and dev.type == "cuda" and "topk" in self.family.kernels:
                 return engine.topk(self.tables(), direction, a, p, k, filters, keep)
-            # CPU parameters, dropout in training mode, TransH / RESCAL (no kge_topk kernel): the same rule on the composed scores
+            # CPU parameters, dropout in training mode, no kge_topk kernel: the same rule on the composed scores
             scores = self.score_sp(a, p) if direction == "sp_" else self.score_po(p, a)
             return topk_composed(scores, k, filters, keep)
 
@@ -415,50 +579,9 @@ class KgeModel(torch.nn.Module):
         """predict_o for the subjects of (?, p_i, o_i)."""
         return self._predict("_po", o, p, k, filter_index, keep)
 
-    # -- 1vsAll loss (SURVEY.md 8f N1): train_1vsAll.py:64-65 / 75-76 in one call
-    def _ce_tables(self):
-        """bf16 tables for the fused loss, or None (then the loss is composed from score_sp/_po)."""
-        if not self._fused() or self._scorer.name not in ("complex", "distmult"):
-            return None
-        w = self._entity_embedder.weight
-        t = self._fwd_tables()
-        if t is None and w.dtype == torch.bfloat16:
-            t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach())
-        return t if (t is not None and w.is_cuda and engine.ce_supported(t)) else None
-
-    def _ce_dist_tables(self):
-        """float32 tables for the distance scorers' fused loss (`fused_dist_loss=True`), or None (then the loss is
-        composed from score_sp / score_po): TransE / RotatE, l_norm 1 or 2, pure lookups, parameters on a GPU."""
-        if not self.fused_dist_loss or not self._fused() or self._scorer.name not in ("transe", "rotate"):
-            return None
-        w = self._entity_embedder.weight
-        if not w.is_cuda or w.dtype != torch.float32 or self._scorer._norm not in (1.0, 2.0):
-            return None
-        t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach(), self._scorer._norm)
-        return t if engine.ce_dist_supported(t) else None
-
-    def _ce_f32_tables(self):
-        """float32 tables for the fused loss of ComplEx / DistMult (`fused_f32_loss=True`), or None (then the loss is
-        composed from score_sp / score_po): float32 parameters scored in float32, pure lookups, on a GPU, a layout
-        kge_ce_f32_workspace_bytes takes."""
-        if not self.fused_f32_loss or not self._fused() or self._scorer.name not in ("complex", "distmult"):
-            return None
-        w = self._entity_embedder.weight
-        if not w.is_cuda or w.dtype != torch.float32 or self._shadow is not None:
-            return None
-        t = engine.Tables(self._scorer.name, w.detach(), self._relation_embedder.weight.detach())
-        return t if engine.ce_f32_supported(t) else None
-
-    # one method per loss, the direction an argument ("sp": a = s; "po": a = o): the fused rows where a family of
-    # fused_loss_rows applies, else composed from the scores
-    def _weights(self):
-        return self._entity_embedder.weight, self._relation_embedder.weight
-
-    def _fused_rows(self, kind: str, direction: str, a: Tensor, p: Tensor, labels: tuple, eps: float = 0.0):
-        scorer = self._scorer  # (one Module.__getattr__, not two)
-        return fused_loss_rows(kind, direction, scorer.name, scorer._norm, self._weights, a, p, labels, eps,
-                               self._ce_tables, self._ce_dist_tables, self._ce_f32_tables)
-
+    # -- 1vsAll loss (SURVEY.md 8f N1): train_1vsAll.py:64-65 / 75-76 in one call; one method per loss, the direction an
+    # argument ("sp": a = s; "po": a = o): the fused rows where a family of fused_loss_rows applies, else composed from
+    # the scores
     def _scores(self, direction: str, a: Tensor, p: Tensor) -> Tensor:
         return self.score_sp(a, p) if direction == "sp" else self.score_po(p, a)
 
@@ -486,19 +609,17 @@ class KgeModel(torch.nn.Module):
         """[2n]: loss_sp(s, p, o) followed by loss_po(p, o, s) -- both directions of a 1vsAll batch
         from one scoring launch and one pair of gradient products (train_1vsAll.py:64-81 sums and
         back-propagates the two separately)."""
-        t = self._ce_tables()
-        if t is not None:
-            return _FusedCE2.apply(self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, t)
-        return torch.cat([self.loss_sp(s, p, o), self.loss_po(p, o, s)])
+        rows = self._route_ce2(s, p, o)
+        return torch.cat([self.loss_sp(s, p, o), self.loss_po(p, o, s)]) if rows is None else rows
 
     def loss_sp_po_sum(self, s: Tensor, p: Tensor, o: Tensor, scale=None) -> Tensor:
         """0-d: scale * loss_sp_po(s, p, o).sum() -- the batch loss of TrainingJob1vsAll (train_1vsAll.py:64-82 with
         scale = 1 / batch_size) -- summed inside the loss kernels' own launches, its backward taking the upstream
         gradient and `scale` (None, a float, or a float32 device scalar) as device scalars: three launches and three
         autograd nodes fewer per step than `.sum() * scale` around loss_sp_po."""
-        t = self._ce_tables()
-        if t is not None:
-            return _FusedCE2Sum.apply(self._entity_embedder.weight, self._relation_embedder.weight, s, p, o, t, scale)
+        total = self._route_ce2_sum(s, p, o, scale)
+        if total is not None:
+            return total
         total = self.loss_sp_po(s, p, o).sum()
         return total if scale is None else total * scale
 
@@ -508,17 +629,21 @@ class KgeModel(torch.nn.Module):
 
     # -- KvsAll loss: train_KvsAll.py:274-294 with train.loss=kl
     @staticmethod
-    def _kl_composed(scores: Tensor, rowptr: Tensor, col: Tensor, label_smoothing: float = 0.0) -> Tensor:
-        """loss.py:208-213 row by row: KLDivLoss(log_softmax(scores), normalize(labels, p=1)); labels
-        smoothed as train_KvsAll.py:260-266 does."""
-        n = scores.shape[0]
+    def _dense_labels(scores: Tensor, rowptr: Tensor, col: Tensor, label_smoothing: float) -> Tensor:
+        """the multi-hot labels of the CSR (rowptr, col) as a matrix of the scores' shape, smoothed as
+        train_KvsAll.py:260-266 does"""
         cnt = (rowptr[1:] - rowptr[:-1]).to(scores.device)
-        rows = torch.repeat_interleave(torch.arange(n, device=scores.device), cnt)
+        rows = torch.repeat_interleave(torch.arange(scores.shape[0], device=scores.device), cnt)
         labels = torch.zeros_like(scores)
         labels[rows, col.to(scores.device).long()] = 1.0
         if label_smoothing > 0.0:
             labels = (1.0 - label_smoothing) * labels + 1.0 / labels.size(1)
-        y = torch.nn.functional.normalize(labels, p=1, dim=1)
+        return labels
+
+    @staticmethod
+    def _kl_composed(scores: Tensor, rowptr: Tensor, col: Tensor, label_smoothing: float = 0.0) -> Tensor:
+        """loss.py:208-213 row by row: KLDivLoss(log_softmax(scores), normalize(labels, p=1))."""
+        y = torch.nn.functional.normalize(KgeModel._dense_labels(scores, rowptr, col, label_smoothing), p=1, dim=1)
         return torch.nn.functional.kl_div(torch.log_softmax(scores, dim=1), y, reduction="none").sum(dim=1)
 
     def kl_loss_sp(self, s: Tensor, p: Tensor, lbl_rowptr: Tensor, lbl_col: Tensor,
@@ -538,10 +663,12 @@ class KgeModel(torch.nn.Module):
         "kl" or "bce": kl_loss_sp + kl_loss_po (bce_loss_sp + bce_loss_po) with ONE backward for both types where the
         fused path applies (_FusedMultiLabel2; no label smoothing), else the two per-type calls.  `sum_scale` given:
         the 0-d batch loss sum_scale * (sum of all rows) instead of the two row vectors."""
-        t = self._ce_tables()
-        if t is not None and label_smoothing == 0.0:
-            return _FusedMultiLabel2.apply(kind, float(offset), self._entity_embedder.weight, self._relation_embedder.weight,
-                                           s, p_sp, rowptr_sp, col_sp, o, p_po, rowptr_po, col_po, t, sum_scale)
+        both = None
+        if label_smoothing == 0.0:
+            both = self._route_multilabel2(kind, offset, (s, p_sp, rowptr_sp, col_sp), (o, p_po, rowptr_po, col_po),
+                                           sum_scale)
+        if both is not None:
+            return both
         if kind == "kl":
             both = (self.kl_loss_sp(s, p_sp, rowptr_sp, col_sp, label_smoothing),
                     self.kl_loss_po(p_po, o, rowptr_po, col_po, label_smoothing))
@@ -554,13 +681,7 @@ class KgeModel(torch.nn.Module):
     @staticmethod
     def _bce_composed(scores: Tensor, rowptr: Tensor, col: Tensor, offset: float = 0.0,
                       label_smoothing: float = 0.0) -> Tensor:
-        n = scores.shape[0]
-        cnt = (rowptr[1:] - rowptr[:-1]).to(scores.device)
-        rows = torch.repeat_interleave(torch.arange(n, device=scores.device), cnt)
-        labels = torch.zeros_like(scores)
-        labels[rows, col.to(scores.device).long()] = 1.0
-        if label_smoothing > 0.0:
-            labels = (1.0 - label_smoothing) * labels + 1.0 / labels.size(1)
+        labels = KgeModel._dense_labels(scores, rowptr, col, label_smoothing)
         return torch.nn.functional.binary_cross_entropy_with_logits(scores + offset, labels,
                                                                      reduction="none").sum(dim=1)
 
@@ -580,10 +701,9 @@ class KgeModel(torch.nn.Module):
         """[n, R] scores of (s_i, ?, o_i) against all relations, or [n, len(p)] against the relations `p`
         (kge_model.py:727-747): kge_score_so where the lookups are plain, the parameters on a GPU and the scorer one of
         ComplEx / DistMult / TransE / RotatE; else composed as the reference does (kge_model.py:202-209)."""
-        ent, rel = self._entity_embedder.weight, self._relation_embedder.weight
-        if self.fused_score_so and self._fused() and score_so_fusable(self._scorer.name, ent, rel, s.numel()):
-            return _ScoreSO.apply(self._scorer.name, self._scorer._norm, ent, rel, s, o, p,
-                                  self._touched_rows if torch.is_grad_enabled() else None)
+        out = self._route_so(s, o, p) if self.fused_score_so else None
+        if out is not None:
+            return out
         se, oe = self._entity_embedder.embed(s), self._entity_embedder.embed(o)
         pe = self._relation_embedder.embed_all() if p is None else self._relation_embedder.embed(p)
         return self._scorer.score_emb(se, pe, oe, combine="s_o")
@@ -619,11 +739,13 @@ class RotatE(KgeModel):
 class TransH(KgeModel):
     """kge/model/transh.py:81-118: relation rows [d_r | w_r] of width 2 dim; float32, l_norm 1 or 2."""
     scorer_cls = TransHScorer
+    family = FAMILIES["transh"]
 
 
 class Rescal(KgeModel):
     """kge/model/rescal.py:55-95: relation rows are d x d mixing matrices (width dim * dim); float32, dim <= 256."""
     scorer_cls = RescalScorer
+    family = FAMILIES["rescal"]
 
 
 class Tucker3RelationEmbedder(torch.nn.Module):
@@ -740,6 +862,11 @@ class Tucker3Routes:
         B, W = self._bw()
         return tucker3_project(B, W, p.reshape(-1)), torch.arange(n, device=B.device), True
 
+    def _operands(self, p: Tensor, project: str = None):
+        """FusedRoutes' nodes are the RESCAL ones over (entity table, projected rows); no touched rows"""
+        rel, p2, rows = self._rel(p, project)
+        return "rescal", 1.0, self.get_s_embedder()._embeddings.weight, rel, p2, rows, None
+
 
 class RelationalTucker3(Tucker3Routes, KgeModel):
     """kge/model/relational_tucker3.py: RESCAL whose mixing matrices are projected from a base relation table,
@@ -747,6 +874,7 @@ class RelationalTucker3(Tucker3Routes, KgeModel):
     it is the RESCAL kernels on the projected rows (the routes: Tucker3Routes).
     `project` ("auto" | "all" | "batch", here or per call) forces a route."""
     scorer_cls = RescalScorer
+    family = FAMILIES["relational_tucker3"]
 
     def __init__(self, num_entities: int, num_relations: int, dim: int, rel_base_dim: int = 100, project: str = "auto",
                  projected_table_max_bytes: int = 1 << 30, **kw):
@@ -770,44 +898,9 @@ class RelationalTucker3(Tucker3Routes, KgeModel):
     def tables(self, flags: int = 0) -> engine.Tables:
         return engine.Tables("rescal", self._entity_embedder.weight.detach(), self.projected_table().detach(), 1.0, flags)
 
-    # -- scoring: the RESCAL autograd nodes over (ent, projected rows)
-    def score_spo(self, s, p, o, direction=None, project=None):
-        if not self._fused():
-            return super().score_spo(s, p, o, direction)
-        rel, p2, rows = self._rel(p, project)
-        return _ScoreSPO.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, None, self.grouped)
-
-    def score_neg(self, s, p, o, slot, neg, project=None):
-        if not (self._fused() and slot in (0, 2)):
-            return super().score_neg(s, p, o, slot, neg)
-        rel, p2, rows = self._rel(p, project)
-        return _ScoreNeg.apply("rescal", 1.0, self._entity_embedder.weight, rel, s, p2, o, int(slot), neg, None,
-                               self.grouped)
-
     def score_neg_shared(self, s, p, o, slot, unique, drop=None, repeat=None):
         raise ValueError("RelationalTucker3: shared negative samples (score_neg_shared) are not supported; use "
                          "score_neg")
-
-    def score_neg_blocks(self, s, p, o, neg_s=None, neg_o=None, project=None):
-        ent = self._entity_embedder.weight
-        if self._fused() and ent.is_cuda and ent.dtype == torch.float32:
-            rel, p2, rows = self._rel(p, project)
-            return _ScoreNegBlocks.apply("rescal", 1.0, ent, rel, s, p2, o, neg_s, neg_o, None, self.grouped)
-        return super().score_neg_blocks(s, p, o, neg_s, neg_o)
-
-    def score_sp(self, s, p, o=None, project=None):
-        if not self._fused():
-            return super().score_sp(s, p, o)
-        rel, p2, rows = self._rel(p, project)
-        return _ScorePairs.apply("rescal", 1.0, "sp", self._entity_embedder.weight, rel, s, p2, o, None,
-                                 self.padded_scores and not torch.is_grad_enabled(), rows)
-
-    def score_po(self, p, o, s=None, project=None):
-        if not self._fused():
-            return super().score_po(p, o, s)
-        rel, p2, rows = self._rel(p, project)
-        return _ScorePairs.apply("rescal", 1.0, "po", self._entity_embedder.weight, rel, o, p2, s, None,
-                                 self.padded_scores and not torch.is_grad_enabled(), rows)
 
     def score_sp_po(self, s, p, o, entity_subset=None, project=None):
         if self._fused() and not torch.is_grad_enabled():
@@ -989,6 +1082,7 @@ class ConvE(ConveRoutes, KgeModel):
     only -- use it under reciprocal relations, as the reference says.  The routes: ConveRoutes.  A fused training forward
     and backward of the network is not here (the follow-up)."""
     scorer_cls = ConvEScorer
+    family = FAMILIES["conve"]
 
     def __init__(self, num_entities: int, num_relations: int, dim: int, aspect_ratio=2, filter_size: int = 3,
                  padding: int = 0, feature_map_dropout: float = 0.2, projection_dropout: float = 0.3,
@@ -1017,11 +1111,6 @@ class ConvE(ConveRoutes, KgeModel):
 
     def tables(self, flags: int = 0):
         raise ValueError("ConvE: there are no kge_tables of a ConvE model (its score is not a function of three rows)")
-
-    def set_touched_rows(self, pair, rel_pair=None):
-        if pair is not None:
-            raise ValueError("ConvE: touched_rows is not supported")
-        self._touched_rows = None
 
     def score_spo(self, s: Tensor, p: Tensor, o: Tensor, direction=None) -> Tensor:
         if direction != "o":
@@ -1910,8 +1999,8 @@ def bce_fused(name: str, l_norm, direction: str, ent: Tensor, rel: Tensor, a: Te
     rows = torch.repeat_interleave(torch.arange(n, device=ent.device), cnt, output_size=col.numel())
     ar, pr = a.long()[rows], p.long()[rows]
     ent32, rel32 = ent.float(), rel.float()
-    lab = (_ScoreSPO.apply(name, l_norm, ent32, rel32, ar, pr, col) if direction == "sp"
-           else _ScoreSPO.apply(name, l_norm, ent32, rel32, col, pr, ar))
+    subj, obj = (ar, col) if direction == "sp" else (col, ar)
+    lab = _ScoreSPO.apply(name, l_norm, ent32, rel32, subj, pr, obj)
     s_lab = torch.zeros(n, dtype=torch.float32, device=ent.device).index_add(0, rows, lab.view(-1) + offset)
     s_all = _score_against_column_sum(name, l_norm, direction, ent, rel, a, p) + E * offset
     return fused + eps * s_lab - s_all / E
