@@ -135,7 +135,8 @@ typedef enum kge_flags {
  * stale fragments: set it on BOTH calls or on neither. */
 #define KGE_FLAG_CE_KEEP_QUERIES (1 << 16)
 /* The relation-grouped RESCAL entries only ("RESCAL, relation-grouped" below): the tables opt in to that route.  Without
- * the bit those entries answer KGE_ERR_UNSUPPORTED for a RESCAL table like every entry outside the RESCAL list. */
+ * the bit those entries answer KGE_ERR_UNSUPPORTED for a RESCAL table like every entry outside the RESCAL list.  The
+ * same bit opts a RESCAL table in to kge_score_so / kge_score_so_workspace_bytes / kge_score_so_bwd_accum. */
 #define KGE_FLAG_RESCAL_GROUPED (1 << 17)
 #define KGE_FLAG_RESERVE_CUS_SHIFT 8
 #define KGE_FLAG_RESERVE_CUS(n) (((n) & 255) << KGE_FLAG_RESERVE_CUS_SHIFT)
@@ -532,8 +533,14 @@ int kge_score_neg_shared(const kge_tables* t, kge_index s, kge_index p, kge_inde
  * outside [n, m] is written.  ComplEx, DistMult, TransE and RotatE on float32 / bf16 tables; other scorers and rows
  * too wide for the LDS tile (f32 dim > 1024, bf16 dim > 2048): KGE_ERR_UNSUPPORTED.  n == 0 or m == 0: KGE_OK, nothing
  * is launched.  rels.ptr == NULL with m != t->num_rel, negative sizes, ldo < m: KGE_ERR_INVALID_ARG.  workspace:
- * kge_score_so_workspace_bytes(t, n, m) bytes of device scratch (currently 0 for every shape: pass NULL); less than
- * that: KGE_ERR_WORKSPACE. */
+ * kge_score_so_workspace_bytes(t, n, m) bytes of device scratch (0 for the four scorers above: pass NULL); less than
+ * that: KGE_ERR_WORKSPACE.
+ * RESCAL: taken only where t->flags carry KGE_FLAG_RESCAL_GROUPED (float32, dim <= KGE_RESCAL_MAX_DIM, n <= 65535 * 64,
+ * m <= 65535 * 32); a plain RESCAL table, bf16 and wider dims stay KGE_ERR_UNSUPPORTED before any launch.  score =
+ * s^T M o = <vec(s o^T), vec(M)>: the GEMM [n, dim^2] x [m, dim^2]^T on v_mfma_f32_16x16x4_f32 with the outer products
+ * formed in registers, K = dim^2 walked in splits of 32 rows of M whose partial sums (the workspace: ceil(dim / 32) *
+ * n * m floats for dim > 32, else 0) are added in ascending order -- no atomics, a score depends on its three rows and
+ * dim only.  The same real number as kge_score_spo's (M^T s) . o in another association: NOT its bits. */
 int64_t kge_score_so_workspace_bytes(const kge_tables* t, int64_t n, int64_t m);
 int kge_score_so(const kge_tables* t, kge_index s, kge_index o, int64_t n, kge_index rels, int64_t m, float* out,
                  int64_t ldo, void* workspace, int64_t workspace_bytes, void* stream);
@@ -1756,7 +1763,12 @@ int kge_score_neg_shared_bwd_accum(const kge_tables* t, kge_index s, kge_index p
  * `scores` = the forward output (row pitch lds; needed for TransE / RotatE with l_norm != 1 -- NULL there:
  * KGE_ERR_INVALID_ARG --, may be NULL otherwise).  f32 tables, dim <= 1024 (odd dims included); bf16 tables and wider
  * dims: KGE_ERR_UNSUPPORTED, gradients untouched.  Rows no index names are not touched; rows that only zero weights
- * reach get +0.f added.  workspace: as kge_score_so. */
+ * reach get +0.f added.  workspace: as kge_score_so.
+ * RESCAL (KGE_FLAG_RESCAL_GROUPED, as kge_score_so; `scores` and the workspace are not read): grad_rel[rels[j]] += sum_i
+ * gout[i, j] s_i o_i^T and both entity gradients on the float32 matrix pipe.  rels.ptr == NULL: every element of
+ * grad_rel has one owner, grad_rel = grad_rel + sum in ascending pair order, no float atomics (the same bits on every
+ * run); a listed rels (it may repeat a relation): atomic adds.  grad_ent: one atomic row add per (pair, tile of 32
+ * relations). */
 int kge_score_so_bwd_accum(const kge_tables* t, kge_index s, kge_index o, int64_t n, kge_index rels, int64_t m,
                            const float* gout, int64_t ldg, const float* scores, int64_t lds, float* grad_ent,
                            int64_t grad_ent_ld, float* grad_rel, int64_t grad_rel_ld, void* workspace,

@@ -95,6 +95,14 @@ int run_so(int scorer, int dtype, const Operand& S, const Operand& R, const Oper
 int run_so_bwd_accum(int scorer, float lp, const Operand& S, const Operand& R, const Operand& O, int d, int dr,
                      long long n, long long m, const float* gout, long long ldg, const float* scores, long long lds,
                      float* ge, long long ge_ld, float* gr, long long gr_ld, hipStream_t st);
+// rescal_so.hip
+long long rescal_so_workspace_bytes(int d, long long n, long long m);
+bool rescal_so_shape_ok(long long n, long long m);
+int run_rescal_so(const Operand& S, const Operand& R, const Operand& O, int d, long long n, long long m, float* out,
+                  long long ldo, void* ws, hipStream_t st);
+int run_rescal_so_bwd_accum(const Operand& S, const Operand& R, const Operand& O, int d, long long n, long long m,
+                            const float* gout, long long ldg, float* ge, long long ge_ld, float* gr, long long gr_ld,
+                            hipStream_t st);
 int run_pairs_exact(int scorer, int dtype, bool use_mfma, const Operand& A, const Operand& R,
                     const Operand& TG, int dir, int d, int dr, long long n, long long m,
                     float lp, float* out, long long ldo, hipStream_t st, bool round_query = true,
@@ -1224,11 +1232,16 @@ int kge_score_neg_shared_bwd_accum(const kge_tables* t, kge_index s, kge_index p
 }
 
 // ---- relation prediction: KgeModel.score_so (kge_model.py:727-747) ----
+// a RESCAL table is taken (rescal_so.hip) where its flags opt in, as for the relation-grouped entries
+static bool so_rescal_opt_in(const kge_tables* t) {
+  return t && t->scorer == KGE_RESCAL && (t->flags & KGE_FLAG_RESCAL_GROUPED);
+}
+
 // the checks both entries share, in the order the header lists them; *done: nothing to launch
 static int check_so(const kge_tables* t, const kge_index& s, const kge_index& o, int64_t n, const kge_index& rels,
                     int64_t m, int64_t workspace_bytes, bool* done) {
   *done = false;
-  int rc = check_tables(t, true);
+  int rc = check_tables(t, true, false, /*rescal_ok=*/so_rescal_opt_in(t));
   if (rc) return rc;
   if (n < 0 || m < 0 || workspace_bytes < 0) return KGE_ERR_INVALID_ARG;
   if (!rels.ptr && m != t->num_rel) return KGE_ERR_INVALID_ARG;
@@ -1241,7 +1254,9 @@ static int check_so(const kge_tables* t, const kge_index& s, const kge_index& o,
 }
 
 int64_t kge_score_so_workspace_bytes(const kge_tables* t, int64_t n, int64_t m) {
-  (void)t, (void)n, (void)m;
+  // RESCAL: the partial sums of the forward's K splits
+  if (so_rescal_opt_in(t) && n > 0 && m > 0 && check_tables(t, false, false, /*rescal_ok=*/true) == KGE_OK)
+    return rescal_so_workspace_bytes((int)t->dim, n, m);
   return 0;  // cos / sin of RotatE's phases live in the LDS tile; gout and the scores are read in place
 }
 
@@ -1253,9 +1268,13 @@ int kge_score_so(const kge_tables* t, kge_index s, kge_index o, int64_t n, kge_i
   if (rc) return rc;
   if (ldo < m || (n * m > 0 && !out)) return KGE_ERR_INVALID_ARG;
   if (done) return KGE_OK;
-  if (!so_tables_ok(t->scorer, t->dtype, t->dim)) return KGE_ERR_UNSUPPORTED;
+  const bool rescal = t->scorer == KGE_RESCAL;  // (opted in: check_so)
+  if (rescal ? !rescal_so_shape_ok(n, m) : !so_tables_ok(t->scorer, t->dtype, t->dim)) return KGE_ERR_UNSUPPORTED;
   const int64_t need = kge_score_so_workspace_bytes(t, n, m);
   if (need > 0 && (!workspace || workspace_bytes < need)) return KGE_ERR_WORKSPACE;
+  if (rescal)
+    return run_rescal_so(ent_op(t, s), rel_op(t, rels), ent_op(t, o), (int)t->dim, n, m, out, ldo, workspace,
+                         (hipStream_t)stream);
   return run_so(t->scorer, t->dtype, ent_op(t, s), rel_op(t, rels), ent_op(t, o), (int)t->dim, (int)t->rel_dim, n, m,
                 t->l_norm, out, ldo, (hipStream_t)stream);
 }
@@ -1272,6 +1291,11 @@ int kge_score_so_bwd_accum(const kge_tables* t, kge_index s, kge_index o, int64_
   if (ldg < m || (scores && lds < m)) return KGE_ERR_INVALID_ARG;
   if (grad_ent_ld < t->dim || grad_rel_ld < t->rel_dim) return KGE_ERR_INVALID_ARG;
   if (done) return KGE_OK;
+  if (t->scorer == KGE_RESCAL) {  // (opted in: check_so) no workspace: every sum stays in registers and LDS
+    if (!rescal_so_shape_ok(n, m)) return KGE_ERR_UNSUPPORTED;
+    return run_rescal_so_bwd_accum(ent_op(t, s), rel_op(t, rels), ent_op(t, o), (int)t->dim, n, m, gout, ldg, grad_ent,
+                                   grad_ent_ld, grad_rel, grad_rel_ld, (hipStream_t)stream);
+  }
   if (!so_tables_ok(t->scorer, t->dtype, t->dim) || t->dtype != KGE_F32 || t->dim > 1024) return KGE_ERR_UNSUPPORTED;
   if (so_bwd_needs_scores(t->scorer, t->l_norm) && !scores) return KGE_ERR_INVALID_ARG;
   const int64_t need = kge_score_so_workspace_bytes(t, n, m);

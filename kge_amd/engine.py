@@ -1234,6 +1234,52 @@ def score_so_bwd(t: Tables, s, o, rels, gout, scores, grad_ent, grad_rel) -> boo
     return True
 
 
+def rescal_score_so_supported(dtype, d: int, n: int) -> bool:
+    """Does kge_score_so take RESCAL tables that opt in with KGE_FLAG_RESCAL_GROUPED, and `n` pairs?  (float32,
+    d <= RESCAL_MAX_DIM, at most 65535 tiles of 64 pairs; score_so_supported stays False for "rescal": a plain table is
+    declined.)"""
+    return dtype == torch.float32 and d <= RESCAL_MAX_DIM and n <= 65535 * 64
+
+
+def rescal_score_so(t: Tables, s, o, rels=None, out=None) -> torch.Tensor:
+    """[n, m] RESCAL scores s_i^T M_{rels[j]} o_i -- rels None: all relations -- as the product of the outer products
+    s_i o_i^T (formed in registers) with the relation table on the float32 matrix pipe (csrc/rescal_so.hip): none of the
+    [n m, d^2] repeats of the reference's composition (kge_model.py:202-209).  The same real number as score_spo in
+    another association: equal within the float32 bound, not bit for bit.  `out`: as score_so."""
+    if t.scorer != SCORERS["rescal"]:
+        raise ValueError("kge_amd: rescal_score_so takes 'rescal' tables")
+    keep, si, oi, n, ri, m = _so_args(t, s, o, rels, "rescal_score_so")
+    if out is None:
+        out = _empty((n, m), t.device)
+    elif (out.shape != (n, m) or out.dtype != torch.float32 or out.device != t.device
+          or (m > 1 and out.stride(1) != 1)):
+        raise ValueError("kge_amd: rescal_score_so: out must be an [n, m] float32 view with unit inner stride")
+    with _on_device(t.device):
+        tc = _grouped_tables(t)
+        need = _lib.lib().kge_score_so_workspace_bytes(ctypes.byref(tc), n, m)
+        ws = _empty((need,), t.device, torch.uint8) if need > 0 else None  # the K splits' partial sums
+        _lib.check(_lib.lib().kge_score_so(ctypes.byref(tc), si, oi, n, ri, m, out.data_ptr(),
+                                           out.stride(0) if n > 1 else max(m, 1),
+                                           None if ws is None else ws.data_ptr(), need, _stream(t.device)),
+                   "kge_score_so")
+    return out
+
+
+def rescal_score_so_bwd(t: Tables, s, o, rels, gout, grad_ent, grad_rel) -> None:
+    """Backward of rescal_score_so accumulated into the dense table gradients `grad_ent` [E, d] and `grad_rel` [R, d^2]
+    (f32, modified in place).  rels None: the relation gradient has one owner per element and no float atomics -- the
+    same bits on every run."""
+    keep, si, oi, n, ri, m = _so_args(t, s, o, rels, "rescal_score_so_bwd")
+    gout = gout.to(device=t.device, dtype=torch.float32)
+    if gout.dim() != 2 or gout.shape != (n, m) or (m > 1 and gout.stride(1) != 1) or (n > 1 and gout.stride(0) < m):
+        gout = gout.contiguous().view(n, m)
+    with _on_device(t.device):
+        _lib.check(_lib.lib().kge_score_so_bwd_accum(
+            ctypes.byref(_grouped_tables(t)), si, oi, n, ri, m, gout.data_ptr(), gout.stride(0) if n > 1 else max(m, 1),
+            None, 0, grad_ent.data_ptr(), grad_ent.stride(0), grad_rel.data_ptr(), grad_rel.stride(0), None, 0,
+            _stream_handle(t.device)), "kge_score_so_bwd_accum")
+
+
 _EMB_TC = {}
 
 

@@ -267,6 +267,10 @@ class FusedRoutes:
             return None
         ent, rel = self._w()
         scorer = self._scorer
+        if self._grouped() and self.family.name == "rescal":  # (relational Tucker3 stays composed)
+            if not rescal_score_so_fusable(ent, rel, s.numel()):
+                return None
+            return _RescalScoreSO.apply(ent, rel, s, o, p)
         if not score_so_fusable(scorer.name, ent, rel, s.numel()):
             return None
         return _ScoreSO.apply(scorer.name, scorer._norm, ent, rel, s, o, p,
@@ -1535,6 +1539,30 @@ def score_so_fusable(name: str, ent: torch.Tensor, rel: torch.Tensor, n: int) ->
     if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
         return ent.dtype == torch.float32 and rel.dtype == torch.float32 and ent.shape[1] <= 1024
     return True
+
+
+class _RescalScoreSO(torch.autograd.Function):
+    """score_so of a grouped RESCAL model: s_i^T M_j o_i as the product of the outer products s_i o_i^T with the relation
+    table on the float32 matrix pipe (engine.rescal_score_so, csrc/rescal_so.hip), none of the [n m, d^2] repeats of the
+    composition in either pass; backward = kge_score_so_bwd_accum into complete table gradients."""
+
+    @staticmethod
+    def forward(ctx, ent, rel, s, o, rels):
+        t = engine.Tables("rescal", ent.detach(), rel.detach())
+        ctx.t, ctx.idx = t, (s, o, rels)
+        return engine.rescal_score_so(t, s, o, rels)
+
+    @staticmethod
+    def backward(ctx, gout):
+        s, o, rels = ctx.idx
+        ge, gr = torch.zeros_like(ctx.t.ent), torch.zeros_like(ctx.t.rel)
+        engine.rescal_score_so_bwd(ctx.t, s, o, rels, gout, ge, gr)
+        return ge, gr, None, None, None
+
+
+def rescal_score_so_fusable(ent: torch.Tensor, rel: torch.Tensor, n: int) -> bool:
+    """Where a grouped RESCAL model's score_so runs kge_score_so: float32 tables on a GPU, dim <= RESCAL_MAX_DIM"""
+    return ent.is_cuda and rel.dtype == ent.dtype and engine.rescal_score_so_supported(ent.dtype, ent.shape[1], n)
 
 
 class _ScoreNegBlocks(torch.autograd.Function):
