@@ -256,6 +256,12 @@ def pairs_bwd(name, l_norm, direction, ent, rel, a, p, targets, gout, defect=Non
     return _run(name, l_norm, direction, ent, rel, a, p, targets, gout, defect, False, None, dtype)[0]
 
 
+def pairs_bwd_companion(name, l_norm, direction, ent, rel, a, p, targets, gout):
+    """-> (A_a, A_p, A_tgt): the companion values alone (module docstring, A).  They are linear in |gout|, so a slack on
+    the coefficients is pushed through the closed forms by passing it as gout (tests/_dense32_ref.py)."""
+    return _run(name, l_norm, direction, ent, rel, a, p, targets, gout, None, True)[1]
+
+
 def pairs_bwd_bound(name, l_norm, direction, ent, rel, a, p, targets, gout):
     """-> (b_a, b_p, b_tgt): |float32 result - pairs_bwd| <= bound elementwise (module docstring)."""
     _, comp = _run(name, l_norm, direction, ent, rel, a, p, targets, gout, None, True)
