@@ -320,6 +320,55 @@ int kge_conve_queries(const kge_conve_net* net, const float* ent, int64_t ent_ld
                       kge_index s, kge_index p, int64_t n, float* q, int64_t q_ld, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* ---- ConvE, training (conve.py:81-93 under Module.train(); csrc/conve_train.hip) -----------------------------------------
+ * The training-mode twin of the network above on DENSE rows s_emb / p_emb [n, d + 1] as the embedders return them
+ * (embedder dropout already applied), and its backward.  float32, no float atomics, two runs give the same bits.
+ *   v      = conv(images)                                          as step 2 above
+ *   vhat   = (v - mean1_c) * rsq1_c     BATCH statistics of channel c over the n * Ho * Wo values: per row tile of 32
+ *                                       (count, mean, M2), merged in ascending tile order (Chan et al.); biased variance
+ *   a      = relu(vhat) * f(row, c)     Dropout2d: a whole channel of a row is kept or dropped
+ *   u_j    = sum_k a_k proj_w[j][k] + proj_b[j]                    the chain and the channel order of step 6 above
+ *   y_j    = u_j * m(row, j)            Dropout
+ *   x_j    = relu((y_j - mean2_j) * rsq2_j)                        batch statistics of column j over the n rows
+ * rsq = 1 / sqrt(var + eps) as above.  kge_conve_net's bn*_mean / bn*_var fields are NOT read (may be NULL): the batch
+ * statistics are outputs (bn1_mean[32], bn1_var[32], bn2_mean[d], bn2_var[d], biased variances); the caller applies the
+ * running-statistics update.  With both probabilities 0, x carries the bits of q[:, 1:] that kge_conve_queries returns
+ * on the same rows with the returned statistics as running statistics.
+ *
+ * THE MASKS use the generator and the key of "Embedder dropout" below (Philox4x32-10, key = (seed low 32,
+ * (seed high 32) ^ 0x44524F50)); element e of row `row` is DROPPED iff word (e % 4) of the block with
+ *   counter = (e / 4, (uint32)row, (uint32)call, role)   role 3: Dropout2d, e = the channel c < 32
+ *                                                        role 4: Dropout,   e = the output column j < d
+ * is below thr = (uint32)floor(p * 2^32) (in double); kept: times scale = 1.0f / (1.0f - p) (host, float32), i.e. kept
+ * iff u >= p.  p == 0 draws nothing (factor 1).  The backward regenerates the masks from (seed, call); none is stored.
+ *
+ * Saved for the backward in caller-owned buffers: y [n, d] (dense) and the four statistics.  The backward takes
+ * g_x [n, d] and writes g_s_emb / g_p_emb [n, d + 1] by plain stores (column 0: +0), g_conv_w [32, fs^2], g_conv_b [32]
+ * (only with has_conv_bias; may be NULL otherwise), g_proj_w [d, F] (pitch g_proj_ld) and g_proj_b [d]; every element
+ * of them is written.  One workspace size serves both calls (no zeroing needed).
+ * Gate, before any launch: that of kge_conve_queries (KGE_ERR_INVALID_ARG in front of KGE_ERR_UNSUPPORTED; NULL train,
+ * NULL buffers with n > 0, pitches below the widths: KGE_ERR_INVALID_ARG), and KGE_ERR_UNSUPPORTED for n == 1 (a
+ * batch statistic of one row), n >= 2^31, p_feature or p_projection outside [0, 1).  n == 0: KGE_OK, nothing launched.
+ * KGE_ERR_WORKSPACE: workspace NULL or below kge_conve_train_workspace_bytes(net, n) (0 outside the gate). */
+typedef struct kge_conve_train {
+  float p_feature;    /* Dropout2d on the feature map, in [0, 1)         */
+  float p_projection; /* Dropout on the projection's output, in [0, 1)   */
+  uint64_t seed;      /* the model's dropout seed                        */
+  uint64_t call;      /* one number per forward; the backward passes it  */
+} kge_conve_train;
+
+int64_t kge_conve_train_workspace_bytes(const kge_conve_net* net, int64_t n);
+int kge_conve_train_fwd(const kge_conve_net* net, const kge_conve_train* train, const float* s_emb, int64_t s_ld,
+                        const float* p_emb, int64_t p_ld, int64_t n, float* x, int64_t x_ld, float* y, float* bn1_mean,
+                        float* bn1_var, float* bn2_mean, float* bn2_var, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int kge_conve_train_bwd(const kge_conve_net* net, const kge_conve_train* train, const float* s_emb, int64_t s_ld,
+                        const float* p_emb, int64_t p_ld, int64_t n, const float* g_x, int64_t g_x_ld, const float* y,
+                        const float* bn1_mean, const float* bn1_var, const float* bn2_mean, const float* bn2_var,
+                        float* g_s_emb, int64_t g_s_ld, float* g_p_emb, int64_t g_p_ld, float* g_conv_w, float* g_conv_b,
+                        float* g_proj_w, int64_t g_proj_ld, float* g_proj_b, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+
 /* ---- library ---------------------------------------------------------- */
 int kge_abi_version(void);
 const char* kge_status_string(int status);
@@ -1653,6 +1702,9 @@ int kge_score_neg_bwd_accum(const kge_tables* t, kge_index s, kge_index p, kge_i
  * For a gathered row occurrence, element c of the row is DROPPED iff r < thr, where
  *   r       = word (c % 4) of Philox4x32-10(counter, key)        (the generator of kge_neg_sample)
  *   counter = (c / 4, occ, (uint32)call, role)                    role: 0 = the s row, 1 = the p row, 2 = the o row
+ *                                                                 (roles 3 / 4: the two masks of ConvE's training network,
+ *                                                                 counter = (e / 4, row, (uint32)call, role): "ConvE,
+ *                                                                 training" above)
  *   key     = (seed low 32, (seed high 32) ^ 0x44524F50)          (apart from kge_neg_sample's streams of the same seed)
  *   thr     = (uint32)floor(p * 2^32), computed in double          p = p_ent for entity rows, p_rel for relation rows
  * A kept element becomes x * scale with scale = 1.0f / (1.0f - p) (one float32 division on the host, one float32

@@ -139,6 +139,11 @@ class KgeConveNet(ctypes.Structure):
                 ("bn1_eps", ctypes.c_float), ("bn2_eps", ctypes.c_float)]
 
 
+class KgeConveTrain(ctypes.Structure):
+    _fields_ = [("p_feature", ctypes.c_float), ("p_projection", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("call", ctypes.c_uint64)]
+
+
 class KgeDropout(ctypes.Structure):
     _fields_ = [("p_ent", ctypes.c_float), ("p_rel", ctypes.c_float), ("seed", ctypes.c_uint64),
                 ("call", ctypes.c_uint64)]
@@ -173,6 +178,12 @@ PROTOTYPES = {
     "kge_conve_workspace_bytes": (c_i64, [ctypes.POINTER(KgeConveNet), c_i64]),
     "kge_conve_queries": (ctypes.c_int, [ctypes.POINTER(KgeConveNet), c_vp, c_i64, c_vp, c_i64, KgeIndex, KgeIndex, c_i64,
                                          c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kge_conve_train_workspace_bytes": (c_i64, [ctypes.POINTER(KgeConveNet), c_i64]),
+    "kge_conve_train_fwd": (ctypes.c_int, [ctypes.POINTER(KgeConveNet), ctypes.POINTER(KgeConveTrain), c_vp, c_i64, c_vp,
+                                           c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "kge_conve_train_bwd": (ctypes.c_int, [ctypes.POINTER(KgeConveNet), ctypes.POINTER(KgeConveTrain), c_vp, c_i64, c_vp,
+                                           c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                           c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "kge_queries_bytes": (c_i64, [_PT, ctypes.c_int, c_i64]),
     "kge_build_queries": (ctypes.c_int, [_PT, ctypes.c_int, KgeIndex, KgeIndex, KgeIndex, c_i64, c_vp, c_i64, c_vp]),
     "kge_score_queries": (ctypes.c_int, [_PT, ctypes.c_int, c_vp, c_i64, KgeIndex, c_i64, c_vp, c_i64, c_i64,

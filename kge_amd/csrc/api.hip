@@ -34,6 +34,16 @@ bool conve_lds_ok(long long hw);
 long long conve_workspace_bytes(int d, long long n);
 int run_conve_queries(const kge_conve_net* cn, const float* ent, long long ent_ld, const float* rel, long long rel_ld,
                       const Index& s, const Index& p, long long n, float* q, long long q_ld, float* ws, hipStream_t st);
+// conve_train.hip
+long long conve_train_workspace_bytes(int d, int hw, int fs, long long n);
+int run_conve_train_fwd(const kge_conve_net* cn, const DropKey& key, const float* s_emb, long long s_ld,
+                        const float* p_emb, long long p_ld, long long n, float* x, long long x_ld, float* y, float* mean1,
+                        float* var1, float* mean2, float* var2, float* ws, hipStream_t st);
+int run_conve_train_bwd(const kge_conve_net* cn, const DropKey& key, const float* s_emb, long long s_ld,
+                        const float* p_emb, long long p_ld, long long n, const float* g_x, long long gx_ld, const float* y,
+                        const float* mean1, const float* var1, const float* mean2, const float* var2, float* g_s,
+                        long long gs_ld, float* g_p, long long gp_ld, float* g_conv_w, float* g_conv_b, float* g_proj_w,
+                        long long gpw_ld, float* g_proj_b, float* ws, hipStream_t st);
 // rescal.hip
 int run_rescal_queries(const Operand& A, const Operand* A2, const Operand& R, int dir, int d, long long n, float* q,
                        float* q2, long long q_ld, float* ones, hipStream_t st);
@@ -903,12 +913,12 @@ int kge_tucker3_project_bwd(const kge_tucker3* t, kge_index idx, int64_t n, cons
 
 // ---- ConvE (conve.hip): the gate of the two entries ("ConvE" in include/kge_amd.h states the rule) ----------------------
 // ONE pass: every KGE_ERR_INVALID_ARG condition is looked at before any KGE_ERR_UNSUPPORTED one
-static int check_conve(const kge_conve_net* c, bool need_ptrs) {
+// (stats: the running statistics are read -- not by the training entries)
+static int check_conve(const kge_conve_net* c, bool need_ptrs, bool stats = true) {
   if (!c) return KGE_ERR_INVALID_ARG;
   if (c->h < 1 || c->w < 1 || c->padding < 0) return KGE_ERR_INVALID_ARG;
-  if (need_ptrs && (!c->conv_w || !c->bn1_mean || !c->bn1_var || !c->proj_w || !c->proj_b || !c->bn2_mean ||
-                    !c->bn2_var || (c->has_conv_bias && !c->conv_b)))
-    return KGE_ERR_INVALID_ARG;
+  if (need_ptrs && (!c->conv_w || !c->proj_w || !c->proj_b || (c->has_conv_bias && !c->conv_b))) return KGE_ERR_INVALID_ARG;
+  if (need_ptrs && stats && (!c->bn1_mean || !c->bn1_var || !c->bn2_mean || !c->bn2_var)) return KGE_ERR_INVALID_ARG;
   const int64_t Ho = 2 * (int64_t)c->h - c->filter_size + 2 * (int64_t)c->padding + 1;
   const int64_t Wo = (int64_t)c->w - c->filter_size + 2 * (int64_t)c->padding + 1;
   if (Ho >= 1 && Wo >= 1 && c->proj_ld < 32 * Ho * Wo) return KGE_ERR_INVALID_ARG;  // (a pitch below the width F)
@@ -953,6 +963,80 @@ int kge_conve_queries(const kge_conve_net* net, const float* ent, int64_t ent_ld
   if (n == 0) return KGE_OK;
   if (!workspace || workspace_bytes < conve_workspace_bytes((int)d, n)) return KGE_ERR_WORKSPACE;
   return run_conve_queries(net, ent, ent_ld, rel, rel_ld, si, pi, n, q, q_ld, (float*)workspace, (hipStream_t)stream);
+}
+
+// ---- ConvE, training (conve_train.hip; "ConvE, training" in include/kge_amd.h) -------------------------------------------
+// Ho * Wo of a net that passed check_conve (in int64, as the gate computes it)
+static int64_t conve_train_hw(const kge_conve_net* c) {
+  return (2 * (int64_t)c->h - c->filter_size + 2 * (int64_t)c->padding + 1) *
+         ((int64_t)c->w - c->filter_size + 2 * (int64_t)c->padding + 1);
+}
+
+int64_t kge_conve_train_workspace_bytes(const kge_conve_net* net, int64_t n) {
+  if (n < 2 || n > 0x7fffffffLL || check_conve(net, false) != KGE_OK) return 0;
+  return conve_train_workspace_bytes(net->h * net->w, (int)conve_train_hw(net), net->filter_size, n);
+}
+
+// the shared gate of the two entries: the network, the masks, n; *go = false: return rc without a launch
+static int check_conve_train(const kge_conve_net* net, const kge_conve_train* tr, bool args_ok, int64_t n,
+                             const void* workspace, int64_t workspace_bytes, kge::DropKey* dk, bool* go) {
+  *go = false;
+  const int gate = check_conve(net, true, false);
+  if (gate == KGE_ERR_INVALID_ARG || !tr || n < 0 || !args_ok) return KGE_ERR_INVALID_ARG;
+  if (gate) return gate;
+  if (!(tr->p_feature >= 0.0f && tr->p_feature < 1.0f) || !(tr->p_projection >= 0.0f && tr->p_projection < 1.0f))
+    return KGE_ERR_UNSUPPORTED;
+  if (n == 0) return KGE_OK;
+  if (n < 2 || n > 0x7fffffffLL) return KGE_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < kge_conve_train_workspace_bytes(net, n)) return KGE_ERR_WORKSPACE;
+  dk->k0 = (unsigned)tr->seed;
+  dk->k1 = (unsigned)(tr->seed >> 32) ^ kge::KGE_DROPOUT_KEY_XOR;
+  dk->call = (unsigned)tr->call;
+  dk->thr_ent = (unsigned)floor((double)tr->p_feature * 4294967296.0);
+  dk->thr_rel = (unsigned)floor((double)tr->p_projection * 4294967296.0);
+  dk->sc_ent = 1.0f / (1.0f - tr->p_feature);
+  dk->sc_rel = 1.0f / (1.0f - tr->p_projection);
+  *go = true;
+  return KGE_OK;
+}
+
+int kge_conve_train_fwd(const kge_conve_net* net, const kge_conve_train* train, const float* s_emb, int64_t s_ld,
+                        const float* p_emb, int64_t p_ld, int64_t n, float* x, int64_t x_ld, float* y, float* bn1_mean,
+                        float* bn1_var, float* bn2_mean, float* bn2_var, void* workspace, int64_t workspace_bytes,
+                        void* stream) {
+  KGE_RANGE();
+  const int64_t d = net ? (int64_t)net->h * net->w : 0;
+  const bool ok = s_ld >= d + 1 && p_ld >= d + 1 && x_ld >= d &&
+                  (n <= 0 || (s_emb && p_emb && x && y && bn1_mean && bn1_var && bn2_mean && bn2_var));
+  kge::DropKey dk;
+  bool go;
+  const int rc = check_conve_train(net, train, ok, n, workspace, workspace_bytes, &dk, &go);
+  if (!go) return rc;
+  return run_conve_train_fwd(net, dk, s_emb, s_ld, p_emb, p_ld, n, x, x_ld, y, bn1_mean, bn1_var, bn2_mean, bn2_var,
+                             (float*)workspace, (hipStream_t)stream);
+}
+
+int kge_conve_train_bwd(const kge_conve_net* net, const kge_conve_train* train, const float* s_emb, int64_t s_ld,
+                        const float* p_emb, int64_t p_ld, int64_t n, const float* g_x, int64_t g_x_ld, const float* y,
+                        const float* bn1_mean, const float* bn1_var, const float* bn2_mean, const float* bn2_var,
+                        float* g_s_emb, int64_t g_s_ld, float* g_p_emb, int64_t g_p_ld, float* g_conv_w, float* g_conv_b,
+                        float* g_proj_w, int64_t g_proj_ld, float* g_proj_b, void* workspace, int64_t workspace_bytes,
+                        void* stream) {
+  KGE_RANGE();
+  const int64_t d = net ? (int64_t)net->h * net->w : 0;
+  // (the width of g_proj_w only where the net itself is inside the gate: outside, the gate's own status is returned)
+  const int64_t F = check_conve(net, false) == KGE_OK ? 32 * conve_train_hw(net) : 0;
+  const bool ok = s_ld >= d + 1 && p_ld >= d + 1 && g_x_ld >= d && g_s_ld >= d + 1 && g_p_ld >= d + 1 &&
+                  (F < 1 || g_proj_ld >= F) &&
+                  (n <= 0 || (s_emb && p_emb && g_x && y && bn1_mean && bn1_var && bn2_mean && bn2_var && g_s_emb &&
+                              g_p_emb && g_conv_w && g_proj_w && g_proj_b && (!net || !net->has_conv_bias || g_conv_b)));
+  kge::DropKey dk;
+  bool go;
+  const int rc = check_conve_train(net, train, ok, n, workspace, workspace_bytes, &dk, &go);
+  if (!go) return rc;
+  return run_conve_train_bwd(net, dk, s_emb, s_ld, p_emb, p_ld, n, g_x, g_x_ld, y, bn1_mean, bn1_var, bn2_mean, bn2_var,
+                             g_s_emb, g_s_ld, g_p_emb, g_p_ld, g_conv_w, g_conv_b, g_proj_w, g_proj_ld, g_proj_b,
+                             (float*)workspace, (hipStream_t)stream);
 }
 
 int kge_build_queries(const kge_tables* t, int combine, kge_index s, kge_index p, kge_index o, int64_t n,

@@ -569,6 +569,86 @@ def conve_queries(net: ConveNet, ent: torch.Tensor, rel: torch.Tensor, s, p, out
     return out
 
 
+def conve_train_supported(h: int, w: int, filter_size: int, padding: int, n: int) -> bool:
+    """Do kge_conve_train_fwd / _bwd take this shape and row count (asked of the library itself)."""
+    Ho, Wo = 2 * h - filter_size + 2 * padding + 1, w - filter_size + 2 * padding + 1
+    c = _lib.KgeConveNet(h=h, w=w, filter_size=filter_size, padding=padding, proj_ld=max(32 * Ho * Wo, 1))
+    return _lib.lib().kge_conve_train_workspace_bytes(ctypes.byref(c), int(n)) > 0
+
+
+def _conve_train_args(net: ConveNet, s_emb, p_emb, conv_w, conv_b, proj_w, proj_b, what: str):
+    """(kge_conve_net without running statistics, n, workspace, tensors to keep alive)"""
+    _require_gpu(s_emb, what + ": s_emb")
+    d, F, dev = net.dim, net.features, s_emb.device
+    for x, name in ((s_emb, "s_emb"), (p_emb, "p_emb")):
+        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != d + 1 or x.stride(1) != 1 or x.device != dev or \
+                x.shape[0] != s_emb.shape[0]:
+            raise ValueError(f"kge_amd: {what}: {name} must be float32 [n, d + 1] with unit inner stride on {dev}")
+    cw, pw, pb = conv_w.contiguous(), proj_w if proj_w.stride(1) == 1 else proj_w.contiguous(), proj_b.contiguous()
+    cb = None if conv_b is None else conv_b.contiguous()
+    for x in (cw, pw, pb) + (() if cb is None else (cb,)):
+        if x.dtype != torch.float32 or x.device != dev:
+            raise ValueError(f"kge_amd: {what}: the network's tensors must be float32 on {dev}")
+    if cw.numel() != 32 * net.filter_size ** 2 or tuple(pw.shape) != (d, F) or pb.numel() != d:
+        raise ValueError(f"kge_amd: {what}: convolution weight [32, 1, fs, fs] and projection weight [d, F] expected")
+    n = s_emb.shape[0]
+    c = _lib.KgeConveNet(net.h, net.w, net.filter_size, net.padding, 0 if cb is None else 1, 0, cw.data_ptr(),
+                         None if cb is None else cb.data_ptr(), None, None, pw.data_ptr(), pw.stride(0) if d > 1 else F,
+                         pb.data_ptr(), None, None, net.bn1_eps, net.bn2_eps)
+    need = _lib.lib().kge_conve_train_workspace_bytes(ctypes.byref(c), n)
+    if n > 0 and need <= 0:
+        _lib.check(_lib.KGE_ERR_UNSUPPORTED, what + " (the shape or the row count is outside the gate)")
+    return c, n, _empty((max(need, 16),), dev, torch.uint8), (cw, cb, pw, pb)
+
+
+def _ld(x: torch.Tensor) -> int:
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
+def conve_train_fwd(net: ConveNet, s_emb, p_emb, dropout: "Dropout"):
+    """The training-mode network of ConvE on dense rows (kge_conve_train_fwd): `net` carries the shape, the parameters
+    and the two eps (its running statistics are not read); `dropout` = Dropout(p_feature, p_projection, seed, call).
+    -> (x [n, d], saved) with saved = (y [n, d], bn1_mean [32], bn1_var [32], bn2_mean [d], bn2_var [d]): the batch
+    statistics (biased variances) and what conve_train_bwd takes."""
+    c, n, ws, keep = _conve_train_args(net, s_emb, p_emb, net.conv_w, net.conv_b, net.proj_w, net.proj_b,
+                                       "conve_train_fwd")
+    d, dev = net.dim, s_emb.device
+    x, y = _empty((n, d), dev), _empty((n, d), dev)
+    st = [_empty((k,), dev) for k in (32, 32, d, d)]
+    tr = _lib.KgeConveTrain(float(dropout.p_ent), float(dropout.p_rel), int(dropout.seed) & (2 ** 64 - 1),
+                            int(dropout.call) & (2 ** 64 - 1))
+    with _on_device(dev):
+        _lib.check(_lib.lib().kge_conve_train_fwd(
+            ctypes.byref(c), ctypes.byref(tr), s_emb.data_ptr(), _ld(s_emb), p_emb.data_ptr(), _ld(p_emb), n,
+            x.data_ptr(), d, y.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(), st[3].data_ptr(),
+            ws.data_ptr(), ws.numel(), _stream(dev)), "kge_conve_train_fwd")
+    return x, (y, *st)
+
+
+def conve_train_bwd(net: ConveNet, s_emb, p_emb, dropout: "Dropout", saved, g_x):
+    """The backward of conve_train_fwd (kge_conve_train_bwd; the masks are regenerated from `dropout`)
+    -> (g_s_emb [n, d + 1], g_p_emb [n, d + 1], g_conv_w [32, 1, fs, fs], g_conv_b [32] or None, g_proj_w [d, F],
+    g_proj_b [d])."""
+    c, n, ws, keep = _conve_train_args(net, s_emb, p_emb, net.conv_w, net.conv_b, net.proj_w, net.proj_b,
+                                       "conve_train_bwd")
+    d, F, dev, fs = net.dim, net.features, s_emb.device, net.filter_size
+    y, m1, v1, m2, v2 = saved
+    g_x = g_x if g_x.dim() == 2 and g_x.stride(1) == 1 and g_x.dtype == torch.float32 else g_x.float().contiguous()
+    g_s, g_p = _empty((n, d + 1), dev), _empty((n, d + 1), dev)
+    g_cw, g_pw, g_pb = _empty((32, 1, fs, fs), dev), _empty((d, F), dev), _empty((d,), dev)
+    g_cb = None if net.conv_b is None else _empty((32,), dev)
+    tr = _lib.KgeConveTrain(float(dropout.p_ent), float(dropout.p_rel), int(dropout.seed) & (2 ** 64 - 1),
+                            int(dropout.call) & (2 ** 64 - 1))
+    with _on_device(dev):
+        _lib.check(_lib.lib().kge_conve_train_bwd(
+            ctypes.byref(c), ctypes.byref(tr), s_emb.data_ptr(), _ld(s_emb), p_emb.data_ptr(), _ld(p_emb), n,
+            g_x.data_ptr(), _ld(g_x) if n > 0 else d, y.data_ptr(), m1.data_ptr(), v1.data_ptr(), m2.data_ptr(),
+            v2.data_ptr(), g_s.data_ptr(), d + 1, g_p.data_ptr(), d + 1, g_cw.data_ptr(),
+            None if g_cb is None else g_cb.data_ptr(), g_pw.data_ptr(), F, g_pb.data_ptr(), ws.data_ptr(), ws.numel(),
+            _stream(dev)), "kge_conve_train_bwd")
+    return g_s, g_p, g_cw, g_cb, g_pw, g_pb
+
+
 def _tucker3(B: torch.Tensor, W: torch.Tensor, what: str):
     """(kge_tucker3 descriptor, d) of a base table B [R, d_r] and a projection weight W [d^2, d_r]."""
     _require_gpu(B, what + ": the base table")

@@ -600,6 +600,11 @@ class HipConvE(ConveRoutes, _FusedScoring, _RefConvE):
             self.padded_table_max_bytes = int(self.get_option("padded_table_max_bytes"))
         except KeyError:
             pass
+        try:  # hip_conve.fused_train (kge_amd.model.ConveRoutes.enable_fused_train): off where the key is absent
+            if self.get_option("fused_train"):
+                self.enable_fused_train()
+        except KeyError:
+            pass
 
     def _fused(self) -> bool:
         ent, rel = self._w()

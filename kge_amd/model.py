@@ -936,8 +936,41 @@ class ConveNetOps:
     feature_map_dropout, projection_dropout) and shape attributes (emb_height, emb_width, filter_size, padding) -- mixed
     into ConvEScorer here and into the plugin's HipConvEScorer, whose modules the reference's constructor builds."""
 
+    fused_train = False  # the fused_train option: ConveRoutes.enable_fused_train
+    _next_dropout = None
+
+    def train_route(self, rows: Tensor, n: int) -> bool:
+        """Does network() run as the fused training node on n rows of `rows`' dtype and device:
+        the option, training mode, float32 on a GPU, stride 1, a shape and a row count inside the gate of
+        kge_conve_train_fwd."""
+        if not (self.fused_train and self.training and torch.is_grad_enabled()) or int(getattr(self, "stride", 1)) != 1:
+            return False
+        ts = (rows, self.convolution.weight, self.projection.weight, self.projection.bias)
+        if any(not t.is_cuda or t.dtype != torch.float32 for t in ts):
+            return False
+        return engine.conve_train_supported(int(self.emb_height), int(self.emb_width), int(self.filter_size),
+                                            int(self.padding), int(n))
+
+    def _update_running(self, bn, mean: Tensor, var: Tensor, count: int):
+        """torch's training-mode update of a batch-norm module's buffers (momentum, UNBIASED variance)"""
+        if not bn.track_running_stats or bn.running_mean is None:
+            return
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+            mom = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
+            bn.running_mean.mul_(1 - mom).add_(mean, alpha=mom)
+            bn.running_var.mul_(1 - mom).add_(var, alpha=mom * count / max(count - 1, 1))
+
     def network(self, s_emb: Tensor, p_emb: Tensor) -> Tensor:
         """x [n, d] of conve.py:81-93"""
+        if s_emb.dtype == p_emb.dtype and s_emb.device == p_emb.device and self.train_route(s_emb, s_emb.shape[0]):
+            dropout = self._next_dropout((self.feature_map_dropout.p, self.projection_dropout.p))
+            x, *stats = _ConveTrainNet.apply(self.kernel_net(), dropout, s_emb, p_emb, self.convolution.weight,
+                                             self.convolution.bias, self.projection.weight, self.projection.bias)
+            n, hw = s_emb.shape[0], self.projection.weight.shape[1] // 32
+            self._update_running(self.bn1, stats[0], stats[1], n * hw)
+            self._update_running(self.bn2, stats[2], stats[3], n)
+            return x
         n = p_emb.size(0)
         s2 = s_emb[:, 1:].reshape(-1, 1, int(self.emb_height), int(self.emb_width))
         p2 = p_emb[:, 1:].reshape(-1, 1, int(self.emb_height), int(self.emb_width))
@@ -968,6 +1001,35 @@ class ConveNetOps:
         else:
             out = (x * o_emb[:, 1:]).sum(-1) + o_emb[:, 0]
         return out.view(n, -1)
+
+
+class _ConveTrainNet(torch.autograd.Function):
+    """The training-mode network of ConvE as ONE node over (s_emb, p_emb, conv_w, conv_b, proj_w, proj_b):
+    kge_conve_train_fwd / kge_conve_train_bwd.  Returns x and the four batch statistics (not differentiable: the
+    caller's running-statistics update); the backward regenerates the dropout masks from the forward's record."""
+
+    @staticmethod
+    def forward(ctx, net, dropout, s_emb, p_emb, conv_w, conv_b, proj_w, proj_b):
+        s_emb, p_emb = s_emb.detach().contiguous(), p_emb.detach().contiguous()
+        net = engine.ConveNet(net.h, net.w, net.filter_size, net.padding, conv_w.detach(),
+                              None if conv_b is None else conv_b.detach(), None, None, net.bn1_eps, proj_w.detach(),
+                              proj_b.detach(), None, None, net.bn2_eps)
+        x, saved = engine.conve_train_fwd(net, s_emb, p_emb, dropout)
+        ctx.shape, ctx.dropout, ctx.has_bias = (net.h, net.w, net.filter_size, net.padding, net.bn1_eps, net.bn2_eps), dropout, \
+            conv_b is not None
+        # through save_for_backward: an in-place update of a parameter between forward and backward raises, as in torch
+        ctx.save_for_backward(s_emb, p_emb, conv_w, proj_w, proj_b, *saved, *(() if conv_b is None else (conv_b,)))
+        ctx.mark_non_differentiable(*saved[1:])
+        return (x,) + tuple(saved[1:])
+
+    @staticmethod
+    def backward(ctx, g_x, *_):
+        s_emb, p_emb, conv_w, proj_w, proj_b, *saved = ctx.saved_tensors
+        conv_b = saved.pop().detach() if ctx.has_bias else None
+        h, w, fs, pad, eps1, eps2 = ctx.shape
+        net = engine.ConveNet(h, w, fs, pad, conv_w.detach(), conv_b, None, None, eps1, proj_w.detach(), proj_b.detach(),
+                              None, None, eps2)
+        return (None, None) + engine.conve_train_bwd(net, s_emb, p_emb, ctx.dropout, tuple(saved), g_x.contiguous())
 
 
 class ConvEScorer(ConveNetOps, RelationalScorer):
@@ -1023,6 +1085,13 @@ class ConveRoutes:
         self._pad_key, self._pad_table, self._pad_ones = None, None, None
         self._gate = None  # (shape, does kge_conve_queries take it): asked of the library once per shape
 
+    def enable_fused_train(self):
+        """The fused_train option (off by default): in training mode the scorer's network() runs as _ConveTrainNet
+        (kge_conve_train_fwd / _bwd) where ConveNetOps.train_route holds; `routes` gains the counter "train"."""
+        sc = self._conve_parts()[2]
+        sc.fused_train, sc._next_dropout = True, self._next_dropout
+        self.routes["train"] = 0
+
     def kernel_route(self) -> bool:
         ent, rel, sc, pure = self._conve_parts()
         if self.training or sc.training or not pure or not ent.is_cuda or ent.dtype != torch.float32 or rel.dtype != torch.float32:
@@ -1077,20 +1146,24 @@ class ConveRoutes:
         if self.kernel_route():
             self.routes["kernel"] += 1
             return self._kernel_scores(s, p, o, combine)
-        self.routes["torch"] += 1
+        ent, _, sc, _ = self._conve_parts()
+        # (fused_train: the scorer's network() then runs as _ConveTrainNet -- the same rule, asked of the same scorer)
+        self.routes["train" if "train" in self.routes and sc.train_route(ent, s.numel()) else "torch"] += 1
         return self._torch_scores(s, p, o, combine)
 
 
 class ConvE(ConveRoutes, KgeModel):
     """kge/model/conve.py:104-144: embedders of d + 1 columns (the bias hack), score_sp and score_spo(direction="o")
-    only -- use it under reciprocal relations, as the reference says.  The routes: ConveRoutes.  A fused training forward
-    and backward of the network is not here (the follow-up)."""
+    only -- use it under reciprocal relations, as the reference says.  The routes: ConveRoutes.  fused_train=True (off by
+    default): in training mode the network's forward and backward run as kge_conve_train_fwd / _bwd (DESIGN.md section
+    44)."""
     scorer_cls = ConvEScorer
     family = FAMILIES["conve"]
 
     def __init__(self, num_entities: int, num_relations: int, dim: int, aspect_ratio=2, filter_size: int = 3,
                  padding: int = 0, feature_map_dropout: float = 0.2, projection_dropout: float = 0.3,
-                 convolution_bias: bool = True, round_dim: bool = False, padded_table_max_bytes: int = 1 << 30, **kw):
+                 convolution_bias: bool = True, round_dim: bool = False, padded_table_max_bytes: int = 1 << 30,
+                 fused_train: bool = False, **kw):
         for opt in ("fused_dist_loss", "fused_f32_loss", "score_dtype"):
             if kw.get(opt):  # no ConvE kernel behind the fused losses, no bf16 scoring
                 raise ValueError("ConvE: {} is not supported (the losses are composed from score_sp)".format(opt))
@@ -1101,6 +1174,8 @@ class ConvE(ConveRoutes, KgeModel):
         super().__init__(num_entities, num_relations, d + 1, scorer_args=net_args, **kw)
         self.padded_table_max_bytes = int(padded_table_max_bytes)
         self._init_routes()
+        if fused_train:
+            self.enable_fused_train()
 
     def _make_scorer(self, l_norm, dtype, device, scorer_args):
         return ConvEScorer(dtype=dtype, device=device, **scorer_args)
